@@ -1,7 +1,14 @@
 """Throughput benchmark of the MI355X split-CNN step (BASELINE.json metric: training samples/sec).
 
-  python bench.py [--gpus N --steps K --warmup W --batch B --topology T]
+  python bench.py [--gpus N --steps K --warmup W --batch B --topology T] [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one process per GPU, RCCL over xGMI)
+
+A plain run sets up, warms up, times the K steps and prints the result line with the headline only.
+--dump-outputs DIR also writes what the timed path left after its last step (N = 1: the trained
+parameters and the per-step losses) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output. Everything else described below (the CPU baseline, the per-kernel pass and
+roofline, the other conv presets, the drop-in modules, the K4 server loop-back, the widened config, and
+at N > 1 the server kernel pass and the side objects) runs only with --full.
 
 N = 1 (BASELINE config 2, "K2"): both stages fused on one MI355X, synthetic 1x28x28 batches of 4096,
 fp32, the whole step (client fwd -> cut hand-off -> server fwd/CE/bwd/SGD -> client bwd/SGD)
@@ -92,7 +99,19 @@ def parse():
                     help="skip the reference's step code on the drop-in modules (side object)")
     ap.add_argument("--no-hub-loopback", action="store_true",
                     help="skip the 1-GPU loopback of the K4 hub server's compute (7 clients x --micro chunks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", default=os.environ.get("SLK_BENCH_FULL") == "1",
+                    help="also run everything beside the headline: CPU baseline, per-kernel pass + roofline, the "
+                         "other conv presets, drop-in modules, K4 server loop-back, widened config, and at N > 1 "
+                         "the server kernel pass and the side objects (each still has its own --no-* switch). "
+                         "SLK_BENCH_FULL=1 in the environment does the same (for scripts that run several passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the trained parameters (float32) and the per-step "
+                         "losses (float64) of the timed trainer as DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_kernel_pass = args.no_conv_compare = args.no_dropin = True
+        args.no_hub_loopback = args.no_k5 = args.no_exchange_phase = True
+    return args
 
 
 def cpu_baseline(seconds: float):
@@ -122,6 +141,22 @@ def cpu_baseline(seconds: float):
                       f"src/server_part.py:25-58, MLflow omitted) at torch's default thread count: server={st} "
                       f"client={ct} threads (OMP_NUM_THREADS={os.environ.get('OMP_NUM_THREADS', 'unset')}), "
                       f"which alternate; affinity mask {aff} CPUs, machine nproc={d.get('nproc')} ({model})"}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array (torch tensor or sequence), float64 kept, the rest float32."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
+def loss_log_for(args, device):
+    """A loss log whose ring holds every step of this run (the default ring holds 4096)."""
+    from splitcnn.engine import LossLog
+    return LossLog(device, capacity=max(4096, args.steps + args.warmup))
 
 
 def make_pool(B, n, device, seed=42):
@@ -314,13 +349,18 @@ def run_single(args, out):
     from splitcnn.engine import CONV_DEFAULT, CONV_PRESETS
     conv = args.conv or CONV_DEFAULT
     a, b = init_models(seed=0)
-    tr = SplitTrainer(a, b, device=dev, graph=not args.no_graph, conv=conv)
+    tr = SplitTrainer(a, b, device=dev, graph=not args.no_graph, conv=conv, loss_log=loss_log_for(args, dev))
     for i in range(4):   # the pool is the loader's ring: one graph per buffer pair, captured before timing
         tr.register_inputs(X[i], Y[i])
     step = lambda i: tr.step(X[i % 4], Y[i % 4])  # noqa: E731
     dt = timed(step, args.steps, args.warmup, dev)
     losses = tr.loss_log.flush()
     out.update(value=args.steps * B / dt, ms_per_step=dt / args.steps * 1e3)
+    if args.dump_outputs:   # what the caller of step() holds after the last timed step
+        cm, sm = tr.client.model, tr.server.model
+        dump_outputs(args.dump_outputs, {"W1": cm.conv1.weight, "b1": cm.conv1.bias, "W2": sm.conv2.weight,
+                                         "b2": sm.conv2.bias, "W3": sm.fc1.weight, "b3": sm.fc1.bias,
+                                         "loss": [float(l) for _, l in losses]})
     fi, di, wi = CONV_PRESETS[conv]
     out["config"] = {"workload": "K2: split CNN (model_def.py ModelPartA+ModelPartB) both stages fused on "
                                  "1xMI355X, synthetic 1x28x28 MNIST-shape batches, fp32, HIP-graph step",
@@ -512,10 +552,15 @@ def run_wide(args, B, steps, warmup, kernel_pass_on=True):
     xs, ys = zip(*(data.batch(B) for _ in range(4)))
     X, Y = torch.stack(xs).to(dev), torch.stack(ys).to(dev)
     tr = WideTrainer(*init_wide_models(seed=0), device=dev, graph=not args.no_graph)
+    if steps + warmup > tr.loss_log.capacity:   # a ring that holds every step (set before the graphs capture it)
+        tr.server.loss_log = loss_log_for(args, dev)
     for i in range(4):
         tr.register_inputs(X[i], Y[i])
     dt = timed(lambda i: tr.step(X[i % 4], Y[i % 4]), steps, warmup, dev)
     losses = tr.loss_log.flush()
+    if args.dump_outputs:   # (the headline run only: the side-object call of main() passes none)
+        dump_outputs(args.dump_outputs, {"client_params": tr.client.params, "server_params": tr.server.params,
+                                         "loss": [float(l) for _, l in losses]})
     r = {"metric": "training samples/sec, widened split CNN (BASELINE config 5)", "value": steps * B / dt,
          "unit": "samples/s", "ms_per_step": dt / steps * 1e3, "dtype": "bf16",
          "config": {"workload": "K5: widened split CNN (conv 3-64-128-256, 3x32x32, cut [256,8,8] after conv3; "
@@ -812,15 +857,16 @@ def run_distributed(args, out, rank, world, local, wd=None):
         roof["link"] = {k: exch[k] for k in ("wire_GBps_per_link_per_direction", "wire_frac_of_measured_p2p_peak",
                                              "wire_frac_of_vendor_link")}
         out["roofline"] = roof
-        wd.phase("roofline: server kernel pass", PHASE_LIMIT_S["roofline"])
-        try:
-            settle()
-            dk = [server_kernel_pass(t, B, dev) if rank == world - 1 else None]
-            settle()
-        except Exception as e:  # noqa: BLE001 (the headline stands on its own)
-            dk = [{"error": repr(e)[:300]}]
-        dist.broadcast_object_list(dk, src=world - 1)
-        out["roofline"]["dominant_kernel"] = dk[0]
+        if args.full:
+            wd.phase("roofline: server kernel pass", PHASE_LIMIT_S["roofline"])
+            try:
+                settle()
+                dk = [server_kernel_pass(t, B, dev) if rank == world - 1 else None]
+                settle()
+            except Exception as e:  # noqa: BLE001 (the headline stands on its own)
+                dk = [{"error": repr(e)[:300]}]
+            dist.broadcast_object_list(dk, src=world - 1)
+            out["roofline"]["dominant_kernel"] = dk[0]
     else:
         out["config"]["replica_step"] = ("fused single-GPU step kernels (x3 conv2, client images, client backward "
                                          "in the dgrad epilogue) captured in a HIP graph; bucket all-reduce "
@@ -974,6 +1020,8 @@ def main():
         local = 0
     if args.gpus != world and world > 1:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE {world}", file=sys.stderr)
+    if args.dump_outputs and world > 1:
+        sys.exit("--dump-outputs writes the single-GPU trainers' outputs: run it with --gpus 1")
     out = {"metric": "training samples/sec (node) for split CNN", "value": None, "unit": "samples/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32",
@@ -1032,8 +1080,8 @@ def main():
             out["dropin_modules"] = {"error": repr(e)[:300]}
         if not args.no_k5:
             try:
-                out["widened"] = run_wide(args, args.k5_batch, max(5, min(args.steps, 20)), 3,
-                                          not args.no_kernel_pass)
+                out["widened"] = run_wide(argparse.Namespace(**{**vars(args), "dump_outputs": None}), args.k5_batch,
+                                          max(5, min(args.steps, 20)), 3, not args.no_kernel_pass)
             except Exception as e:  # the headline stands on its own
                 out["widened"] = {"error": repr(e)[:300]}
     if cpu is not None:

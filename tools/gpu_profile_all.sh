@@ -3,6 +3,9 @@
 # K5 side object, with CPU baseline), rocprofv3 kernel stats of the K2 and K5 benches, and the PMC
 # passes (tools/pmc.sh) for both configs. Stops after any crash/timeout.
 export TMPDIR=/tmp
+# every bench pass below is a --full one (CPU baseline, side objects, the kernel pass whose roofline the
+# profiled run's JSON line carries): bench.py measures only its headline otherwise
+export SLK_BENCH_FULL=1
 mkdir -p gpurun_out
 stop_if_fatal() { case "$1" in 124|134|137|139) echo "fatal rc=$1 in $2, stopping"; exit "$1";; esac; }
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1

@@ -7,6 +7,8 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 600 python -u -m pytest ${TESTS:-tests/test_gpu_parity.py} -v --timeout 200 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -3 gpurun_out/pytest_gpu.log; stop_if_fatal $rc pytest
 fi
+# the whole line (CPU baseline, roofline, side objects), which bench.py measures only with --full
+BENCH_ARGS="--full ${BENCH_ARGS:---steps 30 --warmup 5}"
 timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---steps 30 --warmup 5} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -2 gpurun_out/bench.log; stop_if_fatal $rc bench
 if [ "${PROF:-1}" = "1" ]; then
