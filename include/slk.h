@@ -222,6 +222,11 @@ int64_t slk_relu_bits_bytes(int B);
 int slk_conv2_fwd_pool_x3i(const uint16_t* act16, const float* act_amax, const float* W2, const float* b2,
                            float* pooled, uint8_t* code, int B, void* stream);
 
+/* slk_conv2_fwd_pool_x3i without the routing codes (pooled only, bitwise the same pooled): the forward of an
+ * evaluation pass, which has no backward to route (model_def.py:25-27 under model.eval()). */
+int slk_conv2_fwd_pool_x3p(const uint16_t* act16, const float* act_amax, const float* W2, const float* b2,
+                           float* pooled, int B, void* stream);
+
 /* The x3 dgrad with the client's backward fused (src/server_part.py:51 -> src/client_part.py:132 in one
  * launch, for the single-GPU step): the cut gradient is not written; each workgroup applies the client's
  * ReLU mask (relu_bits from slk_conv1_fwd_x3) and writes one slab [dW1 c*9+tap (288) | db1 c (32)] of the
@@ -229,6 +234,38 @@ int slk_conv2_fwd_pool_x3i(const uint16_t* act16, const float* act_amax, const f
 int slk_conv2_dgrad_x3_c1w(const float* dpooled, const float* dp_amax, const uint8_t* code, const float* W2,
                            const float* x, const uint32_t* relu_bits, float* client_slabs, int B, void* stream);
 int slk_conv2_dgrad_x3_c1w_nslab(int B);
+
+/* ---------------------------------------------------------------- evaluation / prediction
+ * The reference builds a test split (src/client_part.py:52,73) and never evaluates on it; these entries are the
+ * forward-only pass a user's `model.eval(); out = model(x); criterion(out, y); out.argmax(1)` loop needs, with the
+ * metrics summed on the device (no host sync per batch). pred is i64 [B]: argmax of the sample's logits, the first
+ * maximum on exact ties, a NaN logit counting as the maximum (numpy.argmax). */
+
+/* The fc head in evaluation mode: slk_fc_logits_xent's logits stage (bitwise its logits), then loss_i =
+ * logsumexp(z) - z[y] (bitwise its loss_i) and pred; no dlogits. logits may be NULL (not stored). labels may be
+ * NULL (predict only): loss_i is then not written and err_flag not touched. A label outside [0, 10) sets *err_flag
+ * (may be NULL) and gives loss_i = NaN. Replaces model_def.py:28 + the criterion of server_part.py:49 in eval. */
+int slk_fc_eval(const float* pooled, const float* W3, const float* b3, const int64_t* labels, float* logits,
+                float* loss_i, int64_t* pred, int* err_flag, int B, void* stream);
+
+/* The same loss_i / pred stage (bit for bit) for logits f32 [B,10] already in memory: slk_wide_head_fwd's, the
+ * drop-in modules', the U-shaped head's. labels / loss_i / err_flag as in slk_fc_eval. */
+int slk_eval_logits(const float* logits, const int64_t* labels, int B, float* loss_i, int64_t* pred, int* err_flag,
+                    void* stream);
+
+/* Adds one batch to the metric accumulator `acc`: 104 x 8 bytes of device memory (8-byte aligned), zeroed by the
+ * caller before the first batch, updated by one workgroup per launch with plain read-modify-writes (launches on
+ * one stream are ordered; do not update one accumulator from two streams at once):
+ *   acc[0]                   i64  n           samples seen
+ *   acc[1]                   i64  correct     pred == label
+ *   acc[2]                   i64  bad_labels  labels outside [0, 10)
+ *   acc[3]                   f64  loss_sum    sum of loss_i (float64, fixed order: a function of the inputs and B)
+ *   acc[4 + 10 label + pred] i64  confusion counts
+ * A sample with an out-of-range label counts in n and bad_labels only. Replaces the host-side
+ * `correct += (pred == y).sum().item(); loss += ...item()` of an evaluation loop. */
+int slk_eval_accumulate(const float* loss_i, const int64_t* pred, const int64_t* labels, int B, int64_t* acc,
+                        void* stream);
+#define SLK_EVAL_ACC_WORDS 104
 
 /* ---------------------------------------------------------------- reductions / optimizer */
 

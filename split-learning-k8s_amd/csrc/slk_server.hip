@@ -16,6 +16,7 @@
 //
 // The fc1 / cross-entropy head is tiny (0.6 % of FLOPs) and HBM/L2-bound: VALU kernels.
 #include "slk_common.h"
+#include "slk_eval.h"
 
 using namespace slk;
 
@@ -504,7 +505,8 @@ extern "C" int slk_conv2_wgrad_direct_nslab(int B) { return B > 0 ? (2 * B < C2W
 // ============================================================================ fc1 + cross-entropy
 // FCH_S = 16 samples per 512-thread workgroup (B = 4096: one workgroup per CU, one dispatch round).
 // MODE bits: 1 = fc forward (logits), 2 = cross-entropy fwd+bwd, 4 = fc input gradient (dpooled =
-// dlogits @ W3, + dp_amax = per-sample max |dpooled| when asked).
+// dlogits @ W3, + dp_amax = per-sample max |dpooled| when asked), 8 = evaluation (with 1 only: loss_i and
+// pred = argmax from the logits just reduced, slk_eval_row; logits / labels may be null).
 // Logits on v_mfma_f32_16x16x4_f32 (A = 16 samples x 4 features, B = 4 features x 16 classes, 10 used):
 // wave w owns features [1152 w, 1152 (w + 1)) and streams them in 18 chunks of 64 features — the 16
 // sample rows and W3's 10 rows of the chunk — by LDS-DMA into its own two slots (no barrier in the
@@ -550,7 +552,8 @@ __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
     const float* __restrict__ pooled, const float* __restrict__ W3, const float* __restrict__ b3,
     const int64_t* __restrict__ labels, float* __restrict__ logits, float* __restrict__ loss_i,
     float* __restrict__ dlogits, float* __restrict__ dpooled, float grad_scale, int* err_flag, int B,
-    float* __restrict__ dp_amax) {
+    float* __restrict__ dp_amax, int64_t* __restrict__ pred = nullptr) {
+    static_assert((MODE & 8) == 0 || MODE == 9, "evaluation mode = the logits stage + loss_i / pred, nothing else");
     __shared__ __attribute__((aligned(1024))) char smem[(MODE & 1) ? FCH_W * FCH_NS * FCH_SLOT : 16];
     __shared__ __attribute__((aligned(16))) f32x4 red[(MODE & 1) ? FCH_W * 64 : 1];
     __shared__ float zl[FCH_S][NCLS];
@@ -639,7 +642,9 @@ __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
             if (n < NCLS && s < FCH_S) {  // (FCH_S = 8: MFMA rows 8-15 read stand-in rows, never stored)
                 v += b3[n];
                 zl[s][n] = v;
-                if (s < ns) logits[(size_t)(s0 + s) * NCLS + n] = v;
+                if constexpr ((MODE & 8) != 0) {  // evaluation: the logits are optional
+                    if (s < ns && logits) logits[(size_t)(s0 + s) * NCLS + n] = v;
+                } else if (s < ns) logits[(size_t)(s0 + s) * NCLS + n] = v;
             }
         }
         __syncthreads();
@@ -649,6 +654,15 @@ __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
             zl[s][jj] = s < ns ? logits[(size_t)(s0 + s) * NCLS + jj] : 0.f;
         }
         __syncthreads();
+    }
+
+    if constexpr ((MODE & 8) != 0) {  // evaluation: loss_i (with labels) and pred from zl; no dlogits, no dl
+        if (tid < ns) {
+            float z[NCLS];
+#pragma unroll
+            for (int jj = 0; jj < NCLS; ++jj) z[jj] = zl[tid][jj];
+            slk_eval_row(z, labels, (size_t)(s0 + tid), loss_i, pred, err_flag);
+        }
     }
 
     if constexpr ((MODE & 2) != 0) {
@@ -857,6 +871,16 @@ extern "C" int slk_fc_logits_xent(const float* pooled, const float* W3, const fl
     SLK_CHECK_ARG(pooled && W3 && b3 && labels && logits && loss_i && dlogits);
     fc_head16_kernel<3><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
         pooled, W3, b3, labels, logits, loss_i, dlogits, nullptr, grad_scale, err_flag, B, nullptr);
+    return slk_launch_status();
+}
+
+extern "C" int slk_fc_eval(const float* pooled, const float* W3, const float* b3, const int64_t* labels, float* logits,
+                           float* loss_i, int64_t* pred, int* err_flag, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(pooled && W3 && b3 && pred && (!labels || loss_i));
+    fc_head16_kernel<9><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
+        pooled, W3, b3, labels, logits, loss_i, nullptr, nullptr, 0.f, err_flag, B, nullptr, pred);
     return slk_launch_status();
 }
 

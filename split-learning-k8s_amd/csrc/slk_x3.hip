@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void row_amax_kernel(const float* __restrict__
 //      (8 conflict-free ds_read_b32), scales, splits and writes them as two f16 planes [pixel][ci]
 //      (64 B per pixel; chunk slot kc ^ (x & 2) makes every ds_read_b128 of the MFMA loop
 //      conflict-free, tools-checked for all 9 taps).
-// One `s_waitcnt vmcnt` (allowing the previous epilogue's 12 stores to stay in flight) + barrier per
+// One `s_waitcnt vmcnt` (allowing the previous epilogue's stores — 4 per wave, 2 without codes — to stay in flight) + barrier per
 // unit. 8 waves (2 per SIMD): wave = (co half ch, window row wr); its 2 x 9 taps x (h, l) weight
 // fragments (144 VGPRs) stay in registers for the launch. Tried and slower: 4 waves (one per SIMD)
 // holding all 64 co — weights copied back from AGPRs per MFMA by hipcc 0.375 ms; taps 0-7 in AGPRs as
@@ -225,16 +225,18 @@ __device__ __forceinline__ void x3f_t4(uint32_t& r0, uint32_t& r1, uint32_t& r2,
     r2 = s[0];
     r3 = s[1];
 }
+// CODE = false (the evaluation forward): pooled only — no code transpose, no code store (crow is not used)
+template <bool CODE = true>
 __device__ __forceinline__ void x3f_store_row(float m0, float m1, float m2, uint32_t c0, uint32_t c1, uint32_t c2,
                                               int kc, float* __restrict__ prow, uint8_t* __restrict__ crow) {
     uint32_t v0 = __float_as_uint(m0), v1 = __float_as_uint(m1), v2 = __float_as_uint(m2), v3 = 0u;
     uint32_t q3 = 0u;
     x3f_t4(v0, v1, v2, v3);
-    x3f_t4(c0, c1, c2, q3);
+    if constexpr (CODE) x3f_t4(c0, c1, c2, q3);
     if (kc < 3) {
         *reinterpret_cast<float4*>(prow + 4 * kc) =
             make_float4(__uint_as_float(v0), __uint_as_float(v1), __uint_as_float(v2), __uint_as_float(v3));
-        *reinterpret_cast<uint32_t*>(crow + 4 * kc) = c0 | (c1 << 8) | (c2 << 16) | (q3 << 24);
+        if constexpr (CODE) *reinterpret_cast<uint32_t*>(crow + 4 * kc) = c0 | (c1 << 8) | (c2 << 16) | (q3 << 24);
     }
 }
 
@@ -244,13 +246,27 @@ __device__ __forceinline__ void x3f_store_row(float m0, float m1, float m2, uint
 // by LDS-DMA two units ahead into a 3-deep ring of f16 buffers — no f32 rows, no split.
 // AMX = true (IN16 false, act16 required): amax is not read; the per-sample max |act| is computed here
 // (layout above X3F_SP16) and written to amax_out.
-template <bool IN16, bool AMX = false>
+// CODE = false (IN16 only; the evaluation forward): no routing codes — `code` is not used, each epilogue
+// row is one store instead of two, and the counted wait at the top of a unit uses that count (NSTORE).
+template <bool IN16, bool AMX = false, bool CODE = true>
 __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
     const float* __restrict__ act, const float* __restrict__ amax, const float* __restrict__ W2,
     const float* __restrict__ b2, float* __restrict__ pooled, uint8_t* __restrict__ code, int B,
     uint16_t* __restrict__ act16 = nullptr, float* __restrict__ amax_out = nullptr) {
     static_assert(3 * X3F_BUF <= 2 * X3F_BUF + 2 * X3F_RAW, "IN16 ring fits");
     static_assert(!(IN16 && AMX), "AMX reads f32 rows");
+    static_assert(CODE || IN16, "the code-less forward reads act16 images");
+    // epilogue global stores per wave and unit (pooled + code rows, or pooled rows alone): the counted wait at
+    // the top of a unit derives from it. IN16: in one unit a wave issues, in order, [Q] F0 F1 S.. F2 F3 S.. —
+    // the image quarter Q (waves 0-1 only), the 4 full DMA pieces of unit u+2's image, and NSTORE stores in two
+    // groups (NSTORE / 2 each). At the top of unit u the image of unit u was issued during unit u-2, its last
+    // piece being that unit's F3; after it the wave has issued the last NSTORE / 2 stores of unit u-2, then
+    // unit u-1's [Q] + 4 F + NSTORE stores. vmcnt(NSTORE + 4) lets exactly unit u-1's 4 F + NSTORE stay in
+    // flight (its Q too must land on waves 0-1: conservative), so everything of unit u-2 has landed. The
+    // addend 4 is the full pieces per wave and unit, not the 5 DMA instructions waves 0-1 issue. A count
+    // kept at X3F_STORES + 4 with CODE = false would allow 2 more: unit u-2's last store and its F3, a piece
+    // of the image this unit is about to read.
+    constexpr int NSTORE = CODE ? X3F_STORES : X3F_NT;
     constexpr int SMEM = 2 * X3F_BUF + 2 * X3F_RAW + (AMX ? X3F_CI * 1024 : 0);
     static_assert(SMEM + 64 <= 163840, "LDS");
     __shared__ __attribute__((aligned(1024))) char smem[SMEM];
@@ -476,10 +492,11 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
     for (; u < u1; ++u, ++k) {
         const int cb = k & 1;
         // unit u+G's raw rows (issued one unit ago) have landed; the previous epilogue's stores may stay
-        // IN16: unit u's image (issued two units ago) has landed; unit u+G's DMA (at most 5 wave-
-        // instructions, issued one unit ago) and the previous epilogue's stores may stay in flight
-        if constexpr (IN16) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(X3F_STORES + 4) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(X3F_STORES) : "memory");
+        // IN16: unit u's image (issued two units ago) has landed; unit u+1's image DMA (4 full pieces per
+        // wave, issued one unit ago) and the previous epilogue's NSTORE stores may stay in flight (derivation
+        // at NSTORE)
+        if constexpr (IN16) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE + 4) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE) : "memory");
         __syncthreads();
         const int kr = k % 3;  // IN16 ring slot of unit u
         if constexpr (AMX) {
@@ -544,7 +561,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
                         uint32_t c2;
                         pool_piece(pend[nt], p_pre, p_us, bias[nt], m2, c2);
                         const size_t ro = p_o + nt * 16 * P_WIN;
-                        x3f_store_row(hm[0][nt], hm[1][nt], m2, hc[0][nt], hc[1][nt], c2, kc, pooled + ro, code + ro);
+                        x3f_store_row<CODE>(hm[0][nt], hm[1][nt], m2, hc[0][nt], hc[1][nt], c2, kc, pooled + ro, CODE ? code + ro : nullptr);
                     } else {
                         pool_piece(acc[mt - 1][nt], pre_, us_, bias[nt], hm[mt - 1][nt], hc[mt - 1][nt]);
                     }
@@ -612,7 +629,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
             uint32_t c2;
             pool_piece(pend[nt], p_pre, p_us, bias[nt], m2, c2);
             const size_t ro = p_o + nt * 16 * P_WIN;
-            x3f_store_row(hm[0][nt], hm[1][nt], m2, hc[0][nt], hc[1][nt], c2, kc, pooled + ro, code + ro);
+            x3f_store_row<CODE>(hm[0][nt], hm[1][nt], m2, hc[0][nt], hc[1][nt], c2, kc, pooled + ro, CODE ? code + ro : nullptr);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA outlives the workgroup
@@ -2474,6 +2491,18 @@ extern "C" int slk_conv2_fwd_pool_x3i(const uint16_t* act16, const float* act_am
     const int U = 3 * B;
     hipLaunchKernelGGL(conv2_fwd_pool_x3_kernel<true>, dim3(U < X3F_GRID ? U : X3F_GRID), dim3(X3F_THREADS), 0,
                        slk_stream(stream), nullptr, act_amax, W2, b2, pooled, code, B, const_cast<uint16_t*>(act16));
+    return slk_launch_status();
+}
+
+extern "C" int slk_conv2_fwd_pool_x3p(const uint16_t* act16, const float* act_amax, const float* W2, const float* b2,
+                                      float* pooled, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(act16 && act_amax && W2 && b2 && pooled);
+    const int U = 3 * B;
+    hipLaunchKernelGGL((conv2_fwd_pool_x3_kernel<true, false, false>), dim3(U < X3F_GRID ? U : X3F_GRID),
+                       dim3(X3F_THREADS), 0, slk_stream(stream), nullptr, act_amax, W2, b2, pooled, nullptr, B,
+                       const_cast<uint16_t*>(act16));
     return slk_launch_status();
 }
 

@@ -15,4 +15,7 @@ def __getattr__(name):
     if name in ("ClientStage", "ServerStage", "SplitTrainer", "LossLog"):
         from . import engine
         return getattr(engine, name)
+    if name in ("EvalMetrics", "EvalResult", "evaluate_logits"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(name)

@@ -74,6 +74,11 @@ _SIGS = {
     "slk_conv1_fwd_x3": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
     "slk_relu_bits_bytes": [_I],
     "slk_conv2_fwd_pool_x3i": [_P, _P, _P, _P, _P, _P, _I, _P],
+    "slk_conv2_fwd_pool_x3p": [_P, _P, _P, _P, _P, _I, _P],
+    # evaluation / prediction
+    "slk_fc_eval": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "slk_eval_logits": [_P, _P, _I, _P, _P, _P, _P],
+    "slk_eval_accumulate": [_P, _P, _P, _I, _P, _P],
     "slk_conv2_dgrad_x3_c1w": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
     "slk_conv2_dgrad_x3_c1w_nslab": [_I],
     "slk_reduce_slabs": [_P, _I, _I, _P, _I, _P],

@@ -216,6 +216,24 @@ class ClientStage:
             ops.conv1_fwd_x3(x, self.W1.detach(), self.b1.detach(), act_amax, act16)
         self._x, self._act, self._act_amax, self._act16 = x, None, act_amax, act16
 
+    def forward_eval(self, x: torch.Tensor):
+        """The client forward of an evaluation pass: returns (act, act_amax, act16) in this stage's own
+        `eval_` buffers — the x3 operand (act None) when emit_act16, else the f32 act (+ act_amax when
+        emit_amax). Keeps nothing for a backward and leaves _x / _act / _act16 / _relu_bits alone, so a
+        training forward ... backward_step sequence with an evaluation in between still works."""
+        B = x.shape[0]
+        if self.emit_act16:
+            amax = self._buf.get("eval_act_amax", (B,), torch.float32, self.device)
+            a16 = self._buf.get("eval_act16", (ops.conv2_act16_bytes(B),), torch.uint8, self.device)
+            with TIMER("eval_conv1_fwd"):
+                ops.conv1_fwd_x3(x, self.W1.detach(), self.b1.detach(), amax, a16)
+            return None, amax, a16
+        act = self._buf.get("eval_act", (B, 32, 26, 26), torch.float32, self.device)
+        amax = self._buf.get("eval_act_amax", (B,), torch.float32, self.device) if self.emit_amax else None
+        with TIMER("eval_conv1_fwd"):
+            ops.conv1_fwd(x, self.W1.detach(), self.b1.detach(), out=act, act_amax=amax)
+        return act, amax, None
+
     def _slabs(self, cut_grad, x, act, tag="slabs"):
         x = self._x if x is None else x
         act = self._act if act is None else act
@@ -269,6 +287,8 @@ class ServerStage:
             [m.conv2.weight, m.conv2.bias, m.fc1.weight, m.fc1.bias], self.device)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
+        self.eval_logits = None   # the logits of the last evaluate() (a stage buffer)
         self.fuse_optim = True  # step_request: SGD of both slab kinds + the loss log in one launch
         # launch order knobs (profiling, tools/ab_trainers.py): fc1 wgrad right after the head (pooled
         # just read by it), conv2 wgrad before the dgrad. Defaults: the measured fastest order.
@@ -455,6 +475,53 @@ class ServerStage:
         if int(self.err_flag.item()) != 0:
             raise IndexError("splitcnn: a label was out of range [0, 10)")
 
+    def evaluate(self, act: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, *,
+                 act16: Optional[torch.Tensor] = None, act_amax: Optional[torch.Tensor] = None,
+                 metrics=None, logits: Optional[torch.Tensor] = None):
+        """Forward only (model.eval(); outputs = model(act); criterion(outputs, labels); outputs.argmax(1)):
+        returns (pred i64 [B], loss_i f32 [B]); labels=None predicts only (loss_i is None). With act16 +
+        act_amax on the 'x3' preset the code-less image forward runs (slk_conv2_fwd_pool_x3p); with an f32
+        act (a remote client, any conv preset) the preset's own forward does, its routing codes going to
+        scratch. Then the fc head in evaluation mode (slk_fc_eval): logits and loss_i are bitwise the
+        training forward's. `metrics` (metrics.EvalMetrics) receives the batch; `logits` (f32 [B, 10])
+        receives the logits instead of this stage's buffer (self.eval_logits either way).
+        Every buffer is this call's own (`eval_` names: about 0.15 GB of pooled at B = 4096 here, 0.35 GB
+        of images in ClientStage.forward_eval) and the label flag is eval_err_flag: parameters, gradients,
+        the training buffers, err_flag and the loss log are not written."""
+        m = self.model
+        W2, b2 = m.conv2.weight.detach(), m.conv2.bias.detach()
+        W3, b3 = m.fc1.weight.detach(), m.fc1.bias.detach()
+        fi = self.impl_fwd
+        if act16 is not None:
+            if fi != "x3" or act_amax is None:
+                raise ValueError("act16 input needs the x3 forward (conv preset 'x3' or 'x3w') and act_amax")
+            B = ops.batch_of(act_amax, (), "act_amax")
+            pooled = self._b("eval_pooled", (B, 64, 12, 12))
+            with TIMER("eval_conv2_fwd_pool"):
+                ops.conv2_fwd_pool_x3p(act16, act_amax, W2, b2, pooled=pooled)
+        else:
+            if act is None:
+                raise ValueError("evaluate needs act, or act16 + act_amax")
+            B = ops.batch_of(act, (32, 26, 26), "act")
+            if act_amax is None and fi == "x3":
+                act_amax = ops.row_amax(act, out=self._b("eval_act_amax", (B,)))
+            pooled = self._b("eval_pooled", (B, 64, 12, 12))
+            with TIMER("eval_conv2_fwd_pool"):
+                ops.conv2_fwd_pool(act, W2, b2, pooled=pooled, code=self._b("eval_code", (B, 64, 12, 12), torch.uint8),
+                                   impl=fi, act_amax=act_amax if fi == "x3" else None)
+        logits = logits if logits is not None else self._b("eval_logits", (B, 10))
+        with TIMER("eval_fc"):
+            _, loss_i, pred = ops.fc_eval(pooled, W3, b3, labels, logits=logits,
+                                          loss_i=self._b("eval_loss_i", (B,)) if labels is not None else None,
+                                          pred=self._b("eval_pred", (B,), torch.int64), err_flag=self.eval_err_flag)
+        self.eval_logits = logits
+        if metrics is not None:
+            if labels is None:
+                raise ValueError("metrics need labels")
+            with TIMER("eval_accumulate"):
+                metrics.update(loss_i, pred, labels)
+        return pred, loss_i
+
 
 def _n_caller_graphs(tr, B: int) -> int:
     return sum(1 for k in tr._graphs if isinstance(k, tuple) and k[0] == B)
@@ -502,6 +569,72 @@ def select_graph(tr, x, y):
     return g
 
 
+def _eval_graph_for(tr, B: int, metrics, x_tail: tuple):
+    """Trainer `tr`'s evaluation pass for batch size B as a HIP graph on static inputs: one linear chain on
+    one stream (client forward, server forward, head, accumulate), kept in `tr._eval_graphs` — not `_graphs`,
+    whose keys the step's caller-buffer budget counts. The accumulator of `metrics` is baked in: another
+    metrics object (or none) recaptures on the same static inputs. Warm-up and capture leave the accumulator
+    and the evaluation label flag as they were. Shared by SplitTrainer and wide.WideTrainer (`_eval_eager`)."""
+    g = tr._eval_graphs.get(B)
+    if g is not None and g["metrics"] is metrics:
+        return g
+    if g is None:
+        x = torch.zeros((B,) + x_tail, dtype=torch.float32, device=tr.device)
+        y = torch.zeros((B,), dtype=torch.int64, device=tr.device)
+    else:
+        x, y = g["x"], g["y"]
+    state = [tr.server.eval_err_flag] + ([metrics.acc] if metrics is not None else [])
+    saved = [t.clone() for t in state]
+    s = torch.cuda.Stream(tr.device)
+    s.wait_stream(torch.cuda.current_stream(tr.device))
+    with torch.cuda.stream(s):
+        tr._eval_eager(x, y, metrics)
+    torch.cuda.current_stream(tr.device).wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        out = tr._eval_eager(x, y, metrics)
+    for t, v in zip(state, saved):
+        t.copy_(v)
+    # the buffers this graph writes: a replay runs no Python, so eval_batch_on re-points the public
+    # attributes (server.eval_logits, and the wide trainer's eval_cut) at them after every replay
+    g = {"graph": graph, "x": x, "y": y, "metrics": metrics, "out": out, "logits": tr.server.eval_logits,
+         "cut": getattr(tr, "eval_cut", None)}
+    tr._eval_graphs[B] = g
+    return g
+
+
+def eval_batch_on(tr, x, y, metrics, x_tail: tuple):
+    """One evaluation batch on trainer `tr`, asynchronous: returns (pred, loss_i), stage buffers that the
+    next batch of the same size overwrites."""
+    if tuple(x.shape[1:]) != x_tail or tuple(y.shape) != (x.shape[0],):
+        raise ValueError(f"eval_batch: expected x [B,{','.join(map(str, x_tail))}] and y [B], got "
+                         f"{tuple(x.shape)} and {tuple(y.shape)}")
+    if not tr.graph:
+        return tr._eval_eager(x, y, metrics)
+    g = _eval_graph_for(tr, x.shape[0], metrics, x_tail)
+    g["x"].copy_(x, non_blocking=True)
+    g["y"].copy_(y, non_blocking=True)
+    g["graph"].replay()
+    tr.server.eval_logits = g["logits"]   # this batch size's buffers (another size may have run since)
+    if g["cut"] is not None:
+        tr.eval_cut = g["cut"]
+    return g["out"]
+
+
+def evaluate_on(tr, batches, metrics=None):
+    """Evaluate trainer `tr` over an iterable of device (x, y) batches; one host sync, at the end. With
+    metrics=None the trainer's own EvalMetrics is reset and used; a caller's `metrics` is added to as it is
+    (reset it first for a fresh evaluation)."""
+    from .metrics import EvalMetrics
+    if metrics is None:
+        if tr._eval_metrics is None:
+            tr._eval_metrics = EvalMetrics(tr.device)
+        metrics = tr._eval_metrics.reset()
+    for x, y in batches:
+        tr.eval_batch(x, y, metrics)
+    return metrics.result()
+
+
 class SplitTrainer:
     """Both stages fused on ONE GPU (BASELINE config 2): the cut tensor is handed over in place.
 
@@ -531,6 +664,8 @@ class SplitTrainer:
         self.graph_inputs = graph_inputs
         self._seen = {}   # (B, x ptr, y ptr) -> times a caller buffer pair went through the static inputs
         self.global_step = 0
+        self._eval_graphs = {}    # batch size -> the evaluation pass's graph (never in _graphs)
+        self._eval_metrics = None  # evaluate()'s own accumulator, made on first use
 
     @property
     def loss_log(self) -> LossLog:
@@ -616,3 +751,30 @@ class SplitTrainer:
             self._eager(x, y)
         self.server.loss_log.note_step(self.global_step)
         self.global_step += 1
+
+    # ---- evaluation / prediction: forward only, own `eval_` buffers, no training state touched
+    def _eval_eager(self, x, y, metrics=None):
+        act, amax, a16 = self.client.forward_eval(x)
+        return self.server.evaluate(act, y, act16=a16, act_amax=amax, metrics=metrics)
+
+    def eval_batch(self, x: torch.Tensor, y: torch.Tensor, metrics=None):
+        """One held-out batch, asynchronous: (pred, loss_i) (stage buffers; the logits are in
+        server.eval_logits), `metrics` (metrics.EvalMetrics) updated on the device. With graph=True the
+        pass replays a graph captured once per batch size on static inputs that x and y are copied into.
+        The graph holds the accumulator of `metrics`: calling with another metrics object (or none, or
+        alternating with evaluate(), which uses the trainer's own) captures that size again — a warm-up
+        and a capture each switch — so keep to one EvalMetrics per trainer in a loop.
+        Parameters, gradients, the loss log, err_flag and global_step are not touched; the evaluation
+        buffers cost about 0.5 GB extra at B = 4096."""
+        return eval_batch_on(self, x, y, metrics, (1, 28, 28))
+
+    def evaluate(self, batches, metrics=None):
+        """metrics.EvalResult over an iterable of device (x, y) batches — for example
+        DeviceLoader(MnistIDX(root, train=False), 4096, shuffle=False) — with one host sync at the end."""
+        return evaluate_on(self, batches, metrics)
+
+    def predict(self, x: torch.Tensor, return_logits: bool = False):
+        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""
+        act, amax, a16 = self.client.forward_eval(x)
+        pred, _ = self.server.evaluate(act, None, act16=a16, act_amax=amax)
+        return (pred.clone(), self.server.eval_logits.clone()) if return_logits else pred.clone()

@@ -250,6 +250,64 @@ def _labels(labels, B):
     return labels.data_ptr()
 
 
+# ------------------------------------------------------------------------------------ evaluation / prediction
+EVAL_ACC_WORDS = 104  # int64 words of the metric accumulator (include/slk.h, slk_eval_accumulate)
+
+
+def conv2_fwd_pool_x3p(act16, act_amax, W2, b2, pooled=None):
+    """conv2_fwd_pool_x3i without the routing codes (the evaluation forward): the same pooled, bitwise."""
+    B = batch_of(act_amax, (), "act_amax")
+    pooled = _out(pooled, (B, 64, 12, 12), act_amax, name="pooled")
+    _lib.call("slk_conv2_fwd_pool_x3p", _act16(act16, B), _dev(act_amax, "act_amax", (B,)),
+              _dev(W2, "conv2.weight", (64, 32, 3, 3)), _dev(b2, "conv2.bias", (64,)), _dev(pooled, "pooled"),
+              B, _stream(act_amax))
+    return pooled
+
+
+def _eval_outs(like, B, labels, loss_i, pred, err_flag):
+    pred = _out(pred, (B,), like, torch.int64, "pred")
+    lptr = eptr = None
+    if labels is not None:
+        lptr = _labels(labels, B)
+        loss_i = _out(loss_i, (B,), like, name="loss_i")
+        eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    liptr = _dev(loss_i, "loss_i", (B,)) if loss_i is not None else None
+    return pred, loss_i, lptr, liptr, eptr
+
+
+def fc_eval(pooled, W3, b3, labels=None, logits=None, loss_i=None, pred=None, err_flag=None, store_logits=True):
+    """The fc head in evaluation mode (slk_fc_eval): fc_logits_xent's logits and loss_i bitwise, plus pred =
+    argmax (int64 [B], first maximum on ties, NaN counts as the maximum); no dlogits. labels=None predicts only
+    (loss_i, when given, is left as it is). store_logits=False does not write the logits (returned as None).
+    Returns (logits, loss_i, pred)."""
+    B = _pooled_batch(pooled)
+    logits = _out(logits, (B, 10), pooled, name="logits") if store_logits else None
+    pred, loss_i, lptr, liptr, eptr = _eval_outs(pooled, B, labels, loss_i, pred, err_flag)
+    _lib.call("slk_fc_eval", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)), _dev(b3, "fc1.bias", (10,)),
+              lptr, _dev(logits, "logits") if logits is not None else None, liptr, _dev(pred, "pred", dtype=torch.int64),
+              eptr, B, _stream(pooled))
+    return logits, loss_i, pred
+
+
+def eval_logits(logits, labels=None, loss_i=None, pred=None, err_flag=None):
+    """fc_eval's loss_i / pred stage (the same bits) for f32 [B, 10] logits already in memory (slk_eval_logits).
+    Returns (loss_i, pred); labels=None predicts only."""
+    B = batch_of(logits, (10,), "logits")
+    pred, loss_i, lptr, liptr, eptr = _eval_outs(logits, B, labels, loss_i, pred, err_flag)
+    _lib.call("slk_eval_logits", _dev(logits, "logits"), lptr, B, liptr, _dev(pred, "pred", dtype=torch.int64), eptr,
+              _stream(logits))
+    return loss_i, pred
+
+
+def eval_accumulate(loss_i, pred, labels, acc):
+    """Add one batch to the device metric accumulator `acc` (int64 [EVAL_ACC_WORDS]; layout in include/slk.h):
+    one launch, no host sync (slk_eval_accumulate)."""
+    B = batch_of(loss_i, (), "loss_i")
+    _lib.call("slk_eval_accumulate", _dev(loss_i, "loss_i", (B,)), _dev(pred, "pred", (B,), torch.int64),
+              _labels(labels, B), B, _dev(acc, "acc", (EVAL_ACC_WORDS,), torch.int64), _stream(loss_i))
+    return acc
+
+
 def xent_fwd_bwd(logits, labels, grad_scale, loss_i=None, dlogits=None, err_flag=None):
     B = batch_of(logits, (10,), "logits")
     loss_i = _out(loss_i, (B,), logits, name="loss_i")

@@ -32,7 +32,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import TIMER, LossLog, _Buffers, register_graph_inputs, select_graph
+from . import ops
+from .engine import TIMER, LossLog, _Buffers, eval_batch_on, evaluate_on, register_graph_inputs, select_graph
 from .ops import _dev, _stream
 
 P_DROP = 0.25
@@ -472,6 +473,8 @@ class WideServerStage:
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
         self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
+        self.eval_logits = None   # the logits of the last evaluate() (a stage buffer)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self._buf = _Buffers()
         self.refresh_shadows()
@@ -481,6 +484,29 @@ class WideServerStage:
 
     def refresh_shadows(self):
         _k("wide_fc_shadow", self.params.data_ptr(), self.wf8.data_ptr(), _stream(self.params))
+
+    def evaluate(self, cut, labels=None, metrics=None):
+        """Forward only, as WideModelPartB.eval() runs it: slk_wide_head_fwd with every feature kept
+        (keep_threshold 0, keep_scale 1), then loss_i / pred from the logits (slk_eval_logits) and, with
+        `metrics` (metrics.EvalMetrics), the device accumulator. Returns (pred, loss_i); labels=None predicts
+        only (loss_i is None). Own `eval_` buffers and eval_err_flag; step_ctr is read (the dropout hash input,
+        unused at threshold 0) and never ticked; parameters, Adam state and the loss log are not touched."""
+        B = cut.shape[0]
+        _dev(cut, "cut", (B,) + CUT_SHAPE, _BF)
+        logits = self._b("eval_logits", (B, 10), _F32)
+        _k("wide_head_fwd", cut.data_ptr(), self.wf8.data_ptr(), self.params[163840:].data_ptr(),
+           self.step_ctr.data_ptr(), self.seed, 0, 1.0, logits.data_ptr(), 0, B, _stream(cut))
+        with TIMER("eval_logits"):
+            loss_i, pred = ops.eval_logits(logits, labels,
+                                           loss_i=self._b("eval_loss_i", (B,), _F32) if labels is not None else None,
+                                           pred=self._b("eval_pred", (B,), torch.int64), err_flag=self.eval_err_flag)
+        self.eval_logits = logits
+        if metrics is not None:
+            if labels is None:
+                raise ValueError("metrics need labels")
+            with TIMER("eval_accumulate"):
+                metrics.update(loss_i, pred, labels)
+        return pred, loss_i
 
     def forward_backward(self, cut, labels, grad_scale, dcut=None, b0: int = 0):
         B = cut.shape[0]
@@ -574,6 +600,9 @@ class WideTrainer:
         self.graph_inputs = 4   # caller input buffers captured directly (as engine.SplitTrainer)
         self._seen = {}
         self.global_step = 0
+        self._eval_graphs = {}    # batch size -> the evaluation pass's graph (never in _graphs)
+        self._eval_metrics = None  # evaluate()'s own accumulator, made on first use
+        self.eval_cut = None
 
     @property
     def loss_log(self) -> LossLog:
@@ -646,3 +675,26 @@ class WideTrainer:
             self._eager(x, y)
         self.server.loss_log.note_step(self.global_step)
         self.global_step += 1
+
+    # ---- evaluation / prediction (as engine.SplitTrainer's): forward only, no training state touched
+    def _eval_eager(self, x, y, metrics=None):
+        # the client forward under its own tag: the saved tensors of a training forward (tag "") survive
+        self.eval_cut = self.client.forward(x, tag="eval")   # the last evaluation's cut (a stage buffer)
+        return self.server.evaluate(self.eval_cut, y, metrics=metrics)
+
+    def eval_batch(self, x, y, metrics=None):
+        """One held-out batch, asynchronous: (pred, loss_i) (stage buffers; logits in server.eval_logits, the
+        cut in eval_cut); `metrics` updated on the device. No dropout, no tick: both step counters, the
+        parameters, Adam's m / v and the shadows are as before. With graph=True the graph of a batch size
+        holds the accumulator of `metrics`: another metrics object (or none, or alternating with
+        evaluate(), which uses the trainer's own) captures that size again, so keep to one per trainer."""
+        return eval_batch_on(self, x, y, metrics, (3, 32, 32))
+
+    def evaluate(self, batches, metrics=None):
+        """metrics.EvalResult over an iterable of device (x, y) batches, one host sync at the end."""
+        return evaluate_on(self, batches, metrics)
+
+    def predict(self, x, return_logits: bool = False):
+        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""
+        pred, _ = self._eval_eager(x, None)
+        return (pred.clone(), self.server.eval_logits.clone()) if return_logits else pred.clone()
