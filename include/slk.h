@@ -311,6 +311,32 @@ int slk_sgd_multi_from_slabs(float* const* params, float* const* grads, const fl
                              int loss_n, float loss_scale, float* ring, int capacity, int* counter,
                              void* stream);
 
+/* torch.optim.SGD(lr, momentum, dampening, nesterov, weight_decay) fused with the slab reduction, the rate
+ * read on the device: lr = lr_table[clamp(*step, 0, lr_len - 1)], where *step is the number of optimizer
+ * steps this stage has completed (advance it with slk_tick after the launch). A constant rate is a table of
+ * length 1, a torch.optim.lr_scheduler schedule a table of its per-step values (the last one holds past the
+ * end); no host value is baked into a captured HIP graph. Per element, g = sum_s slabs[s*n+i] (the three
+ * summation forms of slk_reduce_slabs); grad[i] = g (if grad != NULL, before weight decay); then
+ *   g += weight_decay * p                                         (weight_decay != 0)
+ *   buf = (*step == 0) ? g : momentum * buf + (1 - dampening) * g  (momentum != 0; buf may be NULL otherwise)
+ *   g = nesterov ? g + momentum * buf : buf
+ *   p -= lr * g.
+ * With momentum 0, weight_decay 0 and a one-entry table the result is bitwise slk_sgd_from_slabs'.
+ * Replaces optimizer.step() (client_part.py:133, server_part.py:52) for any torch.optim.SGD recipe and
+ * scheduler.step() of torch.optim.lr_scheduler.*. */
+int slk_sgdm_from_slabs(float* param, float* grad, float* buf, const float* slabs, int nslab, int n,
+                        const float* lr_table, int lr_len, const int* step, float momentum, float dampening,
+                        float weight_decay, int nesterov, void* stream);
+
+/* slk_sgdm_from_slabs over nseg (<= 4) segments, one buf per segment, plus slk_loss_log when
+ * loss_values != NULL, in ONE launch — bit-identical to the separate launches (the momentum form of
+ * slk_sgd_multi_from_slabs; every segment needs a param). The pointer/size arrays are host memory. */
+int slk_sgdm_multi_from_slabs(float* const* params, float* const* grads, float* const* bufs,
+                              const float* const* slabs, const int* nslab, const int* n, int nseg,
+                              const float* lr_table, int lr_len, const int* step, float momentum, float dampening,
+                              float weight_decay, int nesterov, const float* loss_values, int loss_n,
+                              float loss_scale, float* ring, int capacity, int* counter, void* stream);
+
 /* MNIST batch from the HBM-resident u8 dataset (replaces DataLoader(batch_size=64, shuffle=True)
  * over torchvision MNIST + ToTensor + Normalize((0.1307,),(0.3081,)), src/client_part.py:61-64,98):
  * x[s] = ((float)images[idx[s]] / 255 - mean) / std as f32 [B,1,28,28], y[s] = labels[idx[s]] (i64).
@@ -448,6 +474,20 @@ int slk_adam_from_slabs(float* param, float* grad, float* m, float* v, const flo
 int slk_adam_multi_from_slabs(float* const* params, float* const* grads, float* const* m, float* const* v,
                               const float* const* slabs, const int* nslab, const int* n, int nseg, float lr,
                               float beta1, float beta2, float eps, const int* step, void* stream);
+
+/* slk_adam_from_slabs with the rate read on the device (lr = lr_table[clamp(*step, 0, lr_len - 1)], as
+ * slk_sgdm_from_slabs) and weight decay: decoupled = 1 is torch.optim.AdamW (p *= 1 - lr * weight_decay
+ * before the update), decoupled = 0 is torch.optim.Adam(weight_decay=...) (g += weight_decay * p before the
+ * moments). grad (if non-null) receives the reduced gradient before weight decay. With weight_decay 0 and a
+ * one-entry table the result is bitwise slk_adam_from_slabs'. */
+int slk_adamw_from_slabs(float* param, float* grad, float* m, float* v, const float* slabs, int nslab, int n,
+                         const float* lr_table, int lr_len, const int* step, float beta1, float beta2, float eps,
+                         float weight_decay, int decoupled, void* stream);
+/* slk_adamw_from_slabs over nseg (<= 4) segments in ONE launch (bit-identical to the separate launches). */
+int slk_adamw_multi_from_slabs(float* const* params, float* const* grads, float* const* m, float* const* v,
+                               const float* const* slabs, const int* nslab, const int* n, int nseg,
+                               const float* lr_table, int lr_len, const int* step, float beta1, float beta2,
+                               float eps, float weight_decay, int decoupled, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

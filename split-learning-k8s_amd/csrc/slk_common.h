@@ -45,6 +45,12 @@ static inline int slk_launch_status() { return (int)hipGetLastError(); }
 
 static inline hipStream_t slk_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Learning rate of optimizer step `step` from a device table (slk_sgdm_* / slk_adamw_*): the schedule is
+// device memory, so a captured HIP graph reads this replay's rate; past the end the last value holds.
+__device__ __forceinline__ float slk_lr_at(const float* __restrict__ lr_table, int lr_len, int step) {
+    return lr_table[min(max(step, 0), lr_len - 1)];
+}
+
 // f32-input MFMA wrappers (exact f32, k-ordered fma chain; cdna_hip_programming.md §3).
 // 32x32x2: lane l supplies A[i=l&31][k=l>>5] and B[k=l>>5][j=l&31];
 //          D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5), r in [0,16).

@@ -24,9 +24,53 @@ __host__ __device__ constexpr int rs_cols_per_block(int nslab) {
 }
 static inline int rs_blocks(int n, int nslab) { return (n + rs_cols_per_block(nslab) - 1) / rs_cols_per_block(nslab); }
 
-__device__ __forceinline__ void slab_reduce_sgd_cols(float* __restrict__ param, float* __restrict__ grad,
-                                                     const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                     int acc, int blk) {
+// The per-element step of a reduced gradient t. SgdApply: p -= lr * t (optim.SGD(lr), the reference's
+// recipe; param == NULL only reduces). SgdmApply: torch.optim.SGD with momentum / dampening / Nesterov /
+// weight decay, the rate read from a device table at the stage's device step counter.
+struct SgdApply {
+    float* __restrict__ param;
+    float* __restrict__ grad;
+    float lr;
+    __device__ __forceinline__ void operator()(int i, float t) const {
+        if (grad) grad[i] = t;
+        if (param) param[i] = param[i] - lr * t;
+    }
+};
+
+struct SgdmHyper {
+    const float* lr_table;
+    int lr_len;
+    const int* step;
+    float momentum, dampening, weight_decay;
+    int nesterov;
+};
+struct SgdmApply {
+    float* __restrict__ param;
+    float* __restrict__ grad;
+    float* __restrict__ buf;
+    SgdmHyper h;
+    // torch/optim/sgd.py _single_tensor_sgd: grad.add(param, alpha=wd); buf = grad (first step) or
+    // buf.mul_(momentum).add_(grad, alpha=1 - dampening); grad.add(buf, alpha=momentum) (Nesterov) or buf;
+    // param.add_(grad, alpha=-lr). grad[i] receives the reduced gradient before weight decay.
+    __device__ __forceinline__ void operator()(int i, float g) const {
+        if (grad) grad[i] = g;
+        const int st = *h.step;
+        const float lr = slk_lr_at(h.lr_table, h.lr_len, st);
+        const float p = param[i];
+        if (h.weight_decay != 0.f) g = g + h.weight_decay * p;
+        if (h.momentum != 0.f) {
+            const float b = st == 0 ? g : h.momentum * buf[i] + (1.f - h.dampening) * g;
+            buf[i] = b;
+            g = h.nesterov ? g + h.momentum * b : b;
+        }
+        param[i] = p - lr * g;
+    }
+};
+
+// The three reduction forms; `prior` (if non-null) is added to the sum (slk_reduce_slabs accumulate).
+template <class Apply>
+__device__ __forceinline__ void slab_reduce_cols(const float* __restrict__ prior, const float* __restrict__ slabs,
+                                                 int nslab, int n, int blk, const Apply& apply) {
     const int i = blk * 1024 + threadIdx.x;
     if (i >= n) return;
     const float* s = slabs + i;
@@ -40,14 +84,12 @@ __device__ __forceinline__ void slab_reduce_sgd_cols(float* __restrict__ param, 
         for (int u = 0; u < 8; ++u) g += v[u];
     }
     for (; k < nslab; ++k) g += s[(size_t)k * n];
-    const float t = acc ? grad[i] + g : g;
-    if (grad) grad[i] = t;
-    if (param) param[i] = param[i] - lr * t;
+    apply(i, prior ? prior[i] + g : g);
 }
 
-__device__ __forceinline__ void slab_reduce_sgd_rows(float* __restrict__ param, float* __restrict__ grad,
-                                                     const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                     int acc, int blk) {
+template <class Apply>
+__device__ __forceinline__ void slab_reduce_rows(const float* __restrict__ prior, const float* __restrict__ slabs,
+                                                 int nslab, int n, int blk, const Apply& apply) {
     __shared__ float part[RS_WAVES][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blk * 64 + lane;
@@ -67,17 +109,16 @@ __device__ __forceinline__ void slab_reduce_sgd_rows(float* __restrict__ param, 
     part[wave][lane] = g;
     __syncthreads();
     if (wave == 0 && i < n) {
-        float t = acc ? grad[i] : 0.f;
+        float t = prior ? prior[i] : 0.f;
 #pragma unroll
         for (int w = 0; w < RS_WAVES; ++w) t += part[w][lane];
-        if (grad) grad[i] = t;
-        if (param) param[i] = param[i] - lr * t;
+        apply(i, t);
     }
 }
 
-__device__ __forceinline__ void slab_reduce_sgd_mid(float* __restrict__ param, float* __restrict__ grad,
-                                                    const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                    int acc, int blk) {
+template <class Apply>
+__device__ __forceinline__ void slab_reduce_mid(const float* __restrict__ prior, const float* __restrict__ slabs,
+                                                int nslab, int n, int blk, const Apply& apply) {
     __shared__ float part[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = (wave & 3) * 64 + lane, sg = wave >> 2;  // column within the block, slab group
@@ -98,30 +139,36 @@ __device__ __forceinline__ void slab_reduce_sgd_mid(float* __restrict__ param, f
     part[sg][c] = g;
     __syncthreads();
     if (sg == 0 && i < n) {
-        float t = acc ? grad[i] : 0.f;
+        float t = prior ? prior[i] : 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) t += part[q][c];
-        if (grad) grad[i] = t;
-        if (param) param[i] = param[i] - lr * t;
+        apply(i, t);
     }
 }
 
-__device__ __forceinline__ void slab_reduce_sgd(float* __restrict__ param, float* __restrict__ grad,
-                                                const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                int acc, int blk) {
+template <class Apply>
+__device__ __forceinline__ void slab_reduce(const float* __restrict__ prior, const float* __restrict__ slabs,
+                                            int nslab, int n, int blk, const Apply& apply) {
     if (rs_cols_per_block(nslab) == 1024)
-        slab_reduce_sgd_cols(param, grad, slabs, nslab, n, lr, acc, blk);
+        slab_reduce_cols(prior, slabs, nslab, n, blk, apply);
     else if (rs_cols_per_block(nslab) == 256)
-        slab_reduce_sgd_mid(param, grad, slabs, nslab, n, lr, acc, blk);
+        slab_reduce_mid(prior, slabs, nslab, n, blk, apply);
     else
-        slab_reduce_sgd_rows(param, grad, slabs, nslab, n, lr, acc, blk);
+        slab_reduce_rows(prior, slabs, nslab, n, blk, apply);
 }
 
 __global__ __launch_bounds__(1024) void sgd_from_slabs_kernel(float* __restrict__ param,
                                                               float* __restrict__ grad,
                                                               const float* __restrict__ slabs,
                                                               int nslab, int n, float lr, int acc) {
-    slab_reduce_sgd(param, grad, slabs, nslab, n, lr, acc, blockIdx.x);
+    slab_reduce(acc ? grad : nullptr, slabs, nslab, n, blockIdx.x, SgdApply{param, grad, lr});
+}
+
+__global__ __launch_bounds__(1024) void sgdm_from_slabs_kernel(float* __restrict__ param, float* __restrict__ grad,
+                                                               float* __restrict__ buf,
+                                                               const float* __restrict__ slabs, int nslab, int n,
+                                                               const SgdmHyper h) {
+    slab_reduce(nullptr, slabs, nslab, n, blockIdx.x, SgdmApply{param, grad, buf, h});
 }
 
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ param,
@@ -158,46 +205,61 @@ __global__ __launch_bounds__(256) void loss_log_kernel(const float* __restrict__
 }
 
 // Every optimizer step of one split step in ONE launch (the last launches of the step are latency,
-// not bandwidth): block 0 (if loss_v) logs the loss, the next nblk0 blocks reduce + step segment 0,
+// not bandwidth): block 0 (if loss.v) logs the loss, the next nblk0 blocks reduce + step segment 0,
 // the next nblk1 segment 1, .... Each block runs exactly the code of sgd_from_slabs_kernel /
-// loss_log_kernel on its slice, so the results are bit-identical to the separate launches.
+// sgdm_from_slabs_kernel / loss_log_kernel on its slice, so the results are bit-identical to the
+// separate launches.
 struct SgdSeg {
     float* param;
     float* grad;
+    float* buf;  // momentum buffer (sgdm only)
     const float* slabs;
     int nslab, n, nblk;
 };
 constexpr int SGD_MAXSEG = 4;
-struct SgdMulti {
-    SgdSeg seg[SGD_MAXSEG];
-    int nseg;
-    float lr;
-    const float* loss_v;
-    int loss_n;
-    float loss_scale;
+struct LossLogArgs {
+    const float* v;
+    int n;
+    float scale;
     float* ring;
     int capacity;
     int* counter;
 };
+struct SgdHyper {
+    float lr;
+    __device__ __forceinline__ SgdApply apply(const SgdSeg& g) const { return SgdApply{g.param, g.grad, lr}; }
+};
+struct SgdmMultiHyper {
+    SgdmHyper h;
+    __device__ __forceinline__ SgdmApply apply(const SgdSeg& g) const { return SgdmApply{g.param, g.grad, g.buf, h}; }
+};
+template <class Hyper>
+struct SgdMulti {
+    SgdSeg seg[SGD_MAXSEG];
+    int nseg;
+    Hyper hyper;
+    LossLogArgs loss;
+};
 
-__global__ __launch_bounds__(1024) void sgd_multi_kernel(const SgdMulti a) {
+template <class Hyper>
+__global__ __launch_bounds__(1024) void sgd_multi_kernel(const SgdMulti<Hyper> a) {
     int blk = blockIdx.x;
-    if (a.loss_v) {
+    if (a.loss.v) {
         // block 0 logs the loss (dispatched first: its serial sum overlaps the segments' blocks);
         // threads 0..255 sum exactly as block_sum_256 (the other waves add nothing)
         if (blk == 0) {
             __shared__ float red[4];
             float v = 0.f;
             if (threadIdx.x < 256)
-                for (int i = threadIdx.x; i < a.loss_n; i += 256) v += a.loss_v[i];
+                for (int i = threadIdx.x; i < a.loss.n; i += 256) v += a.loss.v[i];
             v = wave_sum(v);
             if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
             __syncthreads();
             if (threadIdx.x == 0) {
                 const float tot = ((red[0] + red[1]) + red[2]) + red[3];
-                const int c = *a.counter;
-                a.ring[c % a.capacity] = tot * a.loss_scale;
-                *a.counter = c + 1;
+                const int c = *a.loss.counter;
+                a.loss.ring[c % a.loss.capacity] = tot * a.loss.scale;
+                *a.loss.counter = c + 1;
             }
             return;
         }
@@ -207,7 +269,8 @@ __global__ __launch_bounds__(1024) void sgd_multi_kernel(const SgdMulti a) {
     for (int s = 0; s < SGD_MAXSEG; ++s) {
         if (s < a.nseg) {
             if (blk < a.seg[s].nblk) {
-                slab_reduce_sgd(a.seg[s].param, a.seg[s].grad, a.seg[s].slabs, a.seg[s].nslab, a.seg[s].n, a.lr, 0, blk);
+                slab_reduce(nullptr, a.seg[s].slabs, a.seg[s].nslab, a.seg[s].n, blk,
+                                                               a.hyper.apply(a.seg[s]));
                 return;
             }
             blk -= a.seg[s].nblk;
@@ -245,25 +308,58 @@ extern "C" int slk_sgd_multi_from_slabs(float* const* params, float* const* grad
                                         int capacity, int* counter, void* stream) {
     SLK_CHECK_ARG(nseg >= 0 && nseg <= SGD_MAXSEG && (nseg == 0 || (params && slabs && nslab && n)));
     SLK_CHECK_ARG(!loss_values || (loss_n > 0 && capacity > 0 && ring && counter));
-    SgdMulti a{};
+    SgdMulti<SgdHyper> a{};
     int nblk = 0;
     for (int s = 0; s < nseg; ++s) {
         // a segment with no param is a reduce only (grad = sum of slabs): the all-reduce bucket fill
         SLK_CHECK_ARG(n[s] >= 0 && nslab[s] >= 0 && (params[s] || (grads && grads[s])) && (slabs[s] || nslab[s] == 0));
-        a.seg[s] = SgdSeg{params[s], grads ? grads[s] : nullptr, slabs[s], nslab[s], n[s], rs_blocks(n[s], nslab[s])};
+        a.seg[s] = SgdSeg{params[s], grads ? grads[s] : nullptr, nullptr, slabs[s], nslab[s], n[s],
+                          rs_blocks(n[s], nslab[s])};
         nblk += a.seg[s].nblk;
     }
     a.nseg = nseg;
-    a.lr = lr;
-    a.loss_v = loss_values;
-    a.loss_n = loss_n;
-    a.loss_scale = loss_scale;
-    a.ring = ring;
-    a.capacity = capacity;
-    a.counter = counter;
+    a.hyper.lr = lr;
+    a.loss = LossLogArgs{loss_values, loss_n, loss_scale, ring, capacity, counter};
     if (loss_values) ++nblk;
     if (nblk == 0) return 0;
-    sgd_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    sgd_multi_kernel<SgdHyper><<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+extern "C" int slk_sgdm_from_slabs(float* param, float* grad, float* buf, const float* slabs, int nslab, int n,
+                                   const float* lr_table, int lr_len, const int* step, float momentum,
+                                   float dampening, float weight_decay, int nesterov, void* stream) {
+    SLK_CHECK_ARG(nslab > 0 && n >= 0 && lr_len >= 1);
+    SLK_CHECK_ARG(param && slabs && lr_table && step && (buf || momentum == 0.f));
+    if (n == 0) return 0;
+    const SgdmHyper h{lr_table, lr_len, step, momentum, dampening, weight_decay, nesterov ? 1 : 0};
+    sgdm_from_slabs_kernel<<<rs_blocks(n, nslab), 1024, 0, slk_stream(stream)>>>(param, grad, buf, slabs, nslab, n, h);
+    return slk_launch_status();
+}
+
+extern "C" int slk_sgdm_multi_from_slabs(float* const* params, float* const* grads, float* const* bufs,
+                                         const float* const* slabs, const int* nslab, const int* n, int nseg,
+                                         const float* lr_table, int lr_len, const int* step, float momentum,
+                                         float dampening, float weight_decay, int nesterov,
+                                         const float* loss_values, int loss_n, float loss_scale, float* ring,
+                                         int capacity, int* counter, void* stream) {
+    SLK_CHECK_ARG(nseg >= 0 && nseg <= SGD_MAXSEG && lr_len >= 1 && lr_table && step);
+    SLK_CHECK_ARG(nseg == 0 || (params && slabs && nslab && n && (bufs || momentum == 0.f)));
+    SLK_CHECK_ARG(!loss_values || (loss_n > 0 && capacity > 0 && ring && counter));
+    SgdMulti<SgdmMultiHyper> a{};
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        SLK_CHECK_ARG(n[s] >= 0 && nslab[s] > 0 && params[s] && slabs[s] && (momentum == 0.f || bufs[s]));
+        a.seg[s] = SgdSeg{params[s], grads ? grads[s] : nullptr, bufs ? bufs[s] : nullptr, slabs[s], nslab[s], n[s],
+                          rs_blocks(n[s], nslab[s])};
+        nblk += a.seg[s].nblk;
+    }
+    a.nseg = nseg;
+    a.hyper.h = SgdmHyper{lr_table, lr_len, step, momentum, dampening, weight_decay, nesterov ? 1 : 0};
+    a.loss = LossLogArgs{loss_values, loss_n, loss_scale, ring, capacity, counter};
+    if (loss_values) ++nblk;
+    if (nblk == 0) return 0;
+    sgd_multi_kernel<SgdmMultiHyper><<<nblk, 1024, 0, slk_stream(stream)>>>(a);
     return slk_launch_status();
 }
 

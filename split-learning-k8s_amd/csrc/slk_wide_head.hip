@@ -324,12 +324,35 @@ __host__ __device__ constexpr int adam_cols_per_block(int nslab) {
     return nslab <= AD_COLS_MAX ? 1024 : (nslab <= AD_MID_MAX ? 256 : 64);
 }
 
+// Hyper-parameters of one Adam launch. TABLE = false is torch.optim.Adam(lr) as above (lr by value);
+// TABLE = true (slk_adamw_*) reads the rate from a device table at *step (slk_lr_at) and applies weight
+// decay: decoupled (torch.optim.AdamW: p *= 1 - lr * wd before the update, the factor in double like torch's
+// Python float) or coupled (torch.optim.Adam(weight_decay): g += wd * p before the moments).
+struct AdamHyper {
+    float lr;
+    const float* lr_table;
+    int lr_len;
+    float wd;
+    int decoupled;
+    float b1, b2, eps;
+    const int* step;
+};
+
 // the Adam update of element i from its summed gradient t (shared by the reduction forms below)
+template <bool TABLE>
 __device__ __forceinline__ void adam_apply(int i, float t, float* __restrict__ param, float* __restrict__ grad,
-                                           float* __restrict__ m_, float* __restrict__ v_, float lr, float b1,
-                                           float b2, float eps, const int* __restrict__ step_ptr) {
+                                           float* __restrict__ m_, float* __restrict__ v_, const AdamHyper& h) {
     if (grad) grad[i] = t;
-    const double tt = (double)(*step_ptr + 1);
+    const float b1 = h.b1, b2 = h.b2, eps = h.eps;
+    const float lr = TABLE ? slk_lr_at(h.lr_table, h.lr_len, *h.step) : h.lr;
+    float p = param[i];
+    if (TABLE && h.wd != 0.f) {
+        if (h.decoupled)
+            p = p * (float)(1.0 - (double)lr * (double)h.wd);
+        else
+            t = t + h.wd * p;
+    }
+    const double tt = (double)(*h.step + 1);
     const double bc1 = 1.0 - pow((double)b1, tt);
     const float step_size = (float)((double)lr / bc1);
     const float bc2s = (float)sqrt(1.0 - pow((double)b2, tt));
@@ -337,16 +360,16 @@ __device__ __forceinline__ void adam_apply(int i, float t, float* __restrict__ p
     m = m + (1.f - b1) * (t - m);
     v = v * b2 + t * t * (1.f - b2);
     const float denom = sqrtf(v) / bc2s + eps;
-    param[i] = param[i] + (-step_size) * (m / denom);
+    param[i] = p + (-step_size) * (m / denom);
     m_[i] = m;
     v_[i] = v;
 }
 
+template <bool TABLE>
 __device__ __forceinline__ void adam_slab_block_mid(float* __restrict__ param, float* __restrict__ grad,
                                                     float* __restrict__ m_, float* __restrict__ v_,
-                                                    const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                    float b1, float b2, float eps, const int* __restrict__ step_ptr,
-                                                    int blk) {
+                                                    const float* __restrict__ slabs, int nslab, int n,
+                                                    const AdamHyper& h, int blk) {
     __shared__ float part[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = (wave & 3) * 64 + lane, sg = wave >> 2;  // column within the block, slab group
@@ -370,15 +393,15 @@ __device__ __forceinline__ void adam_slab_block_mid(float* __restrict__ param, f
         float t = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) t += part[q][c];
-        adam_apply(i, t, param, grad, m_, v_, lr, b1, b2, eps, step_ptr);
+        adam_apply<TABLE>(i, t, param, grad, m_, v_, h);
     }
 }
 
+template <bool TABLE>
 __device__ __forceinline__ void adam_slab_block_rows(float* __restrict__ param, float* __restrict__ grad,
-                                                float* __restrict__ m_, float* __restrict__ v_,
-                                                const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                float b1, float b2, float eps, const int* __restrict__ step_ptr,
-                                                int blk) {
+                                                     float* __restrict__ m_, float* __restrict__ v_,
+                                                     const float* __restrict__ slabs, int nslab, int n,
+                                                     const AdamHyper& h, int blk) {
     __shared__ float part[AD_WAVES][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blk * 64 + lane;
@@ -401,26 +424,15 @@ __device__ __forceinline__ void adam_slab_block_rows(float* __restrict__ param, 
         float t = 0.f;
 #pragma unroll
         for (int w = 0; w < AD_WAVES; ++w) t += part[w][lane];
-        if (grad) grad[i] = t;
-        const double tt = (double)(*step_ptr + 1);
-        const double bc1 = 1.0 - pow((double)b1, tt);
-        const float step_size = (float)((double)lr / bc1);
-        const float bc2s = (float)sqrt(1.0 - pow((double)b2, tt));
-        float m = m_[i], v = v_[i];
-        m = m + (1.f - b1) * (t - m);
-        v = v * b2 + t * t * (1.f - b2);
-        const float denom = sqrtf(v) / bc2s + eps;
-        param[i] = param[i] + (-step_size) * (m / denom);
-        m_[i] = m;
-        v_[i] = v;
+        adam_apply<TABLE>(i, t, param, grad, m_, v_, h);
     }
 }
 
+template <bool TABLE>
 __device__ __forceinline__ void adam_slab_block_cols(float* __restrict__ param, float* __restrict__ grad,
                                                      float* __restrict__ m_, float* __restrict__ v_,
-                                                     const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                     float b1, float b2, float eps, const int* __restrict__ step_ptr,
-                                                     int blk) {
+                                                     const float* __restrict__ slabs, int nslab, int n,
+                                                     const AdamHyper& h, int blk) {
     const int i = blk * 1024 + threadIdx.x;
     if (i >= n) return;
     const float* s = slabs + i;
@@ -434,39 +446,28 @@ __device__ __forceinline__ void adam_slab_block_cols(float* __restrict__ param, 
         for (int u = 0; u < 8; ++u) t += v[u];
     }
     for (; k < nslab; ++k) t += s[(size_t)k * n];
-    if (grad) grad[i] = t;
-    const double tt = (double)(*step_ptr + 1);
-    const double bc1 = 1.0 - pow((double)b1, tt);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(1.0 - pow((double)b2, tt));
-    float m = m_[i], v = v_[i];
-    m = m + (1.f - b1) * (t - m);
-    v = v * b2 + t * t * (1.f - b2);
-    const float denom = sqrtf(v) / bc2s + eps;
-    param[i] = param[i] + (-step_size) * (m / denom);
-    m_[i] = m;
-    v_[i] = v;
+    adam_apply<TABLE>(i, t, param, grad, m_, v_, h);
 }
 
+template <bool TABLE>
 __device__ __forceinline__ void adam_slab_block(float* __restrict__ param, float* __restrict__ grad,
                                                 float* __restrict__ m_, float* __restrict__ v_,
-                                                const float* __restrict__ slabs, int nslab, int n, float lr,
-                                                float b1, float b2, float eps, const int* __restrict__ step_ptr,
-                                                int blk) {
+                                                const float* __restrict__ slabs, int nslab, int n,
+                                                const AdamHyper& h, int blk) {
     if (adam_cols_per_block(nslab) == 1024)
-        adam_slab_block_cols(param, grad, m_, v_, slabs, nslab, n, lr, b1, b2, eps, step_ptr, blk);
+        adam_slab_block_cols<TABLE>(param, grad, m_, v_, slabs, nslab, n, h, blk);
     else if (adam_cols_per_block(nslab) == 256)
-        adam_slab_block_mid(param, grad, m_, v_, slabs, nslab, n, lr, b1, b2, eps, step_ptr, blk);
+        adam_slab_block_mid<TABLE>(param, grad, m_, v_, slabs, nslab, n, h, blk);
     else
-        adam_slab_block_rows(param, grad, m_, v_, slabs, nslab, n, lr, b1, b2, eps, step_ptr, blk);
+        adam_slab_block_rows<TABLE>(param, grad, m_, v_, slabs, nslab, n, h, blk);
 }
 
+template <bool TABLE>
 __global__ __launch_bounds__(1024) void adam_from_slabs_kernel(float* __restrict__ param, float* __restrict__ grad,
                                                                float* __restrict__ m_, float* __restrict__ v_,
                                                                const float* __restrict__ slabs, int nslab, int n,
-                                                               float lr, float b1, float b2, float eps,
-                                                               const int* __restrict__ step_ptr) {
-    adam_slab_block(param, grad, m_, v_, slabs, nslab, n, lr, b1, b2, eps, step_ptr, blockIdx.x);
+                                                               const AdamHyper h) {
+    adam_slab_block<TABLE>(param, grad, m_, v_, slabs, nslab, n, h, blockIdx.x);
 }
 
 // Several parameter segments (each with its own slab set) in ONE launch: consecutive block ranges,
@@ -483,9 +484,9 @@ struct AdamSeg {
 struct AdamMulti {
     AdamSeg seg[AD_MAXSEG];
     int nseg;
-    float lr, b1, b2, eps;
-    const int* step;
+    AdamHyper h;
 };
+template <bool TABLE>
 __global__ __launch_bounds__(1024) void adam_multi_kernel(const AdamMulti a) {
     int blk = blockIdx.x;
 #pragma unroll
@@ -493,7 +494,7 @@ __global__ __launch_bounds__(1024) void adam_multi_kernel(const AdamMulti a) {
         if (s < a.nseg) {
             const AdamSeg& g = a.seg[s];
             if (blk < g.nblk) {
-                adam_slab_block(g.param, g.grad, g.m, g.v, g.slabs, g.nslab, g.n, a.lr, a.b1, a.b2, a.eps, a.step, blk);
+                adam_slab_block<TABLE>(g.param, g.grad, g.m, g.v, g.slabs, g.nslab, g.n, a.h, blk);
                 return;
             }
             blk -= g.nblk;
@@ -583,37 +584,72 @@ extern "C" int slk_wide_head_bwd(const uint16_t* cut, const float* wf8, const fl
     return slk_launch_status();
 }
 
-extern "C" int slk_adam_from_slabs(float* param, float* grad, float* m, float* v, const float* slabs, int nslab,
-                                   int n, float lr, float beta1, float beta2, float eps, const int* step,
-                                   void* stream) {
-    SLK_CHECK_ARG(param && m && v && slabs && step && nslab > 0 && n >= 0);
+static inline int adam_blocks(int n, int nslab) {
+    return (n + adam_cols_per_block(nslab) - 1) / adam_cols_per_block(nslab);
+}
+
+template <bool TABLE>
+static int adam_launch(float* param, float* grad, float* m, float* v, const float* slabs, int nslab, int n,
+                       const AdamHyper& h, void* stream) {
+    SLK_CHECK_ARG(param && m && v && slabs && h.step && nslab > 0 && n >= 0);
     if (n == 0) return 0;
-    hipLaunchKernelGGL(adam_from_slabs_kernel, dim3((n + adam_cols_per_block(nslab) - 1) / adam_cols_per_block(nslab)), dim3(1024), 0, slk_stream(stream), param, grad, m, v,
-                       slabs, nslab, n, lr, beta1, beta2, eps, step);
+    hipLaunchKernelGGL(adam_from_slabs_kernel<TABLE>, dim3(adam_blocks(n, nslab)), dim3(1024), 0, slk_stream(stream),
+                       param, grad, m, v, slabs, nslab, n, h);
     return slk_launch_status();
 }
-extern "C" int slk_adam_multi_from_slabs(float* const* params, float* const* grads, float* const* m, float* const* v,
-                                         const float* const* slabs, const int* nslab, const int* n, int nseg,
-                                         float lr, float beta1, float beta2, float eps, const int* step,
-                                         void* stream) {
-    SLK_CHECK_ARG(nseg >= 0 && nseg <= AD_MAXSEG && step);
+
+template <bool TABLE>
+static int adam_multi_launch(float* const* params, float* const* grads, float* const* m, float* const* v,
+                             const float* const* slabs, const int* nslab, const int* n, int nseg, const AdamHyper& h,
+                             void* stream) {
+    SLK_CHECK_ARG(nseg >= 0 && nseg <= AD_MAXSEG && h.step);
     SLK_CHECK_ARG(nseg == 0 || (params && m && v && slabs && nslab && n));
     AdamMulti a{};
     int nblk = 0;
     for (int s = 0; s < nseg; ++s) {
         SLK_CHECK_ARG(params[s] && m[s] && v[s] && slabs[s] && nslab[s] > 0 && n[s] >= 0);
-        a.seg[s] = AdamSeg{params[s], grads ? grads[s] : nullptr, m[s], v[s], slabs[s], nslab[s], n[s], (n[s] + adam_cols_per_block(nslab[s]) - 1) / adam_cols_per_block(nslab[s])};
+        a.seg[s] = AdamSeg{params[s], grads ? grads[s] : nullptr, m[s], v[s], slabs[s], nslab[s], n[s],
+                           adam_blocks(n[s], nslab[s])};
         nblk += a.seg[s].nblk;
     }
     a.nseg = nseg;
-    a.lr = lr;
-    a.b1 = beta1;
-    a.b2 = beta2;
-    a.eps = eps;
-    a.step = step;
+    a.h = h;
     if (nblk == 0) return 0;
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(nblk), dim3(1024), 0, slk_stream(stream), a);
+    hipLaunchKernelGGL(adam_multi_kernel<TABLE>, dim3(nblk), dim3(1024), 0, slk_stream(stream), a);
     return slk_launch_status();
+}
+
+extern "C" int slk_adam_from_slabs(float* param, float* grad, float* m, float* v, const float* slabs, int nslab,
+                                   int n, float lr, float beta1, float beta2, float eps, const int* step,
+                                   void* stream) {
+    return adam_launch<false>(param, grad, m, v, slabs, nslab, n,
+                              AdamHyper{lr, nullptr, 0, 0.f, 0, beta1, beta2, eps, step}, stream);
+}
+extern "C" int slk_adam_multi_from_slabs(float* const* params, float* const* grads, float* const* m, float* const* v,
+                                         const float* const* slabs, const int* nslab, const int* n, int nseg,
+                                         float lr, float beta1, float beta2, float eps, const int* step,
+                                         void* stream) {
+    return adam_multi_launch<false>(params, grads, m, v, slabs, nslab, n, nseg,
+                                    AdamHyper{lr, nullptr, 0, 0.f, 0, beta1, beta2, eps, step}, stream);
+}
+extern "C" int slk_adamw_from_slabs(float* param, float* grad, float* m, float* v, const float* slabs, int nslab,
+                                    int n, const float* lr_table, int lr_len, const int* step, float beta1,
+                                    float beta2, float eps, float weight_decay, int decoupled, void* stream) {
+    SLK_CHECK_ARG(lr_table && lr_len >= 1);
+    return adam_launch<true>(param, grad, m, v, slabs, nslab, n,
+                             AdamHyper{0.f, lr_table, lr_len, weight_decay, decoupled ? 1 : 0, beta1, beta2, eps, step},
+                             stream);
+}
+extern "C" int slk_adamw_multi_from_slabs(float* const* params, float* const* grads, float* const* m,
+                                          float* const* v, const float* const* slabs, const int* nslab,
+                                          const int* n, int nseg, const float* lr_table, int lr_len, const int* step,
+                                          float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                                          void* stream) {
+    SLK_CHECK_ARG(lr_table && lr_len >= 1);
+    return adam_multi_launch<true>(params, grads, m, v, slabs, nslab, n, nseg,
+                                   AdamHyper{0.f, lr_table, lr_len, weight_decay, decoupled ? 1 : 0, beta1, beta2, eps,
+                                             step},
+                                   stream);
 }
 extern "C" int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f,
                                 uint16_t* w2d, uint16_t* w3f, uint16_t* w3d, void* stream) {

@@ -87,6 +87,10 @@ _SIGS = {
     "slk_loss_sum": [_P, _I, _F, _P, _P],
     "slk_loss_log": [_P, _I, _F, _P, _I, _P, _P],
     "slk_sgd_multi_from_slabs": [_P, _P, _P, _P, _P, _I, _F, _P, _I, _F, _P, _I, _P, _P],
+    # momentum / weight decay / device learning-rate table (splitcnn.optim)
+    "slk_sgdm_from_slabs": [_P, _P, _P, _P, _I, _I, _P, _I, _P, _F, _F, _F, _I, _P],
+    "slk_sgdm_multi_from_slabs": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _I, _P, _I, _F, _P, _I, _P,
+                                  _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)
     "slk_wide_conv1_fwd": [_P, _P, _P, _P, _P, _I, _P],
@@ -109,6 +113,8 @@ _SIGS = {
     "slk_wide_conv1_wgrad_nslab": [_I],
     "slk_adam_from_slabs": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P],
     "slk_adam_multi_from_slabs": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P],
+    "slk_adamw_from_slabs": [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P],
+    "slk_adamw_multi_from_slabs": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P],
     "slk_wide_shadows": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
     "slk_wide_fc_shadow": [_P, _P, _P],
     "slk_tick": [_P, _P],

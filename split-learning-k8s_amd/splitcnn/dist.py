@@ -96,6 +96,16 @@ def _loss_sum(values, scale, out):
         out.copy_((values.double().sum() * scale).to(out.dtype).reshape(1))
 
 
+def _default_optimizer_only(who: str, *stages) -> None:
+    """These classes step with the stages' by-value lr (ops.sgd_multi_from_slabs / slk_adam_from_slabs): refuse
+    a stage built with an optimizer config or a schedule (splitcnn.optim) instead of ignoring it."""
+    for st in stages:
+        if getattr(st, "optim", None) is not None or getattr(st, "schedule", None) is not None:
+            raise ValueError(f"dist.{who}: {type(st).__name__} carries an optimizer config / learning-rate schedule "
+                             "(splitcnn.optim); the multi-GPU classes take only the default optimizer — build "
+                             "the stage without optim= and schedule=")
+
+
 def _pair_amax(client, server):
     """Same-device client/server pair: let the client's conv1 emit the cut's per-sample max when the
     server runs the x3 conv2 kernels (saves re-reading the cut)."""
@@ -131,6 +141,7 @@ class Replicated:
 
     def __init__(self, client, server, group=None, device=None, fused: Optional[bool] = None,
                  graph: bool = False, overlap: Optional[bool] = None):
+        _default_optimizer_only("Replicated", client, server)
         self.client, self.server = client, server
         self.fused = _fused_pair(client, server) if fused is None else fused
         if self.fused and overlap:
@@ -304,6 +315,7 @@ class Hub:
     def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, compress=True,
                  server_rank: Optional[int] = None, client_ranks=None, graph: bool = True, groups=None,
                  ship_amax: bool = True, images: bool = False, fuse_codec: bool = True):
+        _default_optimizer_only(type(self).__name__, stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.fuse_codec = bool(fuse_codec)
         # images (dense exchange only): the client ships its x3 split images (act16, the same 86,528 B a
@@ -734,6 +746,7 @@ class Pipeline(Hub):
     def __init__(self, stage, role: str, peer: int, micro: int = 4, compress=True, graph: bool = True,
                  groups=None, ship_amax: bool = True, images: bool = False, fuse_codec: bool = True):
         assert role in ("client", "server")
+        _default_optimizer_only("Pipeline", stage)
         me = dist.get_rank()
         super().__init__(stage, me, dist.get_world_size(), None, micro, compress,
                          server_rank=peer if role == "client" else me,
@@ -753,6 +766,7 @@ class FedAvg:
     The aggregated client loss is logged for `step` like server_part.py:84 (mlflow.log_metric)."""
 
     def __init__(self, client, server, group=None, device=None):
+        _default_optimizer_only("FedAvg", client, server)
         self.client, self.server = client, server
         _pair_amax(client, server)
         self.group = group
@@ -802,6 +816,7 @@ class UShaped:
 
     def __init__(self, stage, role: str, peer: int, group=None):
         assert role in ("client", "server")
+        _default_optimizer_only("UShaped", stage, getattr(stage, "conv", None))   # UClientStage.conv: a ClientStage
         self.stage, self.role, self.peer, self.group = stage, role, peer, group
         self.global_step = 0
         self._bufs = {}
@@ -855,6 +870,7 @@ class WideHub:
     cut_shape / cut_dtype; server.accumulate(cut, labels, scale, b0, k, nparts, dcut) / finish_step."""
 
     def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None):
+        _default_optimizer_only("WideHub", stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.server_rank = world - 1
         self.nclients = world - 1

@@ -29,6 +29,7 @@ import torch.nn as nn
 
 from . import ops
 from .model_def import ModelPartA, ModelPartB
+from .optim import SGD, LRSchedule
 
 LR = 0.01  # optim.SGD(lr=0.01) on both sides (client_part.py:17, server_part.py:15)
 
@@ -81,6 +82,51 @@ def _flatten_params(params: List[nn.Parameter], device) -> Tuple[torch.Tensor, t
         p.grad = gflat[off:off + k].view(p.shape)
         off += k
     return flat, gflat
+
+
+class _SgdRecipe:
+    """Optimizer state of a K2 stage. Without a config (optim=None, schedule=None) the stage runs the
+    reference's optim.SGD(lr) on slk_sgd_*, `lr` a by-value kernel argument (frozen into a captured graph).
+    With an optim.SGD config and / or an optim.LRSchedule it runs slk_sgdm_*: the momentum buffers `buf` (one
+    flat block like params / grads), the device counter `step_ctr` of completed optimizer steps and the
+    schedule's device table, all read by the kernels, so graph replays follow them. The stage advances
+    step_ctr after its optimizer launches unless a trainer that shares one counter between both stages does
+    (auto_tick False)."""
+
+    def _init_optim(self, lr, optim, schedule):
+        if optim is not None and not isinstance(optim, SGD):
+            raise TypeError(f"optim: expected splitcnn.optim.SGD or None, got {type(optim).__name__}")
+        if optim is None and schedule is not None:
+            optim = SGD(lr)
+        self.optim, self.schedule = optim, None
+        self.buf = self.step_ctr = None
+        self.auto_tick = True
+        if optim is None:
+            return
+        self.lr = optim.lr
+        self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
+        self.buf = torch.zeros_like(self.params)
+        self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _sgdm(self, segments, loss=None, multi=False):
+        """slk_sgdm_* on (lo, hi, slabs) slices of this stage (slabs [nslab, hi - lo]) and ready
+        (param, grad, buf, slabs) tuples: separate launches, or ONE with the loss log (multi)."""
+        segs = [(self.params[g[0]:g[1]], self.grads[g[0]:g[1]], self.buf[g[0]:g[1]], g[2]) if len(g) == 3 else g
+                for g in segments]
+        kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
+        if multi:
+            ops.sgdm_multi_from_slabs(segs, loss=loss, **kw)
+        else:
+            for g in segs:
+                ops.sgdm_from_slabs(*g, **kw)
+
+    def _tick(self):
+        if self.auto_tick:
+            ops.tick(self.step_ctr)
+
+    def optim_segment(self, slabs):
+        """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch."""
+        return (self.params, self.grads, self.buf, slabs)
 
 
 class _Buffers:
@@ -149,7 +195,7 @@ CONV_PRESETS = {"f32": ("wino", "wino", "wino"), "x3": ("x3", "x3", "x3"), "x3w"
 CONV_DEFAULT = "x3"
 
 
-class ClientStage:
+class ClientStage(_SgdRecipe):
     """Client half: ModelPartA on one device + SGD (src/client_part.py:16-17,112-133).
 
     forward(x) -> act; then either backward_step(cut_grad) (fused wgrad-slab reduce + SGD, the
@@ -157,12 +203,14 @@ class ClientStage:
     accumulate=...) into the flat gradient block followed by step() (micro-batched / all-reduced
     topologies)."""
 
-    def __init__(self, model: Optional[ModelPartA] = None, lr: float = LR, device="cuda"):
+    def __init__(self, model: Optional[ModelPartA] = None, lr: float = LR, device="cuda",
+                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else ModelPartA()).to(self.device)
         self.lr = lr
         self.params, self.grads = _flatten_params(
             [self.model.conv1.weight, self.model.conv1.bias], self.device)
+        self._init_optim(lr, optim, schedule)
         self._buf = _Buffers()
         self._x = None
         self._act = None
@@ -249,15 +297,17 @@ class ClientStage:
                       act: Optional[torch.Tensor] = None) -> None:
         """act.backward(cut_grad); optimizer.step() (client_part.py:132-133): relu-bwd + conv1
         wgrad slabs, then ONE fused reduce+SGD launch over the 320 client parameters."""
-        slabs = self._slabs(cut_grad, x, act)
-        with TIMER("sgd_client"):
-            ops.sgd_from_slabs(self.params, self.grads, slabs, self.lr)
+        self.step_from_slabs(self._slabs(cut_grad, x, act))
 
     def step_from_slabs(self, slabs: torch.Tensor) -> None:
         """optimizer.step() from gradient slabs produced elsewhere (the server's fused x3 dgrad,
         ServerStage.forward_backward(client_fuse=...)): one fused reduce + SGD launch."""
         with TIMER("sgd_client"):
-            ops.sgd_from_slabs(self.params, self.grads, slabs, self.lr)
+            if self.optim is None:
+                ops.sgd_from_slabs(self.params, self.grads, slabs, self.lr)
+            else:
+                self._sgdm([(0, ops.CLIENT_NPARAM, slabs)])
+                self._tick()
 
     def backward(self, cut_grad: torch.Tensor, x: Optional[torch.Tensor] = None,
                  act: Optional[torch.Tensor] = None, accumulate: bool = False) -> None:
@@ -268,14 +318,19 @@ class ClientStage:
     def step(self):
         """SGD from the (already reduced / all-reduced) flat gradient block."""
         with TIMER("sgd_client"):
-            ops.sgd(self.params, self.grads, self.lr)
+            if self.optim is None:
+                ops.sgd(self.params, self.grads, self.lr)
+            else:
+                self._sgdm([(self.params, None, self.buf, self.grads.view(1, -1))])
+                self._tick()
 
 
-class ServerStage:
+class ServerStage(_SgdRecipe):
     """Server half: ModelPartB + CrossEntropyLoss + SGD + loss log (src/server_part.py:14-16,25-58)."""
 
     def __init__(self, model: Optional[ModelPartB] = None, lr: float = LR, device="cuda",
-                 loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT):
+                 loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT,
+                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
         self.conv = conv
         self.impl_fwd, self.impl_dgrad, self.impl_wgrad = CONV_PRESETS[conv]
@@ -285,6 +340,7 @@ class ServerStage:
         m = self.model
         self.params, self.grads = _flatten_params(
             [m.conv2.weight, m.conv2.bias, m.fc1.weight, m.fc1.bias], self.device)
+        self._init_optim(lr, optim, schedule)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -414,8 +470,12 @@ class ServerStage:
     def apply_grad_slabs(self, s2, s3):
         """optimizer.step() (server_part.py:52): two fused reduce+SGD launches, one per slab kind."""
         with TIMER("sgd_server"):
-            ops.sgd_from_slabs(self.params[:ops.CONV2_SLAB], self.grads[:ops.CONV2_SLAB], s2, self.lr)
-            ops.sgd_from_slabs(self.params[ops.CONV2_SLAB:], self.grads[ops.CONV2_SLAB:], s3, self.lr)
+            if self.optim is None:
+                ops.sgd_from_slabs(self.params[:ops.CONV2_SLAB], self.grads[:ops.CONV2_SLAB], s2, self.lr)
+                ops.sgd_from_slabs(self.params[ops.CONV2_SLAB:], self.grads[ops.CONV2_SLAB:], s3, self.lr)
+            else:
+                self._sgdm([(0, ops.CONV2_SLAB, s2), (ops.CONV2_SLAB, ops.SERVER_NPARAM, s3)])
+                self._tick()
 
     def reduce_grads(self, s2, s3, accumulate: bool = False):
         """Reduce slabs into the flat gradient block without stepping (micro-batches, all-reduce)."""
@@ -432,7 +492,11 @@ class ServerStage:
 
     def step(self):
         with TIMER("sgd_server"):
-            ops.sgd(self.params, self.grads, self.lr)
+            if self.optim is None:
+                ops.sgd(self.params, self.grads, self.lr)
+            else:
+                self._sgdm([(self.params, None, self.buf, self.grads.view(1, -1))])
+                self._tick()
 
     def log_loss(self, values, scale: Optional[float] = None, step: Optional[int] = None):
         """Log scale*sum(values) (default: the mean of per-sample losses) for `step`."""
@@ -448,7 +512,8 @@ class ServerStage:
         """One /forward_pass request (server_part.py:38-58): returns (cut_grad, loss_i). The mean
         loss for `step` lands in the device loss log. `extra_segments`: further (param, grad, slabs)
         reduce+SGD segments at this stage's lr run in the same optimizer launch (the fused trainer's
-        client update, whose slabs the dgrad wrote)."""
+        client update, whose slabs the dgrad wrote); with an optimizer config they are (param, grad, buf,
+        slabs) (ClientStage.optim_segment) and step by this stage's recipe, schedule and counter."""
         B = labels.shape[0]
         cut_grad, loss_i, s2, s3 = self.forward_backward(act, labels, 1.0 / B, cut_grad=cut_grad,
                                                          act_amax=act_amax, act16=act16, client_fuse=client_fuse)
@@ -457,17 +522,27 @@ class ServerStage:
             # -10 us per step at B = 4096 (tools/ab_step.py). The client's SGD stays a separate launch
             # after its wgrad: moving that wgrad ahead of the server's update measured +25-35 us.
             k = ops.CONV2_SLAB
+            loss = (loss_i, 1.0 / B, self.loss_log.ring, self.loss_log.counter)
             with TIMER("sgd_server"):
-                ops.sgd_multi_from_slabs([(self.params[:k], self.grads[:k], s2), (self.params[k:], self.grads[k:], s3),
-                                          *extra_segments],
-                                         self.lr, loss=(loss_i, 1.0 / B, self.loss_log.ring, self.loss_log.counter))
+                if self.optim is None:
+                    ops.sgd_multi_from_slabs([(self.params[:k], self.grads[:k], s2),
+                                              (self.params[k:], self.grads[k:], s3), *extra_segments],
+                                             self.lr, loss=loss)
+                else:
+                    self._sgdm([(0, k, s2), (k, ops.SERVER_NPARAM, s3), *extra_segments], loss=loss, multi=True)
+                    self._tick()
             if step is not None:
                 self.loss_log.note_step(step)
-        else:
+        elif self.optim is None:
             self.apply_grad_slabs(s2, s3)
             self.log_loss(loss_i, step=step)
             for prm, grd, sl in extra_segments:
                 ops.sgd_from_slabs(prm, grd, sl, self.lr)
+        else:
+            with TIMER("sgd_server"):
+                self._sgdm([(0, ops.CONV2_SLAB, s2), (ops.CONV2_SLAB, ops.SERVER_NPARAM, s3), *extra_segments])
+                self._tick()
+            self.log_loss(loss_i, step=step)
         return cut_grad, loss_i
 
     def check_labels(self):
@@ -640,15 +715,25 @@ class SplitTrainer:
 
     `step(x, y)` = client fwd -> server fwd/loss/bwd/SGD -> client bwd/SGD, exactly one reference
     step. With `graph=True` the step is captured once per batch size into a HIP graph (static input
-    buffers; `step` copies into them unless the caller hands in those very buffers)."""
+    buffers; `step` copies into them unless the caller hands in those very buffers).
+
+    `optim` (optim.SGD) and `schedule` (optim.LRSchedule) replace the reference's optim.SGD(lr): both stages
+    share the config, the schedule and ONE device step counter, ticked once at the end of the step, so the
+    captured graph follows the schedule. Without them `lr` is a by-value kernel argument: changing a
+    stage's `lr` attribute after the first step does not reach a captured graph (use a schedule and
+    LRSchedule.set_lr)."""
 
     def __init__(self, client: Optional[ModelPartA] = None, server: Optional[ModelPartB] = None,
                  lr: float = LR, device="cuda", graph: bool = True, loss_log: Optional[LossLog] = None,
                  conv: str = CONV_DEFAULT, act16: bool = True, fuse_client_backward: bool = True,
-                 graph_inputs: int = 4):
+                 graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
-        self.client = ClientStage(client, lr, self.device)
-        self.server = ServerStage(server, lr, self.device, loss_log, conv=conv)
+        self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule)
+        self.server = ServerStage(server, lr, self.device, loss_log, conv=conv, optim=self.client.optim,
+                                  schedule=self.client.schedule)
+        if self.server.optim is not None:
+            self.client.step_ctr = self.server.step_ctr
+            self.client.auto_tick = self.server.auto_tick = False   # _eager ticks the shared counter
         # the cut's per-sample max rides along with the cut (fused into conv1) for the x3 kernels; with the
         # x3 forward AND wgrad the client writes the server's split input images directly (no f32 cut)
         self.client.emit_amax = "x3" in (self.server.impl_fwd, self.server.impl_wgrad)
@@ -680,15 +765,40 @@ class SplitTrainer:
                                torch.float32, self.device)
             # the client's update joins the server's optimizer launch (its slabs are complete once the
             # dgrad has run; bit-identical to step_from_slabs) when both stages step at one lr
-            one = c.lr == self.server.lr
-            self.server.step_request(act, y, act_amax=c._act_amax, act16=a16,
-                                     client_fuse=(x, c._relu_bits, slabs),
-                                     extra_segments=[(c.params, c.grads, slabs)] if one else ())
+            s = self.server
+            if s.optim is None and c.optim is None:
+                one, seg = c.lr == s.lr, (c.params, c.grads, slabs)
+            else:   # one recipe, one schedule and one counter (a config given to this trainer)
+                one = c.optim is s.optim and c.schedule is s.schedule and c.step_ctr is s.step_ctr
+                seg = c.optim_segment(slabs) if one else None
+            s.step_request(act, y, act_amax=c._act_amax, act16=a16, client_fuse=(x, c._relu_bits, slabs),
+                           extra_segments=[seg] if one else ())
             if not one:
                 c.step_from_slabs(slabs)
-            return
-        cut_grad, _ = self.server.step_request(act, y, act_amax=self.client._act_amax, act16=a16)
-        self.client.backward_step(cut_grad)
+        else:
+            cut_grad, _ = self.server.step_request(act, y, act_amax=self.client._act_amax, act16=a16)
+            self.client.backward_step(cut_grad)
+        if self.server.optim is not None and not self.server.auto_tick:
+            ops.tick(self.server.step_ctr)
+
+    def _optim_state(self):
+        """The device tensors of the optimizer state, by name (momentum buffers and step counters)."""
+        return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
+                if st.optim is not None for k, a in (("momentum_buffer", "buf"), ("step", "step_ctr"))}
+
+    def optimizer_state(self) -> Dict[str, torch.Tensor]:
+        """CPU copies of the optimizer state (empty without an optimizer config: plain SGD has none). With
+        the modules' state_dict() it resumes training bit for bit (load_optimizer_state)."""
+        return {k: t.detach().cpu().clone() for k, t in self._optim_state().items()}
+
+    def load_optimizer_state(self, state: Dict[str, torch.Tensor]) -> None:
+        """Copy a saved optimizer_state() into the device state — also under already captured graphs,
+        which read exactly these tensors."""
+        own = self._optim_state()
+        if set(state) != set(own):
+            raise ValueError(f"load_optimizer_state: expected keys {sorted(own)}, got {sorted(state)}")
+        for k, t in own.items():
+            t.copy_(state[k])
 
     def static_inputs(self, B: int):
         g = self._graph_for(B)
@@ -707,6 +817,7 @@ class SplitTrainer:
         # parameters and the loss log so the warm-up leaves no trace.
         saved_c, saved_s = self.client.params.clone(), self.server.params.clone()
         saved_ctr = self.server.loss_log.counter.clone()
+        saved_opt = {k: t.clone() for k, t in self._optim_state().items()}   # momentum buffers, step counters
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
@@ -719,6 +830,8 @@ class SplitTrainer:
         self.client.params.copy_(saved_c)
         self.server.params.copy_(saved_s)
         self.server.loss_log.counter.copy_(saved_ctr)
+        for k, t in self._optim_state().items():
+            t.copy_(saved_opt[k])
         g = {"graph": graph, "x": x, "y": y}
         self._graphs[key] = g
         return g

@@ -556,6 +556,97 @@ def sgd_multi_from_slabs(segments, lr, loss=None):
               float(lr), lv, ln, float(lsc), ring, cap, ctr, _stream(stream_of))
 
 
+def _host_arrays(columns, n_int=2, k=4):
+    """Host arrays (length k) for the *_multi_from_slabs entry points, as void pointers: device pointers,
+    except the last n_int columns (nslab, n), which are ints."""
+    P = ctypes.c_void_p
+    types = [P] * (len(columns) - n_int) + [ctypes.c_int] * n_int
+    return [ctypes.cast((t * k)(*col), P) for t, col in zip(types, columns)]
+
+
+def _loss_args(loss):
+    if loss is None:
+        return None, 0, 0.0, None, 0, None
+    values, scale, ring, counter = loss
+    return (_dev(values, "values"), values.numel(), float(scale), _dev(ring, "ring"), ring.numel(),
+            _dev(counter, "counter", (1,), torch.int32))
+
+
+def _lr_args(lr_table, step):
+    """(table pointer, length, step counter pointer) of a device learning-rate table (optim.LRSchedule.table)
+    and a stage's device step counter."""
+    if lr_table.dim() != 1 or lr_table.numel() < 1:
+        raise ValueError("lr_table: expected a 1-D table of at least one rate")
+    return _dev(lr_table, "lr_table"), lr_table.numel(), _dev(step, "step", (1,), torch.int32)
+
+
+def sgdm_from_slabs(param, grad, buf, slabs, lr_table, step, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                    nesterov=False):
+    """torch.optim.SGD's step from sum(slabs) with the rate lr_table[min(step, len - 1)] read on the device
+    (slk_sgdm_from_slabs); grad (may be None) receives the reduced gradient, buf is the momentum buffer
+    (may be None when momentum is 0). The caller advances `step` (tick) after the stage's launches."""
+    nslab, n = slabs.shape
+    _dev(param, "param", (n,))
+    gptr = _dev(grad, "grad", (n,)) if grad is not None else None
+    bptr = _dev(buf, "buf", (n,)) if buf is not None else None
+    _lib.call("slk_sgdm_from_slabs", param.data_ptr(), gptr, bptr, _dev(slabs, "slabs"), nslab, n,
+              *_lr_args(lr_table, step), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+              _stream(param))
+
+
+def sgdm_multi_from_slabs(segments, lr_table, step, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+                          loss=None):
+    """ONE launch: sgdm_from_slabs(param, grad, buf, slabs, ...) for each of `segments` (<= 4), plus
+    loss_log(*loss) — bit-identical to the separate launches (slk_sgdm_multi_from_slabs)."""
+    k = len(segments)
+    if not 0 <= k <= 4:
+        raise ValueError("sgdm_multi_from_slabs: at most 4 segments")
+    cols = [[], [], [], [], [], []]
+    for param, grad, buf, sl in segments:
+        nsl, n = sl.shape
+        row = (_dev(param, "param", (n,)), _dev(grad, "grad", (n,)) if grad is not None else None,
+               _dev(buf, "buf", (n,)) if buf is not None else None, _dev(sl, "slabs"), int(nsl), int(n))
+        for c, v in zip(cols, row):
+            c.append(v)
+    stream_of = segments[0][0] if k else (loss[0] if loss is not None else None)
+    if stream_of is None:
+        return
+    _lib.call("slk_sgdm_multi_from_slabs", *_host_arrays(cols), k, *_lr_args(lr_table, step), float(momentum),
+              float(dampening), float(weight_decay), int(bool(nesterov)), *_loss_args(loss), _stream(stream_of))
+
+
+def adamw_from_slabs(param, grad, m, v, slabs, lr_table, step, beta1, beta2, eps, weight_decay=0.0, decoupled=True):
+    """torch.optim.AdamW's (decoupled) or torch.optim.Adam(weight_decay)'s step from sum(slabs), t = step + 1,
+    the rate read from the device table (slk_adamw_from_slabs); grad may be None."""
+    nslab, n = slabs.shape
+    gptr = _dev(grad, "grad", (n,)) if grad is not None else None
+    _lib.call("slk_adamw_from_slabs", _dev(param, "param", (n,)), gptr, _dev(m, "m", (n,)), _dev(v, "v", (n,)),
+              _dev(slabs, "slabs"), nslab, n, *_lr_args(lr_table, step), float(beta1), float(beta2), float(eps),
+              float(weight_decay), int(bool(decoupled)), _stream(param))
+
+
+def adamw_multi_from_slabs(segments, lr_table, step, beta1, beta2, eps, weight_decay=0.0, decoupled=True):
+    """ONE launch: adamw_from_slabs(param, grad, m, v, slabs, ...) for each of `segments` (<= 4),
+    bit-identical to the separate launches (slk_adamw_multi_from_slabs)."""
+    k = len(segments)
+    if not 1 <= k <= 4:
+        raise ValueError("adamw_multi_from_slabs: 1 to 4 segments")
+    cols = [[], [], [], [], [], [], []]
+    for param, grad, m, v, sl in segments:
+        nsl, n = sl.shape
+        row = (_dev(param, "param", (n,)), _dev(grad, "grad", (n,)) if grad is not None else None,
+               _dev(m, "m", (n,)), _dev(v, "v", (n,)), _dev(sl, "slabs"), int(nsl), int(n))
+        for c, val in zip(cols, row):
+            c.append(val)
+    _lib.call("slk_adamw_multi_from_slabs", *_host_arrays(cols), k, *_lr_args(lr_table, step), float(beta1),
+              float(beta2), float(eps), float(weight_decay), int(bool(decoupled)), _stream(segments[0][0]))
+
+
+def tick(counter):
+    """++counter on the device (a stage's optimizer step counter; advances inside a captured graph)."""
+    _lib.call("slk_tick", _dev(counter, "counter", (1,), torch.int32), _stream(counter))
+
+
 def sgd(param, grad, lr):
     n = param.numel()
     _lib.call("slk_sgd", _dev(param, "param"), _dev(grad, "grad", tuple(param.shape)), n, float(lr),

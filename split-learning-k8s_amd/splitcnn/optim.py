@@ -1,0 +1,161 @@
+"""Optimizer recipes and learning-rate schedules for the stage engines (engine.py: K2, wide.py: K5).
+
+The reference trains with two fixed recipes (optim.SGD(lr=0.01): src/client_part.py:17,133,
+src/server_part.py:15,52; the widened config with Adam(lr=1e-3)). `SGD` and `Adam` here are plain config
+objects with torch's semantics (torch.optim.SGD; torch.optim.Adam / AdamW) for the fused reduce + step
+kernels slk_sgdm_* and slk_adamw_*; `LRSchedule` is the learning rate as a device table those kernels
+index with the stage's device step counter, so a captured HIP graph follows a schedule (or `set_lr`)
+without being recaptured and without a host sync.
+
+    from splitcnn import optim
+    sched = optim.LRSchedule.warmup_cosine(0.05, warmup=100, total=2000)
+    tr = SplitTrainer(client, server, optim=optim.SGD(0.05, momentum=0.9, nesterov=True, weight_decay=5e-4),
+                      schedule=sched)
+
+Limits: one rate and one recipe per stage (no per-parameter groups), no gradient clipping, and the
+multi-GPU classes of dist.py take only stages built without a config.
+"""
+from __future__ import annotations
+
+import math
+from typing import Callable, Sequence, Tuple
+
+import numpy as np
+import torch
+
+
+class SGD:
+    """torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov) as a config."""
+
+    def __init__(self, lr: float, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
+                 weight_decay: float = 0.0):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.lr, self.momentum, self.dampening = float(lr), float(momentum), float(dampening)
+        self.nesterov, self.weight_decay = bool(nesterov), float(weight_decay)
+
+    def kernel_args(self) -> dict:
+        return {"momentum": self.momentum, "dampening": self.dampening, "weight_decay": self.weight_decay,
+                "nesterov": self.nesterov}
+
+    def __repr__(self):
+        return (f"SGD(lr={self.lr}, momentum={self.momentum}, dampening={self.dampening}, "
+                f"nesterov={self.nesterov}, weight_decay={self.weight_decay})")
+
+
+class Adam:
+    """torch.optim.AdamW (decoupled=True, the default) or torch.optim.Adam(weight_decay=...) (decoupled=False)
+    as a config; with weight_decay 0 the two are the same update."""
+
+    def __init__(self, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, decoupled: bool = True):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.decoupled = float(weight_decay), bool(decoupled)
+
+    def kernel_args(self) -> dict:
+        return {"beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps, "weight_decay": self.weight_decay,
+                "decoupled": self.decoupled}
+
+    def __repr__(self):
+        return (f"Adam(lr={self.lr}, betas={self.betas}, eps={self.eps}, weight_decay={self.weight_decay}, "
+                f"decoupled={self.decoupled})")
+
+
+class LRSchedule:
+    """The learning rate of every optimizer step as an f32 device table: step k (0-based, the stage's device
+    counter) runs at table[min(k, len - 1)]. The host fills the table once; the kernels read it."""
+
+    def __init__(self, values: Sequence[float], device="cuda"):
+        v = np.asarray(values, dtype=np.float32).reshape(-1)
+        if v.size < 1:
+            raise ValueError("LRSchedule: needs at least one rate")
+        if not np.all(np.isfinite(v)) or np.any(v < 0):
+            raise ValueError("LRSchedule: rates must be finite and >= 0")
+        self.values = v.copy()
+        self.table = torch.from_numpy(v.copy()).to(device)
+
+    def __len__(self):
+        return int(self.values.size)
+
+    def lr_at(self, step: int) -> float:
+        """The rate of optimizer step `step` (host copy of the table; past the end the last value holds)."""
+        return float(self.values[min(max(int(step), 0), len(self) - 1)])
+
+    def to(self, device) -> "LRSchedule":
+        """Move the table (a no-op on its own device); captured graphs hold the table's address, so move
+        a schedule before the first step only."""
+        if self.table.device != torch.device(device):
+            self.table = self.table.to(device)
+        return self
+
+    def set_lr(self, lr: float) -> None:
+        """Overwrite a constant (one-entry) table in place: an asynchronous device write on the current
+        stream, so the next step — eager or a replay of an already captured graph — runs at `lr`."""
+        if len(self) != 1:
+            raise ValueError("LRSchedule.set_lr: only a constant (one-entry) schedule can be overwritten")
+        if not (lr >= 0.0 and math.isfinite(lr)):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        self.values[0] = lr
+        self.table.fill_(float(lr))
+
+    # ---- constructors
+    @classmethod
+    def constant(cls, lr: float, device="cuda") -> "LRSchedule":
+        return cls([lr], device)
+
+    @classmethod
+    def from_values(cls, seq: Sequence[float], device="cuda") -> "LRSchedule":
+        return cls(seq, device)
+
+    @classmethod
+    def from_torch(cls, make_scheduler: Callable, base_lr: float, steps: int, device="cuda") -> "LRSchedule":
+        """Record a torch.optim.lr_scheduler: make_scheduler(optimizer) -> scheduler runs on a dummy CPU
+        parameter at `base_lr`; entry k is get_last_lr()[0] after k scheduler steps."""
+        if steps < 1:
+            raise ValueError("LRSchedule.from_torch: steps must be >= 1")
+        opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=base_lr)
+        sched = make_scheduler(opt)
+        vals = []
+        for k in range(steps):
+            vals.append(sched.get_last_lr()[0])
+            if k + 1 < steps:   # a scheduler with a fixed length (OneCycleLR) refuses a step past its end
+                opt.step()
+                sched.step()
+        return cls(vals, device)
+
+    @classmethod
+    def warmup_cosine(cls, base_lr: float, warmup: int, total: int, min_lr: float = 0.0,
+                      device="cuda") -> "LRSchedule":
+        """Linear warm-up over `warmup` steps (base_lr * (k + 1) / warmup), then a half cosine from base_lr
+        to min_lr at step total - 1 (a LambdaLR)."""
+        if not 0 <= warmup < total:
+            raise ValueError("LRSchedule.warmup_cosine: need 0 <= warmup < total")
+        floor = min_lr / base_lr if base_lr > 0 else 0.0
+        span = max(1, total - 1 - warmup)
+
+        def factor(k):
+            if k < warmup:
+                return (k + 1) / warmup
+            return floor + (1.0 - floor) * 0.5 * (1.0 + math.cos(math.pi * min(k - warmup, span) / span))
+        return cls.from_torch(lambda o: torch.optim.lr_scheduler.LambdaLR(o, factor), base_lr, total, device)
+
+    @classmethod
+    def step_decay(cls, base_lr: float, step_size: int, gamma: float, steps: int, device="cuda") -> "LRSchedule":
+        """base_lr * gamma ** (k // step_size) (a StepLR)."""
+        return cls.from_torch(lambda o: torch.optim.lr_scheduler.StepLR(o, step_size, gamma), base_lr, steps, device)

@@ -35,6 +35,7 @@ from . import _lib
 from . import ops
 from .engine import TIMER, LossLog, _Buffers, eval_batch_on, evaluate_on, register_graph_inputs, select_graph
 from .ops import _dev, _stream
+from .optim import Adam, LRSchedule
 
 P_DROP = 0.25
 KEEP_THRESHOLD = int(round(P_DROP * 4294967296.0))          # keep iff hash >= p * 2^32
@@ -338,14 +339,46 @@ class _WideHeadFn(torch.autograd.Function):
         return (c8_to_nchw(dcut).to(ctx.in_dtype), g[:163840].view(10, 16384), g[163840:], None, None, None, None)
 
 # ------------------------------------------------------------------------------------ stages
-class WideClientStage:
+class _AdamRecipe:
+    """Optimizer recipe of a K5 stage. Without a config (optim=None, schedule=None) the stage runs
+    torch.optim.Adam(lr, betas, eps) on slk_adam_*, `lr` a by-value kernel argument (frozen into a captured
+    graph). With an optim.Adam config and / or an optim.LRSchedule it runs slk_adamw_*: weight decay
+    (AdamW or Adam's) and the rate read from the schedule's device table at the stage's step_ctr."""
+
+    def _init_optim(self, optim, schedule):
+        if optim is not None and not isinstance(optim, Adam):
+            raise TypeError(f"optim: expected splitcnn.optim.Adam or None, got {type(optim).__name__}")
+        if optim is None and schedule is not None:
+            optim = Adam(self.lr, self.betas, self.eps)
+        self.optim, self.schedule = optim, None
+        if optim is None:
+            return
+        self.lr, self.betas, self.eps = optim.lr, optim.betas, optim.eps
+        self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
+
+    def _adamw(self, segments, write_grads=True, fuse=True):
+        """slk_adamw_* on (lo, n, slabs) slices of this stage (slabs [nslab, n]): ONE launch (fuse) or one
+        per slice."""
+        segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
+                 self.v[lo:lo + n], sl) for lo, n, sl in segments]
+        kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
+        if fuse and len(segs) > 1:
+            with TIMER("adamw_multi_from_slabs"):
+                ops.adamw_multi_from_slabs(segs, **kw)
+        else:
+            for g in segs:
+                with TIMER("adamw_from_slabs"):
+                    ops.adamw_from_slabs(*g, **kw)
+
+
+class WideClientStage(_AdamRecipe):
     """Client half: forward(x) -> cut (bf16 C8); backward_step(dcut) = activations.backward(grads) +
     Adam (client_part.py:114,132-133 for the widened model)."""
 
     OFF = {"W1": 0, "b1": 1728, "W2": 1792, "b2": 75520, "W3": 75648, "b3": 370560}
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
-                 eps=EPS):
+                 eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartA()).to(self.device)
         m = self.model
@@ -356,6 +389,7 @@ class WideClientStage:
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps = lr, betas, eps
+        self._init_optim(optim, schedule)
         self.fuse_adam = True  # step_from_slabs: the three Adam segments in one launch
         self.sh = new_shadows(self.device)   # bf16 conv weight shadows (slk_wide_shadows layouts)
         self._buf = _Buffers()
@@ -410,7 +444,9 @@ class WideClientStage:
     def step_from_slabs(self, s1, s2, s3):
         """Adam on all client parameters from the three slab sets (ONE launch, bit-identical to one
         slk_adam_from_slabs per set), then shadows + step counter."""
-        if self.fuse_adam:
+        if self.optim is not None:
+            self._adamw(((0, 1792, s1), (1792, 73856, s2), (75648, 295168, s3)), fuse=self.fuse_adam)
+        elif self.fuse_adam:
             P, I = ctypes.c_void_p, ctypes.c_int
             segs = ((0, 1792, s1), (1792, 73856, s2), (75648, 295168, s3))
             arr = lambda ts: ctypes.cast((P * 3)(*ts), P)  # noqa: E731
@@ -450,19 +486,23 @@ class WideClientStage:
     def step_from_grads(self):
         """Adam from self.grads (e.g. after an all-reduce over the client ranks)."""
         g = self.grads
-        _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
-           CLIENT_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-           self.step_ctr.data_ptr(), _stream(g))
+        if self.optim is not None:
+            self._adamw([(0, CLIENT_NPARAM, g.view(1, -1))], write_grads=False)
+        else:
+            _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
+               CLIENT_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+               self.step_ctr.data_ptr(), _stream(g))
         self.refresh_shadows()
         _k("tick", self.step_ctr.data_ptr(), _stream(g))
 
 
-class WideServerStage:
+class WideServerStage(_AdamRecipe):
     """Server half: step_request(cut, labels, step) -> (dcut, loss_i): dropout + fc + CE forward and
     backward, Adam, loss logged to the device ring (server_part.py:38-58 for the widened model)."""
 
     def __init__(self, model: Optional[WideModelPartB] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
-                 eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None):
+                 eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None, optim: Optional[Adam] = None,
+                 schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartB()).to(self.device)
         self.params, self.grads = _flat([self.model.fc.weight, self.model.fc.bias], self.device)
@@ -471,6 +511,7 @@ class WideServerStage:
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
+        self._init_optim(optim, schedule)
         self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -529,9 +570,12 @@ class WideServerStage:
 
     def step_from_slabs(self, sf):
         s = _stream(sf)
-        _k("adam_from_slabs", self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                  self.v.data_ptr(), sf.data_ptr(), sf.shape[0], SERVER_NPARAM, float(self.lr),
-                  float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_ctr.data_ptr(), s)
+        if self.optim is not None:
+            self._adamw([(0, SERVER_NPARAM, sf)])
+        else:
+            _k("adam_from_slabs", self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+               self.v.data_ptr(), sf.data_ptr(), sf.shape[0], SERVER_NPARAM, float(self.lr),
+               float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_ctr.data_ptr(), s)
         self.refresh_shadows()
         _k("tick", self.step_ctr.data_ptr(), s)
 
@@ -574,9 +618,12 @@ class WideServerStage:
         """Adam from the accumulated gradient, loss logged (sum of the parts), step counter ticked."""
         g = self.grads
         s = _stream(g)
-        _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
-           SERVER_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-           self.step_ctr.data_ptr(), s)
+        if self.optim is not None:
+            self._adamw([(0, SERVER_NPARAM, g.view(1, -1))], write_grads=False)
+        else:
+            _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
+               SERVER_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+               self.step_ctr.data_ptr(), s)
         self.refresh_shadows()
         parts = self._b("loss_parts", (nparts,), _F32)
         _k("loss_log", parts.data_ptr(), nparts, 1.0, self.loss_log.ring.data_ptr(), self.loss_log.ring.numel(),
@@ -588,13 +635,20 @@ class WideServerStage:
 
 class WideTrainer:
     """Both widened stages fused on one GPU, the whole step captured as one HIP graph (like
-    engine.SplitTrainer): client fwd -> server dropout/fc/CE/bwd/Adam -> client bwd/Adam."""
+    engine.SplitTrainer): client fwd -> server dropout/fc/CE/bwd/Adam -> client bwd/Adam.
+
+    `optim` (optim.Adam) and `schedule` (optim.LRSchedule) replace Adam(lr=1e-3): both stages share the
+    config and the schedule's device table, each indexing it with its own step counter (the server's also
+    seeds the dropout mask), so the captured graph follows the schedule. Without them `lr` is a by-value
+    kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it)."""
 
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
-                 device="cuda", graph: bool = True, seed: int = 0):
+                 device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
+                 schedule: Optional[LRSchedule] = None):
         self.device = torch.device(device)
-        self.client = WideClientStage(client, self.device)
-        self.server = WideServerStage(server, self.device, seed=seed)
+        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule)
+        self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
+                                      schedule=self.client.schedule)
         self.graph = graph
         self._graphs = {}
         self.graph_inputs = 4   # caller input buffers captured directly (as engine.SplitTrainer)
@@ -616,6 +670,26 @@ class WideTrainer:
     def _state(self):
         c, s = self.client, self.server
         return [c.params, c.m, c.v, c.step_ctr, s.params, s.m, s.v, s.step_ctr, s.loss_log.counter]
+
+    def _optim_state(self):
+        return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
+                for k, a in (("exp_avg", "m"), ("exp_avg_sq", "v"), ("step", "step_ctr"))}
+
+    def optimizer_state(self):
+        """CPU copies of Adam's m / v and the step counters of both stages. With the modules' state_dict()
+        it resumes training bit for bit (load_optimizer_state)."""
+        return {k: t.detach().cpu().clone() for k, t in self._optim_state().items()}
+
+    def load_optimizer_state(self, state) -> None:
+        """Copy a saved optimizer_state() into the device state and rebuild the bf16 / C8 weight shadows from
+        the f32 masters (load the modules' state_dict() first) — also under already captured graphs."""
+        own = self._optim_state()
+        if set(state) != set(own):
+            raise ValueError(f"load_optimizer_state: expected keys {sorted(own)}, got {sorted(state)}")
+        for k, t in own.items():
+            t.copy_(state[k])
+        self.client.refresh_shadows()
+        self.server.refresh_shadows()
 
     def _graph_for(self, B, x=None, y=None):
         """The step's graph on the static inputs, or (x, y given) on those caller buffers."""
