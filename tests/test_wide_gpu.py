@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import wide_step as W
+from wide_ref64 import bf16_close, codes_close, grad_close
 
 pytestmark = pytest.mark.gpu
 
@@ -30,43 +31,6 @@ def _np(t):
 def _nchw(t):
     from splitcnn.wide import c8_to_nchw
     return _np(c8_to_nchw(t))
-
-
-def bf16_close(got, want, frac=1e-3, acc_floor=4e-6):
-    """One bf16 ulp where the rounding flipped, on top of the f32 accumulation noise floor
-    (acc_floor x the tensor's max: f32 sums of O(1) terms carry absolute, not relative, error)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = got != want
-    if not bad.any():
-        return
-    d = np.abs(got - want)[bad]
-    lim = 2.0 ** -7 * np.abs(want)[bad] + acc_floor * np.abs(want).max() + 1e-30
-    assert (d <= lim * 1.0001).all(), f"max rel diff {np.max(d / np.maximum(np.abs(want[bad]), 1e-30)):.3g}"
-    assert bad.mean() <= frac, f"{bad.mean():.2e} of elements differ by one bf16 ulp"
-
-
-def codes_close(c_pre, code_got, code_want, rtol=1e-5):
-    """Routing differences must be numerical ties of the f32/f64 pre-pool values c_pre."""
-    diff = code_got != code_want
-    if not diff.any():
-        return
-    B, C, H, Wd = c_pre.shape
-    win = c_pre.reshape(B, C, H // 2, 2, Wd // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, Wd // 2, 4)
-    win = np.maximum(win, 0.0)[diff]
-    scale = max(np.abs(c_pre).max(), 1e-30)
-
-    def val(code):
-        return np.where(code < 4, np.take_along_axis(win, np.minimum(code, 3)[:, None], axis=1)[:, 0], 0.0)
-    va, vb = val(code_got[diff]), val(code_want[diff])
-    assert (np.abs(va - vb) <= rtol * scale).all(), f"{diff.sum()} non-tie routing differences"
-    assert diff.mean() < 1e-3
-
-
-def grad_close(got, want, rtol=1e-5):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    err = np.abs(got - want).max() / max(np.abs(want).max(), 1e-30)
-    assert err <= rtol, err
 
 
 def _params(client, server):
