@@ -275,7 +275,9 @@ int slk_eval_accumulate(const float* loss_i, const int64_t* pred, const int64_t*
  * 16 < nslab <= 64 -> 4 partial sums over slabs w, w+4, w+8, ... (w = 0..3) added in w order; nslab > 64 ->
  * 16 partial sums over slabs w, w+16, ... added in w order (Adam from slabs: the same three forms). Each is
  * a fixed function of (slabs, nslab): bit-stable run to run, but results from different forms are not
- * bitwise comparable. */
+ * bitwise comparable. Where the prior out[i] of accumulate = 1 enters, in float32: the ascending form adds
+ * it last, out = out + (((s0 + s1) + s2) + ...); the 4- and 16-partial forms start their chain of partials
+ * at it, out = (((out + p0) + p1) + p2) + ... (tests/test_reduce_order_gpu.py pins all of this bit for bit). */
 int slk_reduce_slabs(const float* slabs, int nslab, int n, float* out, int accumulate, void* stream);
 
 /* Fused deterministic slab reduction + SGD (lr, no momentum, no weight decay):
