@@ -38,6 +38,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from .graphs import capture, replay_on
+
 CLIENT_N = 320
 SERVER_N = 110666
 # bytes per sample of the x3 split images (act16: 32 channels x 676 pixels x (hi, lo) f16) = the f32 cut's
@@ -189,18 +191,9 @@ class Replicated:
         dev = self.bucket.device
         x = torch.zeros((B, 1, 28, 28), dtype=torch.float32, device=dev)
         y = torch.zeros((B,), dtype=torch.int64, device=dev)
-        # warm up on a side stream (allocations happen here, not during capture); the compute segment
-        # writes only scratch and the bucket, so the warm-up leaves no trace in the parameters
-        st = torch.cuda.Stream(dev)
-        st.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(st):
-            self._compute_fused(x, y)
-        torch.cuda.current_stream(dev).wait_stream(st)
-        graph = torch.cuda.CUDAGraph()
-        # thread-local capture mode: ProcessGroupNCCL's watchdog thread queries the events of earlier
-        # collectives while this thread captures; in the default global mode that query invalidates it
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            self._compute_fused(x, y)
+        # the compute segment writes only scratch and the bucket, so the warm-up leaves no trace in the
+        # parameters: nothing to preserve
+        graph, _ = capture(lambda: self._compute_fused(x, y), dev)
         g = {"graph": graph, "x": x, "y": y}
         self._graphs[B] = g
         return g
@@ -214,12 +207,7 @@ class Replicated:
     def _step_fused(self, x, y):
         from . import ops
         if self.graph:
-            g = self._graph_for(x.shape[0])
-            if x.data_ptr() != g["x"].data_ptr():
-                g["x"].copy_(x, non_blocking=True)
-            if y.data_ptr() != g["y"].data_ptr():
-                g["y"].copy_(y, non_blocking=True)
-            g["graph"].replay()
+            replay_on(self._graph_for(x.shape[0]), x, y)
         else:
             self._compute_fused(x, y)
         dist.all_reduce(self.bucket, group=self.group)
@@ -620,19 +608,11 @@ class Hub:
         if self.ship_amax:
             self._buf("amax", (G,), torch.float32, device).zero_()
         n = (B // self.micro) * 32 * 26 * 26
-        st = torch.cuda.Stream(device)
         for k in range(self.micro):
             if codec is not None:
                 for ci in range(self.nclients):
                     codec.buffers(("s", ci, k), n, device)[0].zero_()
-            st.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(st):
-                self._chunk(k, B, device, codec)
-            torch.cuda.current_stream(device).wait_stream(st)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):   # see Replicated._graph_for
-                self._chunk(k, B, device, codec)
-            self._graphs[k, B, codec is not None] = g
+            self._graphs[k, B, codec is not None], _ = capture(lambda: self._chunk(k, B, device, codec), device)
         torch.cuda.current_stream(device).synchronize()
 
     def prepare(self, B: int, device) -> None:

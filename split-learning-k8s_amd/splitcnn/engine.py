@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .graphs import GraphedTrainer
 from .model_def import ModelPartA, ModelPartB
 from .optim import SGD, LRSchedule
 
@@ -598,124 +599,13 @@ class ServerStage(_SgdRecipe):
         return pred, loss_i
 
 
-def _n_caller_graphs(tr, B: int) -> int:
-    return sum(1 for k in tr._graphs if isinstance(k, tuple) and k[0] == B)
-
-
-def _is_static(tr, x, y) -> bool:
-    st = tr._graphs.get(x.shape[0])
-    return st is not None and x.data_ptr() == st["x"].data_ptr() and y.data_ptr() == st["y"].data_ptr()
-
-
-def register_graph_inputs(tr, x, y) -> bool:
-    """Capture trainer `tr`'s step graph on the caller's own (x, y) buffers now — a loader declaring its
-    ring of batch buffers — so step() on them replays with no copy and no capture later. Counts toward
-    `tr.graph_inputs`; False (nothing captured) when the buffers do not qualify or that budget is spent.
-    Shared by SplitTrainer and wide.WideTrainer (`_graphs`, `_graph_for`, `_own_buffers_ok`)."""
-    if not tr.graph or not tr._own_buffers_ok(x, y):
-        return False
-    B = x.shape[0]
-    if _is_static(tr, x, y) or (B, x.data_ptr(), y.data_ptr()) in tr._graphs:
-        return True
-    if _n_caller_graphs(tr, B) >= tr.graph_inputs:
-        return False
-    tr._graph_for(B, x, y)
-    return True
-
-
-def select_graph(tr, x, y):
-    """The graph step() replays directly on (x, y), or None (then it copies into the static inputs).
-    The static inputs handed back (static_inputs(B)) replay their own graph; a caller buffer pair gets a
-    graph of its own the SECOND time it is seen (a loader's ring), so a one-off fresh tensor goes
-    through the static-input copy and is not kept alive by a graph."""
-    if not tr._own_buffers_ok(x, y):
-        return None
-    if _is_static(tr, x, y):
-        return tr._graphs[x.shape[0]]
-    B = x.shape[0]
-    key = (B, x.data_ptr(), y.data_ptr())
-    g = tr._graphs.get(key)
-    if g is None:
-        n = tr._seen.get(key, 0) + 1
-        tr._seen[key] = n
-        if n >= 2 and _n_caller_graphs(tr, B) < tr.graph_inputs:
-            g = tr._graph_for(B, x, y)
-            del tr._seen[key]
-    return g
-
-
-def _eval_graph_for(tr, B: int, metrics, x_tail: tuple):
-    """Trainer `tr`'s evaluation pass for batch size B as a HIP graph on static inputs: one linear chain on
-    one stream (client forward, server forward, head, accumulate), kept in `tr._eval_graphs` — not `_graphs`,
-    whose keys the step's caller-buffer budget counts. The accumulator of `metrics` is baked in: another
-    metrics object (or none) recaptures on the same static inputs. Warm-up and capture leave the accumulator
-    and the evaluation label flag as they were. Shared by SplitTrainer and wide.WideTrainer (`_eval_eager`)."""
-    g = tr._eval_graphs.get(B)
-    if g is not None and g["metrics"] is metrics:
-        return g
-    if g is None:
-        x = torch.zeros((B,) + x_tail, dtype=torch.float32, device=tr.device)
-        y = torch.zeros((B,), dtype=torch.int64, device=tr.device)
-    else:
-        x, y = g["x"], g["y"]
-    state = [tr.server.eval_err_flag] + ([metrics.acc] if metrics is not None else [])
-    saved = [t.clone() for t in state]
-    s = torch.cuda.Stream(tr.device)
-    s.wait_stream(torch.cuda.current_stream(tr.device))
-    with torch.cuda.stream(s):
-        tr._eval_eager(x, y, metrics)
-    torch.cuda.current_stream(tr.device).wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        out = tr._eval_eager(x, y, metrics)
-    for t, v in zip(state, saved):
-        t.copy_(v)
-    # the buffers this graph writes: a replay runs no Python, so eval_batch_on re-points the public
-    # attributes (server.eval_logits, and the wide trainer's eval_cut) at them after every replay
-    g = {"graph": graph, "x": x, "y": y, "metrics": metrics, "out": out, "logits": tr.server.eval_logits,
-         "cut": getattr(tr, "eval_cut", None)}
-    tr._eval_graphs[B] = g
-    return g
-
-
-def eval_batch_on(tr, x, y, metrics, x_tail: tuple):
-    """One evaluation batch on trainer `tr`, asynchronous: returns (pred, loss_i), stage buffers that the
-    next batch of the same size overwrites."""
-    if tuple(x.shape[1:]) != x_tail or tuple(y.shape) != (x.shape[0],):
-        raise ValueError(f"eval_batch: expected x [B,{','.join(map(str, x_tail))}] and y [B], got "
-                         f"{tuple(x.shape)} and {tuple(y.shape)}")
-    if not tr.graph:
-        return tr._eval_eager(x, y, metrics)
-    g = _eval_graph_for(tr, x.shape[0], metrics, x_tail)
-    g["x"].copy_(x, non_blocking=True)
-    g["y"].copy_(y, non_blocking=True)
-    g["graph"].replay()
-    tr.server.eval_logits = g["logits"]   # this batch size's buffers (another size may have run since)
-    if g["cut"] is not None:
-        tr.eval_cut = g["cut"]
-    return g["out"]
-
-
-def evaluate_on(tr, batches, metrics=None):
-    """Evaluate trainer `tr` over an iterable of device (x, y) batches; one host sync, at the end. With
-    metrics=None the trainer's own EvalMetrics is reset and used; a caller's `metrics` is added to as it is
-    (reset it first for a fresh evaluation)."""
-    from .metrics import EvalMetrics
-    if metrics is None:
-        if tr._eval_metrics is None:
-            tr._eval_metrics = EvalMetrics(tr.device)
-        metrics = tr._eval_metrics.reset()
-    for x, y in batches:
-        tr.eval_batch(x, y, metrics)
-    return metrics.result()
-
-
-class SplitTrainer:
+class SplitTrainer(GraphedTrainer):
     """Both stages fused on ONE GPU (BASELINE config 2): the cut tensor is handed over in place.
 
     `step(x, y)` = client fwd -> server fwd/loss/bwd/SGD -> client bwd/SGD, exactly one reference
     step. With `graph=True` the step is captured once per batch size into a HIP graph (static input
-    buffers; `step` copies into them unless the caller hands in those very buffers).
+    buffers; `step` copies into them unless the caller hands in those very buffers or registered its
+    own: graphs.GraphedTrainer, which also holds evaluate / eval_batch and the optimizer state's save / load).
 
     `optim` (optim.SGD) and `schedule` (optim.LRSchedule) replace the reference's optim.SGD(lr): both stages
     share the config, the schedule and ONE device step counter, ticked once at the end of the step, so the
@@ -723,11 +613,13 @@ class SplitTrainer:
     stage's `lr` attribute after the first step does not reach a captured graph (use a schedule and
     LRSchedule.set_lr)."""
 
+    input_shape = (1, 28, 28)
+
     def __init__(self, client: Optional[ModelPartA] = None, server: Optional[ModelPartB] = None,
                  lr: float = LR, device="cuda", graph: bool = True, loss_log: Optional[LossLog] = None,
                  conv: str = CONV_DEFAULT, act16: bool = True, fuse_client_backward: bool = True,
                  graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
-        self.device = torch.device(device)
+        super().__init__(device, graph, graph_inputs)
         self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule)
         self.server = ServerStage(server, lr, self.device, loss_log, conv=conv, optim=self.client.optim,
                                   schedule=self.client.schedule)
@@ -741,20 +633,6 @@ class SplitTrainer:
         # the x3 dgrad also runs the client's ReLU backward + conv1 wgrad (no cut gradient in HBM)
         # (the client's ReLU mask comes from the bit map conv1_fwd_x3 writes next to the images)
         self.fuse_client_backward = self.server.impl_dgrad == "x3" and self.client.emit_act16 and fuse_client_backward
-        self.graph = graph
-        self._graphs = {}
-        # graphs captured on a caller's own input buffers (a loader's ring of batch buffers): replaying
-        # one reads its inputs where they already are, with no copy into the static inputs; at most
-        # `graph_inputs` such buffer pairs per batch size, any others go through the static inputs
-        self.graph_inputs = graph_inputs
-        self._seen = {}   # (B, x ptr, y ptr) -> times a caller buffer pair went through the static inputs
-        self.global_step = 0
-        self._eval_graphs = {}    # batch size -> the evaluation pass's graph (never in _graphs)
-        self._eval_metrics = None  # evaluate()'s own accumulator, made on first use
-
-    @property
-    def loss_log(self) -> LossLog:
-        return self.server.loss_log
 
     def _eager(self, x, y):
         act = self.client.forward(x)
@@ -786,105 +664,15 @@ class SplitTrainer:
         return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
                 if st.optim is not None for k, a in (("momentum_buffer", "buf"), ("step", "step_ctr"))}
 
-    def optimizer_state(self) -> Dict[str, torch.Tensor]:
-        """CPU copies of the optimizer state (empty without an optimizer config: plain SGD has none). With
-        the modules' state_dict() it resumes training bit for bit (load_optimizer_state)."""
-        return {k: t.detach().cpu().clone() for k, t in self._optim_state().items()}
+    def _state(self):
+        """Both parameter blocks, the loss log's counter and the optimizer state: what a step writes."""
+        return [self.client.params, self.server.params, self.server.loss_log.counter, *self._optim_state().values()]
 
-    def load_optimizer_state(self, state: Dict[str, torch.Tensor]) -> None:
-        """Copy a saved optimizer_state() into the device state — also under already captured graphs,
-        which read exactly these tensors."""
-        own = self._optim_state()
-        if set(state) != set(own):
-            raise ValueError(f"load_optimizer_state: expected keys {sorted(own)}, got {sorted(state)}")
-        for k, t in own.items():
-            t.copy_(state[k])
-
-    def static_inputs(self, B: int):
-        g = self._graph_for(B)
-        return g["x"], g["y"]
-
-    def _graph_for(self, B: int, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
-        """The step's graph for batch size B on the static inputs, or (x, y given) on those buffers."""
-        key = B if x is None else (B, x.data_ptr(), y.data_ptr())
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        if x is None:
-            x = torch.zeros((B, 1, 28, 28), dtype=torch.float32, device=self.device)
-            y = torch.zeros((B,), dtype=torch.int64, device=self.device)
-        # warm up on a side stream (allocations happen here, not during capture), then restore the
-        # parameters and the loss log so the warm-up leaves no trace.
-        saved_c, saved_s = self.client.params.clone(), self.server.params.clone()
-        saved_ctr = self.server.loss_log.counter.clone()
-        saved_opt = {k: t.clone() for k, t in self._optim_state().items()}   # momentum buffers, step counters
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._eager(x, y)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        # thread-local capture: another thread's CUDA calls (a process group's watchdog) cannot void it
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            self._eager(x, y)
-        self.client.params.copy_(saved_c)
-        self.server.params.copy_(saved_s)
-        self.server.loss_log.counter.copy_(saved_ctr)
-        for k, t in self._optim_state().items():
-            t.copy_(saved_opt[k])
-        g = {"graph": graph, "x": x, "y": y}
-        self._graphs[key] = g
-        return g
-
-    def _own_buffers_ok(self, x, y) -> bool:
-        return (x.device == self.device and y.device == self.device and x.dtype == torch.float32
-                and y.dtype == torch.int64 and x.is_contiguous() and y.is_contiguous()
-                and tuple(x.shape[1:]) == (1, 28, 28) and y.shape == (x.shape[0],))
-
-    def register_inputs(self, x: torch.Tensor, y: torch.Tensor) -> bool:
-        """Capture a graph on the caller's own (x, y) buffers now (see `register_graph_inputs`)."""
-        return register_graph_inputs(self, x, y)
-
-    def step(self, x: torch.Tensor, y: torch.Tensor):
-        B = x.shape[0]
-        if self.graph:
-            g = select_graph(self, x, y)
-            if g is not None:
-                g["graph"].replay()
-                self.server.loss_log.note_step(self.global_step)
-                self.global_step += 1
-                return
-            g = self._graph_for(B)
-            if x.data_ptr() != g["x"].data_ptr():
-                g["x"].copy_(x, non_blocking=True)
-            if y.data_ptr() != g["y"].data_ptr():
-                g["y"].copy_(y, non_blocking=True)
-            g["graph"].replay()
-        else:
-            self._eager(x, y)
-        self.server.loss_log.note_step(self.global_step)
-        self.global_step += 1
-
-    # ---- evaluation / prediction: forward only, own `eval_` buffers, no training state touched
+    # ---- evaluation / prediction: forward only, own `eval_` buffers (about 0.5 GB extra at B = 4096), no
+    # training state touched
     def _eval_eager(self, x, y, metrics=None):
         act, amax, a16 = self.client.forward_eval(x)
         return self.server.evaluate(act, y, act16=a16, act_amax=amax, metrics=metrics)
-
-    def eval_batch(self, x: torch.Tensor, y: torch.Tensor, metrics=None):
-        """One held-out batch, asynchronous: (pred, loss_i) (stage buffers; the logits are in
-        server.eval_logits), `metrics` (metrics.EvalMetrics) updated on the device. With graph=True the
-        pass replays a graph captured once per batch size on static inputs that x and y are copied into.
-        The graph holds the accumulator of `metrics`: calling with another metrics object (or none, or
-        alternating with evaluate(), which uses the trainer's own) captures that size again — a warm-up
-        and a capture each switch — so keep to one EvalMetrics per trainer in a loop.
-        Parameters, gradients, the loss log, err_flag and global_step are not touched; the evaluation
-        buffers cost about 0.5 GB extra at B = 4096."""
-        return eval_batch_on(self, x, y, metrics, (1, 28, 28))
-
-    def evaluate(self, batches, metrics=None):
-        """metrics.EvalResult over an iterable of device (x, y) batches — for example
-        DeviceLoader(MnistIDX(root, train=False), 4096, shuffle=False) — with one host sync at the end."""
-        return evaluate_on(self, batches, metrics)
 
     def predict(self, x: torch.Tensor, return_logits: bool = False):
         """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""

@@ -33,7 +33,8 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
-from .engine import TIMER, LossLog, _Buffers, eval_batch_on, evaluate_on, register_graph_inputs, select_graph
+from .engine import TIMER, LossLog, _Buffers
+from .graphs import GraphedTrainer
 from .ops import _dev, _stream
 from .optim import Adam, LRSchedule
 
@@ -633,34 +634,25 @@ class WideServerStage(_AdamRecipe):
         _k("tick", self.step_ctr.data_ptr(), s)
 
 
-class WideTrainer:
+class WideTrainer(GraphedTrainer):
     """Both widened stages fused on one GPU, the whole step captured as one HIP graph (like
-    engine.SplitTrainer): client fwd -> server dropout/fc/CE/bwd/Adam -> client bwd/Adam.
+    engine.SplitTrainer, on graphs.GraphedTrainer): client fwd -> server dropout/fc/CE/bwd/Adam -> client
+    bwd/Adam.
 
     `optim` (optim.Adam) and `schedule` (optim.LRSchedule) replace Adam(lr=1e-3): both stages share the
     config and the schedule's device table, each indexing it with its own step counter (the server's also
     seeds the dropout mask), so the captured graph follows the schedule. Without them `lr` is a by-value
     kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it)."""
 
+    input_shape = (3, 32, 32)
+
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None):
-        self.device = torch.device(device)
+        super().__init__(device, graph)
         self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
                                       schedule=self.client.schedule)
-        self.graph = graph
-        self._graphs = {}
-        self.graph_inputs = 4   # caller input buffers captured directly (as engine.SplitTrainer)
-        self._seen = {}
-        self.global_step = 0
-        self._eval_graphs = {}    # batch size -> the evaluation pass's graph (never in _graphs)
-        self._eval_metrics = None  # evaluate()'s own accumulator, made on first use
-        self.eval_cut = None
-
-    @property
-    def loss_log(self) -> LossLog:
-        return self.server.loss_log
 
     def _eager(self, x, y):
         c = self.client
@@ -672,101 +664,21 @@ class WideTrainer:
         return [c.params, c.m, c.v, c.step_ctr, s.params, s.m, s.v, s.step_ctr, s.loss_log.counter]
 
     def _optim_state(self):
+        """Adam's m / v and the step counters of both stages, by name."""
         return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
                 for k, a in (("exp_avg", "m"), ("exp_avg_sq", "v"), ("step", "step_ctr"))}
 
-    def optimizer_state(self):
-        """CPU copies of Adam's m / v and the step counters of both stages. With the modules' state_dict()
-        it resumes training bit for bit (load_optimizer_state)."""
-        return {k: t.detach().cpu().clone() for k, t in self._optim_state().items()}
-
-    def load_optimizer_state(self, state) -> None:
-        """Copy a saved optimizer_state() into the device state and rebuild the bf16 / C8 weight shadows from
-        the f32 masters (load the modules' state_dict() first) — also under already captured graphs."""
-        own = self._optim_state()
-        if set(state) != set(own):
-            raise ValueError(f"load_optimizer_state: expected keys {sorted(own)}, got {sorted(state)}")
-        for k, t in own.items():
-            t.copy_(state[k])
+    def _state_written(self):
+        """The bf16 / C8 weight shadows follow the f32 masters."""
         self.client.refresh_shadows()
         self.server.refresh_shadows()
 
-    def _graph_for(self, B, x=None, y=None):
-        """The step's graph on the static inputs, or (x, y given) on those caller buffers."""
-        key = B if x is None else (B, x.data_ptr(), y.data_ptr())
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        if x is None:
-            x = torch.zeros((B, 3, 32, 32), dtype=_F32, device=self.device)
-            y = torch.zeros((B,), dtype=torch.int64, device=self.device)
-        saved = [t.clone() for t in self._state()]
-        st = torch.cuda.Stream(self.device)
-        st.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(st):
-            self._eager(x, y)
-        torch.cuda.current_stream(self.device).wait_stream(st)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            self._eager(x, y)
-        for t, v in zip(self._state(), saved):
-            t.copy_(v)
-        self.client.refresh_shadows()
-        self.server.refresh_shadows()
-        g = {"graph": graph, "x": x, "y": y}
-        self._graphs[key] = g
-        return g
-
-    def _own_buffers_ok(self, x, y) -> bool:
-        return (x.device == self.device and y.device == self.device and x.dtype == _F32 and y.dtype == torch.int64
-                and x.is_contiguous() and y.is_contiguous() and tuple(x.shape[1:]) == (3, 32, 32)
-                and y.shape == (x.shape[0],))
-
-    def register_inputs(self, x, y) -> bool:
-        """Capture a graph on the caller's own (x, y) buffers now (engine.register_graph_inputs)."""
-        return register_graph_inputs(self, x, y)
-
-    def static_inputs(self, B):
-        g = self._graph_for(B)
-        return g["x"], g["y"]
-
-    def step(self, x, y):
-        B = x.shape[0]
-        if self.graph:
-            g = select_graph(self, x, y)
-            if g is not None:
-                g["graph"].replay()
-                self.server.loss_log.note_step(self.global_step)
-                self.global_step += 1
-                return
-            g = self._graph_for(B)
-            if x.data_ptr() != g["x"].data_ptr():
-                g["x"].copy_(x, non_blocking=True)
-            if y.data_ptr() != g["y"].data_ptr():
-                g["y"].copy_(y, non_blocking=True)
-            g["graph"].replay()
-        else:
-            self._eager(x, y)
-        self.server.loss_log.note_step(self.global_step)
-        self.global_step += 1
-
-    # ---- evaluation / prediction (as engine.SplitTrainer's): forward only, no training state touched
+    # ---- evaluation / prediction: no dropout, no tick: both step counters, the parameters, Adam's m / v
+    # and the shadows are as before (the cut of the last evaluation is in eval_cut)
     def _eval_eager(self, x, y, metrics=None):
         # the client forward under its own tag: the saved tensors of a training forward (tag "") survive
         self.eval_cut = self.client.forward(x, tag="eval")   # the last evaluation's cut (a stage buffer)
         return self.server.evaluate(self.eval_cut, y, metrics=metrics)
-
-    def eval_batch(self, x, y, metrics=None):
-        """One held-out batch, asynchronous: (pred, loss_i) (stage buffers; logits in server.eval_logits, the
-        cut in eval_cut); `metrics` updated on the device. No dropout, no tick: both step counters, the
-        parameters, Adam's m / v and the shadows are as before. With graph=True the graph of a batch size
-        holds the accumulator of `metrics`: another metrics object (or none, or alternating with
-        evaluate(), which uses the trainer's own) captures that size again, so keep to one per trainer."""
-        return eval_batch_on(self, x, y, metrics, (3, 32, 32))
-
-    def evaluate(self, batches, metrics=None):
-        """metrics.EvalResult over an iterable of device (x, y) batches, one host sync at the end."""
-        return evaluate_on(self, batches, metrics)
 
     def predict(self, x, return_logits: bool = False):
         """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""

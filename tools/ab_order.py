@@ -16,6 +16,7 @@ from bench import make_pool  # noqa: E402
 from splitcnn import ops  # noqa: E402
 from splitcnn.data import init_models  # noqa: E402
 from splitcnn.engine import SplitTrainer  # noqa: E402
+from splitcnn.graphs import capture  # noqa: E402
 
 ORDERS = os.environ.get("ORDERS", "dg,wg,fw,S,c1,C;fw,dg,wg,S,c1,C;wg,dg,fw,S,c1,C;fw,wg,dg,S,c1,C;"
                                   "dg,fw,wg,S,c1,C;wg,fw,dg,S,c1,C;dg,c1,wg,fw,S,C;dg,wg,fw,c1,S,C").split(";")
@@ -65,14 +66,7 @@ for o in ORDERS:
     fn = make_step(o.split(","), tr)
     xs = torch.zeros_like(X[0])
     ys = torch.zeros_like(Y[0])
-    st = torch.cuda.Stream(dev)
-    st.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(st):
-        fn(xs, ys)
-    torch.cuda.current_stream(dev).wait_stream(st)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn(xs, ys)
+    g, _ = capture(lambda: fn(xs, ys), dev)
     variants[o] = (g, xs, ys, tr)
 res = {k: [] for k in variants}
 for r in range(R):
