@@ -339,6 +339,56 @@ int slk_sgdm_multi_from_slabs(float* const* params, float* const* grads, float* 
                               float weight_decay, int nesterov, const float* loss_values, int loss_n,
                               float loss_scale, float* ring, int capacity, int* counter, void* stream);
 
+/* Global-norm gradient clipping, torch.nn.utils.clip_grad_norm_(params, max_norm) (L2, error_if_nonfinite =
+ * False) in front of slk_sgdm_* / slk_adamw_*, per GROUP of segments (a group = one stage = one torch
+ * optimizer's parameters). The whole norm must be known before the first parameter moves, so the fused
+ * reduce + step is two launches, both without atomics and bit-reproducible:
+ *   1. slk_reduce_sqnorm_multi   grads[s] = sum of slabs[s] and one partial of sum g^2 per block;
+ *   2. slk_sgdm_clip_multi / slk_adamw_clip_multi   every block sums its group's partials, forms
+ *      norm = sqrt(sum), coef = max_norm / (norm + 1e-6) clamped from above at 1, and steps from coef * g.
+ * Layout shared by both passes (host arrays of nseg <= 4 entries): group[s] in [0, ngroup), group[0] = 0,
+ * group[s] = group[s-1] or group[s-1] + 1, the last one ngroup - 1. Segment s owns
+ * slk_reduce_sqnorm_nblk(n[s], nslab[s]) consecutive floats of partials[group[s]], after those of the earlier
+ * segments of its group (so each group's buffer holds the sum of its segments' counts, and nothing behind
+ * that is written). Both passes must be given the same nslab, n and group. */
+
+/* Blocks (= partials) of one segment in pass 1: ceil(n / 1024) for nslab <= 16, ceil(n / 256) for nslab <= 64,
+ * else ceil(n / 64) — the three forms of slk_reduce_slabs; 0 when n or nslab is 0. */
+int slk_reduce_sqnorm_nblk(int n, int nslab);
+
+/* Pass 1. Per segment: grads[s][i] = sum_k slabs[s][k*n+i] in the form of slk_reduce_slabs for nslab[s]
+ * (bitwise the grad slk_sgdm_from_slabs / slk_adamw_from_slabs write), and block blk of the segment writes
+ * partial[blk] = sum over its columns of g*g in this float32 order: the thread that holds the finished sum
+ * of a column squares it (one rounding); every other thread of the 1024 holds 0 — columns past n, and the
+ * threads that only sum slabs: in the 256-column form the columns belong to threads 0..255 (waves 0..3), in
+ * the 64-column form to wave 0, in the 1024-column form thread = column. Inside each of the 16 waves the 64
+ * values are added as a balanced tree over neighbouring lanes (lane pairs, then 4, 8, 16, 32, 64 lanes); then
+ * the 16 wave sums are added in ascending wave order, ((w0 + w1) + w2) + ... . With grads[s] == slabs[s]
+ * (nslab[s] must be 1) the gradient block already holds the sum — after slk_reduce_slabs(accumulate) or an
+ * all-reduce — and is only read. When loss_values != NULL one more block runs slk_loss_log, as in
+ * slk_sgdm_multi_from_slabs. */
+int slk_reduce_sqnorm_multi(float* const* grads, const float* const* slabs, const int* nslab, const int* n,
+                            const int* group, int nseg, float* const* partials, int ngroup,
+                            const float* loss_values, int loss_n, float loss_scale, float* ring, int capacity,
+                            int* counter, void* stream);
+
+/* Pass 2 for torch.optim.SGD. Every block (1024 elements of one segment) first sums the np partials of its
+ * group: thread j (0..1023) adds partials j, j + 1024, j + 2048, ... in ascending order starting from 0; the
+ * 1024 values are then added exactly as in pass 1 (the tree inside each wave, the 16 waves ascending). The
+ * order depends on that group's partials alone, so a group's total is the same bits in every block and in any
+ * launch, whatever shares it. Then, in float32, norm = sqrt(total), coef = *max_norm / (norm + 1e-6f),
+ * coef = coef > 1 ? 1 : coef (a NaN norm keeps a NaN coef, as torch.clamp; an infinite one gives 0 and
+ * inf * 0 = NaN parameters; a zero one gives 1), and slk_sgdm_from_slabs' arithmetic runs on
+ * fl(coef * grads[s][i]) — clipping before weight decay. grads is only read: it keeps the UNCLIPPED reduced
+ * gradient (the clipped one is coef * grads). The group's first block writes norm_out[g][0] = norm,
+ * norm_out[g][1] = coef. max_norm is device memory (so is the rate): a captured HIP graph follows both.
+ * *max_norm = inf gives coef = 1, bitwise slk_sgdm_multi_from_slabs. The caller ticks `step`. */
+int slk_sgdm_clip_multi(float* const* params, const float* const* grads, float* const* bufs, const int* nslab,
+                        const int* n, const int* group, int nseg, const float* const* partials,
+                        float* const* norm_out, int ngroup, const float* max_norm, const float* lr_table,
+                        int lr_len, const int* step, float momentum, float dampening, float weight_decay,
+                        int nesterov, void* stream);
+
 /* MNIST batch from the HBM-resident u8 dataset (replaces DataLoader(batch_size=64, shuffle=True)
  * over torchvision MNIST + ToTensor + Normalize((0.1307,),(0.3081,)), src/client_part.py:61-64,98):
  * x[s] = ((float)images[idx[s]] / 255 - mean) / std as f32 [B,1,28,28], y[s] = labels[idx[s]] (i64).
@@ -490,6 +540,14 @@ int slk_adamw_multi_from_slabs(float* const* params, float* const* grads, float*
                                const float* const* slabs, const int* nslab, const int* n, int nseg,
                                const float* lr_table, int lr_len, const int* step, float beta1, float beta2,
                                float eps, float weight_decay, int decoupled, void* stream);
+/* slk_sgdm_clip_multi with torch.optim.AdamW / Adam(weight_decay) in place of SGD: slk_adamw_from_slabs'
+ * arithmetic on coef * grads[s][i] (clipping before either weight decay), after slk_reduce_sqnorm_multi over the
+ * same segments. Arguments, groups, orders and outputs as slk_sgdm_clip_multi. */
+int slk_adamw_clip_multi(float* const* params, const float* const* grads, float* const* m, float* const* v,
+                         const int* nslab, const int* n, const int* group, int nseg, const float* const* partials,
+                         float* const* norm_out, int ngroup, const float* max_norm, const float* lr_table,
+                         int lr_len, const int* step, float beta1, float beta2, float eps, float weight_decay,
+                         int decoupled, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

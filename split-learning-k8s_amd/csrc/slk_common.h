@@ -76,6 +76,63 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Sum of one value per thread over a 1024-thread block, the same bits in every thread: wave_sum inside each
+// of the 16 waves, lane 0 of wave w leaves its wave's sum in red[w], then every thread adds red[0..15] in
+// ascending wave order. Block-wide (one barrier); red holds 16 floats of LDS scratch.
+__device__ __forceinline__ float slk_block_sum_1024(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = red[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += red[w];
+    return t;
+}
+
+// Global-norm gradient clipping (slk_reduce_sqnorm_multi -> slk_sgdm_clip_multi / slk_adamw_clip_multi).
+// The coefficient of one group from the block partials of its squared norm; every thread of a 1024-thread
+// block calls it. Thread j adds partials j, j + 1024, j + 2048, ... in ascending order (starting from 0),
+// then slk_block_sum_1024: a fixed function of (partials, npart) alone, so every block of every launch holds
+// the same total, whatever else shares the launch. norm = sqrtf(total); coef = max_norm / (norm + 1e-6f)
+// clamped from above at 1 by a compare, so a NaN norm gives a NaN coefficient (torch.clamp(max=1.0)), an
+// infinite one 0 and a zero one 1: torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False) in float32.
+__device__ __forceinline__ float slk_clip_coef(const float* __restrict__ partials, int npart,
+                                               const float* __restrict__ max_norm, float* red, float& norm) {
+    float s = 0.f;
+    for (int j = threadIdx.x; j < npart; j += 1024) s += partials[j];
+    norm = sqrtf(slk_block_sum_1024(s, red));
+    const float coef = *max_norm / (norm + 1e-6f);
+    return coef > 1.f ? 1.f : coef;
+}
+
+// Host side of the two clip passes: where each segment's block partials live. Segments of one group (one
+// stage) are consecutive, group ids start at 0 and rise by at most 1; segment s writes / its group reads
+// partials[group[s]][off[s] + blk], blk < nblk[s] = slk_reduce_sqnorm_nblk(n[s], nslab[s]); npart[s] is the
+// group's total and first[s] marks the group's first non-empty segment (its first block reports norm, coef).
+constexpr int SLK_CLIP_MAXSEG = 4;
+struct SlkClipLayout {
+    int nblk[SLK_CLIP_MAXSEG], off[SLK_CLIP_MAXSEG], npart[SLK_CLIP_MAXSEG], first[SLK_CLIP_MAXSEG];
+};
+static inline bool slk_clip_layout(const int* nslab, const int* n, const int* group, int nseg, int ngroup,
+                                   SlkClipLayout& L) {
+    if (nseg < 1 || nseg > SLK_CLIP_MAXSEG || ngroup < 1 || ngroup > nseg || !nslab || !n || !group) return false;
+    int gtot[SLK_CLIP_MAXSEG] = {0, 0, 0, 0};
+    bool seen[SLK_CLIP_MAXSEG] = {false, false, false, false};
+    for (int s = 0; s < nseg; ++s) {
+        const int g = group[s];
+        if (g >= ngroup || (s == 0 ? g != 0 : (g != group[s - 1] && g != group[s - 1] + 1))) return false;
+        if (n[s] < 0 || nslab[s] < 1) return false;
+        L.nblk[s] = slk_reduce_sqnorm_nblk(n[s], nslab[s]);
+        L.off[s] = gtot[g];
+        gtot[g] += L.nblk[s];
+        L.first[s] = L.nblk[s] > 0 && !seen[g];
+        seen[g] = seen[g] || L.nblk[s] > 0;
+    }
+    if (group[nseg - 1] != ngroup - 1) return false;
+    for (int s = 0; s < nseg; ++s) L.npart[s] = gtot[group[s]];
+    return true;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

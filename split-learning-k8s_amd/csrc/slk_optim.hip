@@ -241,26 +241,31 @@ struct SgdMulti {
     LossLogArgs loss;
 };
 
+// slk_loss_log as one block of a 1024-thread launch: threads 0..255 sum exactly as block_sum_256 (the other
+// waves add nothing).
+__device__ __forceinline__ void loss_log_block(const LossLogArgs& l) {
+    __shared__ float red[4];
+    float v = 0.f;
+    if (threadIdx.x < 256)
+        for (int i = threadIdx.x; i < l.n; i += 256) v += l.v[i];
+    v = wave_sum(v);
+    if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float tot = ((red[0] + red[1]) + red[2]) + red[3];
+        const int c = *l.counter;
+        l.ring[c % l.capacity] = tot * l.scale;
+        *l.counter = c + 1;
+    }
+}
+
 template <class Hyper>
 __global__ __launch_bounds__(1024) void sgd_multi_kernel(const SgdMulti<Hyper> a) {
     int blk = blockIdx.x;
     if (a.loss.v) {
-        // block 0 logs the loss (dispatched first: its serial sum overlaps the segments' blocks);
-        // threads 0..255 sum exactly as block_sum_256 (the other waves add nothing)
+        // block 0 logs the loss (dispatched first: its serial sum overlaps the segments' blocks)
         if (blk == 0) {
-            __shared__ float red[4];
-            float v = 0.f;
-            if (threadIdx.x < 256)
-                for (int i = threadIdx.x; i < a.loss.n; i += 256) v += a.loss.v[i];
-            v = wave_sum(v);
-            if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const float tot = ((red[0] + red[1]) + red[2]) + red[3];
-                const int c = *a.loss.counter;
-                a.loss.ring[c % a.loss.capacity] = tot * a.loss.scale;
-                *a.loss.counter = c + 1;
-            }
+            loss_log_block(a.loss);
             return;
         }
         --blk;
@@ -274,6 +279,108 @@ __global__ __launch_bounds__(1024) void sgd_multi_kernel(const SgdMulti<Hyper> a
                 return;
             }
             blk -= a.seg[s].nblk;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------- global-norm gradient clipping
+// torch.nn.utils.clip_grad_norm_ needs a stage's whole norm before its first parameter moves, so the fused
+// reduce + step becomes two launches, neither with atomics: reduce_sqnorm_multi_kernel (the slab reduction
+// as above, plus one partial of the squared norm per block) and sgdm_clip_multi_kernel (every block sums its
+// group's partials in one fixed order, forms the coefficient and steps from coef * grad).
+//
+// Pass 1, one block: slab_reduce on its columns (so `grad` gets the bits slk_sgdm_from_slabs writes), the
+// applying thread of each column keeping q = t * t; every other thread — columns past n, and in the 256- and
+// 64-column forms the waves that only sum slabs (waves 4..15 / 1..15) — keeps q = 0. Then
+// slk_block_sum_1024(q): wave_sum inside each wave, the 16 wave sums added in ascending wave order; thread 0
+// writes the block's partial. grad == NULL: the gradient block already holds the sum (nslab 1, in place).
+struct SqApply {
+    float* __restrict__ grad;
+    float* q;
+    __device__ __forceinline__ void operator()(int i, float t) const {
+        if (grad) grad[i] = t;
+        *q = t * t;
+    }
+};
+struct RsqSeg {
+    float* grad;
+    const float* slabs;
+    float* partials;  // this segment's slice of its group's partials
+    int nslab, n, nblk;
+};
+struct RsqMulti {
+    RsqSeg seg[SGD_MAXSEG];
+    int nseg;
+    LossLogArgs loss;
+};
+
+__global__ __launch_bounds__(1024) void reduce_sqnorm_multi_kernel(const RsqMulti a) {
+    __shared__ float red[16];
+    int blk = blockIdx.x;
+    if (a.loss.v) {
+        if (blk == 0) {
+            loss_log_block(a.loss);
+            return;
+        }
+        --blk;
+    }
+#pragma unroll
+    for (int s = 0; s < SGD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const RsqSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float q = 0.f;
+                slab_reduce(nullptr, g.slabs, g.nslab, g.n, blk, SqApply{g.grad, &q});
+                slk_keep(q);  // the square is rounded on its own (never fused into the first add of wave_sum)
+                const float tot = slk_block_sum_1024(q, red);
+                if (threadIdx.x == 0) g.partials[blk] = tot;
+                return;
+            }
+            blk -= g.nblk;
+        }
+    }
+}
+
+// Pass 2: thread = element, 1024 per block. SgdmApply's arithmetic on coef * grad[i], one f32 multiply
+// rounded on its own (clipping comes before weight decay); grad keeps the unclipped gradient.
+struct ClipSeg {
+    float* param;
+    const float* grad;
+    float* buf;
+    const float* partials;  // the group's partials
+    float* out;             // the group's [norm, coef]
+    int n, nblk, npart, first;
+};
+struct SgdmClipMulti {
+    ClipSeg seg[SGD_MAXSEG];
+    int nseg;
+    const float* max_norm;
+    SgdmHyper h;
+};
+
+__global__ __launch_bounds__(1024) void sgdm_clip_multi_kernel(const SgdmClipMulti a) {
+    __shared__ float red[16];
+    int blk = blockIdx.x;
+#pragma unroll
+    for (int s = 0; s < SGD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const ClipSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float norm;
+                const float coef = slk_clip_coef(g.partials, g.npart, a.max_norm, red, norm);
+                if (g.first && blk == 0 && threadIdx.x == 0) {
+                    g.out[0] = norm;
+                    g.out[1] = coef;
+                }
+                const int i = blk * 1024 + threadIdx.x;
+                if (i < g.n) {
+                    float cg = coef * g.grad[i];
+                    slk_keep(cg);
+                    SgdmApply{g.param, nullptr, g.buf, a.h}(i, cg);
+                }
+                return;
+            }
+            blk -= g.nblk;
         }
     }
 }
@@ -360,6 +467,62 @@ extern "C" int slk_sgdm_multi_from_slabs(float* const* params, float* const* gra
     if (loss_values) ++nblk;
     if (nblk == 0) return 0;
     sgd_multi_kernel<SgdmMultiHyper><<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+extern "C" int slk_reduce_sqnorm_nblk(int n, int nslab) { return n > 0 && nslab > 0 ? rs_blocks(n, nslab) : 0; }
+
+extern "C" int slk_reduce_sqnorm_multi(float* const* grads, const float* const* slabs, const int* nslab,
+                                       const int* n, const int* group, int nseg, float* const* partials,
+                                       int ngroup, const float* loss_values, int loss_n, float loss_scale,
+                                       float* ring, int capacity, int* counter, void* stream) {
+    static_assert(SGD_MAXSEG == SLK_CLIP_MAXSEG, "clip layout");
+    SLK_CHECK_ARG(grads && slabs && partials);
+    SLK_CHECK_ARG(!loss_values || (loss_n > 0 && capacity > 0 && ring && counter));
+    SlkClipLayout L;
+    SLK_CHECK_ARG(slk_clip_layout(nslab, n, group, nseg, ngroup, L));
+    RsqMulti a{};
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        SLK_CHECK_ARG(grads[s] && slabs[s] && partials[group[s]]);
+        // in place: the gradient block is the one slab (after a reduce / all-reduce); nothing is written to it
+        const bool in_place = grads[s] == slabs[s];
+        SLK_CHECK_ARG(!in_place || nslab[s] == 1);
+        a.seg[s] = RsqSeg{in_place ? nullptr : grads[s], slabs[s], partials[group[s]] + L.off[s], nslab[s], n[s],
+                          L.nblk[s]};
+        nblk += L.nblk[s];
+    }
+    a.nseg = nseg;
+    a.loss = LossLogArgs{loss_values, loss_n, loss_scale, ring, capacity, counter};
+    if (loss_values) ++nblk;
+    if (nblk == 0) return 0;
+    reduce_sqnorm_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+extern "C" int slk_sgdm_clip_multi(float* const* params, const float* const* grads, float* const* bufs,
+                                   const int* nslab, const int* n, const int* group, int nseg,
+                                   const float* const* partials, float* const* norm_out, int ngroup,
+                                   const float* max_norm, const float* lr_table, int lr_len, const int* step,
+                                   float momentum, float dampening, float weight_decay, int nesterov,
+                                   void* stream) {
+    SLK_CHECK_ARG(params && grads && partials && norm_out && max_norm && lr_table && lr_len >= 1 && step);
+    SLK_CHECK_ARG(bufs || momentum == 0.f);
+    SlkClipLayout L;
+    SLK_CHECK_ARG(slk_clip_layout(nslab, n, group, nseg, ngroup, L));
+    SgdmClipMulti a{};
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        SLK_CHECK_ARG(params[s] && grads[s] && partials[group[s]] && norm_out[group[s]] && (momentum == 0.f || bufs[s]));
+        a.seg[s] = ClipSeg{params[s], grads[s], bufs ? bufs[s] : nullptr, partials[group[s]], norm_out[group[s]], n[s],
+                           (n[s] + 1023) / 1024, L.npart[s], L.first[s]};
+        nblk += a.seg[s].nblk;
+    }
+    a.nseg = nseg;
+    a.max_norm = max_norm;
+    a.h = SgdmHyper{lr_table, lr_len, step, momentum, dampening, weight_decay, nesterov ? 1 : 0};
+    if (nblk == 0) return 0;
+    sgdm_clip_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
     return slk_launch_status();
 }
 

@@ -502,6 +502,52 @@ __global__ __launch_bounds__(1024) void adam_multi_kernel(const AdamMulti a) {
     }
 }
 
+// Global-norm clipping, pass 2 (pass 1 is slk_reduce_sqnorm_multi, slk_optim.hip): thread = element, 1024 per
+// block; every block sums its group's partials (slk_clip_coef: one fixed order), then adam_apply<true> on
+// coef * grad[i], one f32 multiply rounded on its own, before either weight decay. grad keeps the unclipped
+// gradient; the first block of a group writes [norm, coef].
+struct AdamClipSeg {
+    float* param;
+    const float* grad;
+    float* m;
+    float* v;
+    const float* partials;  // the group's partials
+    float* out;             // the group's [norm, coef]
+    int n, nblk, npart, first;
+};
+struct AdamClipMulti {
+    AdamClipSeg seg[AD_MAXSEG];
+    int nseg;
+    const float* max_norm;
+    AdamHyper h;
+};
+__global__ __launch_bounds__(1024) void adamw_clip_multi_kernel(const AdamClipMulti a) {
+    __shared__ float red[16];
+    int blk = blockIdx.x;
+#pragma unroll
+    for (int s = 0; s < AD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const AdamClipSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float norm;
+                const float coef = slk_clip_coef(g.partials, g.npart, a.max_norm, red, norm);
+                if (g.first && blk == 0 && threadIdx.x == 0) {
+                    g.out[0] = norm;
+                    g.out[1] = coef;
+                }
+                const int i = blk * 1024 + threadIdx.x;
+                if (i < g.n) {
+                    float cg = coef * g.grad[i];
+                    slk_keep(cg);
+                    adam_apply<true>(i, cg, g.param, nullptr, g.m, g.v, a.h);
+                }
+                return;
+            }
+            blk -= g.nblk;
+        }
+    }
+}
+
 // bf16 shadows of the client conv weights (torch layout [co][ci][3][3] f32 masters) in the layouts
 // slk_wide.hip's implicit GEMMs stream: forward [co/128][tap][ci/8][co%128][8]; dgrad (roles
 // swapped, taps flipped) [ci/MT][8-tap][co/8][ci%MT][8] with MT = 64 (conv2) / 128 (conv3).
@@ -650,6 +696,31 @@ extern "C" int slk_adamw_multi_from_slabs(float* const* params, float* const* gr
                                    AdamHyper{0.f, lr_table, lr_len, weight_decay, decoupled ? 1 : 0, beta1, beta2, eps,
                                              step},
                                    stream);
+}
+extern "C" int slk_adamw_clip_multi(float* const* params, const float* const* grads, float* const* m,
+                                    float* const* v, const int* nslab, const int* n, const int* group, int nseg,
+                                    const float* const* partials, float* const* norm_out, int ngroup,
+                                    const float* max_norm, const float* lr_table, int lr_len, const int* step,
+                                    float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                                    void* stream) {
+    static_assert(AD_MAXSEG == SLK_CLIP_MAXSEG, "clip layout");
+    SLK_CHECK_ARG(params && grads && m && v && partials && norm_out && max_norm && lr_table && lr_len >= 1 && step);
+    SlkClipLayout L;
+    SLK_CHECK_ARG(slk_clip_layout(nslab, n, group, nseg, ngroup, L));
+    AdamClipMulti a{};
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        SLK_CHECK_ARG(params[s] && grads[s] && m[s] && v[s] && partials[group[s]] && norm_out[group[s]]);
+        a.seg[s] = AdamClipSeg{params[s], grads[s], m[s], v[s], partials[group[s]], norm_out[group[s]], n[s],
+                               (n[s] + 1023) / 1024, L.npart[s], L.first[s]};
+        nblk += a.seg[s].nblk;
+    }
+    a.nseg = nseg;
+    a.max_norm = max_norm;
+    a.h = AdamHyper{0.f, lr_table, lr_len, weight_decay, decoupled ? 1 : 0, beta1, beta2, eps, step};
+    if (nblk == 0) return 0;
+    hipLaunchKernelGGL(adamw_clip_multi_kernel, dim3(nblk), dim3(1024), 0, slk_stream(stream), a);
+    return slk_launch_status();
 }
 extern "C" int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f,
                                 uint16_t* w2d, uint16_t* w3f, uint16_t* w3d, void* stream) {

@@ -91,6 +91,11 @@ _SIGS = {
     "slk_sgdm_from_slabs": [_P, _P, _P, _P, _I, _I, _P, _I, _P, _F, _F, _F, _I, _P],
     "slk_sgdm_multi_from_slabs": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _I, _P, _I, _F, _P, _I, _P,
                                   _P],
+    # global-norm gradient clipping (optim.ClipNorm): reduce + square-norm partials, then the clipped step
+    "slk_reduce_sqnorm_nblk": [_I, _I],
+    "slk_reduce_sqnorm_multi": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _F, _P, _I, _P, _P],
+    "slk_sgdm_clip_multi": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _I, _P],
+    "slk_adamw_clip_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _F, _I, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)
     "slk_wide_conv1_fwd": [_P, _P, _P, _P, _P, _I, _P],

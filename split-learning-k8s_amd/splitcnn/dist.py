@@ -100,12 +100,13 @@ def _loss_sum(values, scale, out):
 
 def _default_optimizer_only(who: str, *stages) -> None:
     """These classes step with the stages' by-value lr (ops.sgd_multi_from_slabs / slk_adam_from_slabs): refuse
-    a stage built with an optimizer config or a schedule (splitcnn.optim) instead of ignoring it."""
+    a stage built with an optimizer config, a schedule or gradient clipping (splitcnn.optim) instead of
+    ignoring it."""
     for st in stages:
-        if getattr(st, "optim", None) is not None or getattr(st, "schedule", None) is not None:
+        if any(getattr(st, a, None) is not None for a in ("optim", "schedule", "clip")):
             raise ValueError(f"dist.{who}: {type(st).__name__} carries an optimizer config / learning-rate schedule "
-                             "(splitcnn.optim); the multi-GPU classes take only the default optimizer — build "
-                             "the stage without optim= and schedule=")
+                             "/ gradient clipping (splitcnn.optim); the multi-GPU classes take only the default "
+                             "optimizer — build the stage without optim=, schedule= and clip=")
 
 
 def _pair_amax(client, server):

@@ -30,7 +30,7 @@ import torch.nn as nn
 from . import ops
 from .graphs import GraphedTrainer
 from .model_def import ModelPartA, ModelPartB
-from .optim import SGD, LRSchedule
+from .optim import SGD, ClipNorm, LRSchedule, check_clip
 
 LR = 0.01  # optim.SGD(lr=0.01) on both sides (client_part.py:17, server_part.py:15)
 
@@ -92,14 +92,19 @@ class _SgdRecipe:
     flat block like params / grads), the device counter `step_ctr` of completed optimizer steps and the
     schedule's device table, all read by the kernels, so graph replays follow them. The stage advances
     step_ctr after its optimizer launches unless a trainer that shares one counter between both stages does
-    (auto_tick False)."""
+    (auto_tick False). With an optim.ClipNorm (`clip`, which like a schedule selects slk_sgdm_*) every step is
+    two launches, slk_reduce_sqnorm_multi then slk_sgdm_clip_multi: the stage's gradient is clipped by its own
+    global L2 norm before weight decay; `grads` keeps the unclipped gradient and `clip_out` the last step's
+    device [norm, coef]."""
 
-    def _init_optim(self, lr, optim, schedule):
+    def _init_optim(self, lr, optim, schedule, clip=None):
         if optim is not None and not isinstance(optim, SGD):
             raise TypeError(f"optim: expected splitcnn.optim.SGD or None, got {type(optim).__name__}")
-        if optim is None and schedule is not None:
+        check_clip(clip)
+        if optim is None and (schedule is not None or clip is not None):
             optim = SGD(lr)
         self.optim, self.schedule = optim, None
+        self.clip = self.clip_out = None
         self.buf = self.step_ctr = None
         self.auto_tick = True
         if optim is None:
@@ -108,14 +113,32 @@ class _SgdRecipe:
         self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
         self.buf = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if clip is not None:
+            self.clip = clip.to(self.device)
+            self.clip_out = torch.zeros(2, dtype=torch.float32, device=self.device)   # [norm, coef] of the last step
+
+    def _clip_group(self, segs):
+        """This stage's segments as one group of the clip launches: its own partials and [norm, coef]."""
+        need = self.clip_npart = ops.clip_partials_needed(segs)   # partials of this stage's last clipped step
+        return (self._buf.get("clip_partials", (need,), torch.float32, self.device), self.clip_out, segs)
 
     def _sgdm(self, segments, loss=None, multi=False):
         """slk_sgdm_* on (lo, hi, slabs) slices of this stage (slabs [nslab, hi - lo]) and ready
-        (param, grad, buf, slabs) tuples: separate launches, or ONE with the loss log (multi)."""
+        (param, grad, buf, slabs) tuples: separate launches, or ONE with the loss log (multi). With `clip`
+        always the two clip launches (the loss log rides in the first); another clipped stage's
+        optim_segment joins them as a group of its own."""
+        if any(len(g) == (4 if self.clip is not None else 5) and g[0] is not self.params for g in segments):
+            raise ValueError("a segment of another stage must share this stage's clip= (both clipped by one "
+                             "optim.ClipNorm, or neither)")
         segs = [(self.params[g[0]:g[1]], self.grads[g[0]:g[1]], self.buf[g[0]:g[1]], g[2]) if len(g) == 3 else g
                 for g in segments]
         kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
-        if multi:
+        if self.clip is not None:
+            groups = [self._clip_group([g for g in segs if len(g) == 4])]
+            groups += [g[4]._clip_group([g[:4]]) for g in segs if len(g) == 5]
+            ops.reduce_sqnorm_multi(groups, loss=loss)
+            ops.sgdm_clip_multi(groups, self.clip.value, **kw)
+        elif multi:
             ops.sgdm_multi_from_slabs(segs, loss=loss, **kw)
         else:
             for g in segs:
@@ -126,8 +149,10 @@ class _SgdRecipe:
             ops.tick(self.step_ctr)
 
     def optim_segment(self, slabs):
-        """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch."""
-        return (self.params, self.grads, self.buf, slabs)
+        """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch; with
+        `clip` (shared with that stage) a group of its own in that stage's two clip launches."""
+        seg = (self.params, self.grads, self.buf, slabs)
+        return seg if self.clip is None else seg + (self,)
 
 
 class _Buffers:
@@ -205,13 +230,14 @@ class ClientStage(_SgdRecipe):
     topologies)."""
 
     def __init__(self, model: Optional[ModelPartA] = None, lr: float = LR, device="cuda",
-                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
+                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
+                 clip: Optional[ClipNorm] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else ModelPartA()).to(self.device)
         self.lr = lr
         self.params, self.grads = _flatten_params(
             [self.model.conv1.weight, self.model.conv1.bias], self.device)
-        self._init_optim(lr, optim, schedule)
+        self._init_optim(lr, optim, schedule, clip)
         self._buf = _Buffers()
         self._x = None
         self._act = None
@@ -331,7 +357,8 @@ class ServerStage(_SgdRecipe):
 
     def __init__(self, model: Optional[ModelPartB] = None, lr: float = LR, device="cuda",
                  loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT,
-                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
+                 optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
+                 clip: Optional[ClipNorm] = None):
         self.device = torch.device(device)
         self.conv = conv
         self.impl_fwd, self.impl_dgrad, self.impl_wgrad = CONV_PRESETS[conv]
@@ -341,7 +368,7 @@ class ServerStage(_SgdRecipe):
         m = self.model
         self.params, self.grads = _flatten_params(
             [m.conv2.weight, m.conv2.bias, m.fc1.weight, m.fc1.bias], self.device)
-        self._init_optim(lr, optim, schedule)
+        self._init_optim(lr, optim, schedule, clip)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -611,18 +638,22 @@ class SplitTrainer(GraphedTrainer):
     share the config, the schedule and ONE device step counter, ticked once at the end of the step, so the
     captured graph follows the schedule. Without them `lr` is a by-value kernel argument: changing a
     stage's `lr` attribute after the first step does not reach a captured graph (use a schedule and
-    LRSchedule.set_lr)."""
+    LRSchedule.set_lr). `clip` (optim.ClipNorm, shared by both stages; selects the configured kernels like a
+    schedule) clips each stage's gradient by that stage's own global norm before its update; grad_norms()
+    reads the last step's norms."""
 
     input_shape = (1, 28, 28)
 
     def __init__(self, client: Optional[ModelPartA] = None, server: Optional[ModelPartB] = None,
                  lr: float = LR, device="cuda", graph: bool = True, loss_log: Optional[LossLog] = None,
                  conv: str = CONV_DEFAULT, act16: bool = True, fuse_client_backward: bool = True,
-                 graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None):
+                 graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
+                 clip: Optional[ClipNorm] = None):
+        check_clip(clip)
         super().__init__(device, graph, graph_inputs)
-        self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule)
+        self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule, clip=clip)
         self.server = ServerStage(server, lr, self.device, loss_log, conv=conv, optim=self.client.optim,
-                                  schedule=self.client.schedule)
+                                  schedule=self.client.schedule, clip=self.client.clip)
         if self.server.optim is not None:
             self.client.step_ctr = self.server.step_ctr
             self.client.auto_tick = self.server.auto_tick = False   # _eager ticks the shared counter
@@ -647,7 +678,8 @@ class SplitTrainer(GraphedTrainer):
             if s.optim is None and c.optim is None:
                 one, seg = c.lr == s.lr, (c.params, c.grads, slabs)
             else:   # one recipe, one schedule and one counter (a config given to this trainer)
-                one = c.optim is s.optim and c.schedule is s.schedule and c.step_ctr is s.step_ctr
+                one = (c.optim is s.optim and c.schedule is s.schedule and c.step_ctr is s.step_ctr
+                       and c.clip is s.clip)
                 seg = c.optim_segment(slabs) if one else None
             s.step_request(act, y, act_amax=c._act_amax, act16=a16, client_fuse=(x, c._relu_bits, slabs),
                            extra_segments=[seg] if one else ())

@@ -4,7 +4,8 @@
 engine.SplitTrainer and wide.WideTrainer have in common around their step: the graph caches and the
 policy of which buffers get a graph of their own, the evaluation pass and its graphs, and the optimizer
 state save / load. A trainer supplies its launch sequences (`_eager`, `_eval_eager`) and names its
-state (`_state`, `_optim_state`). Nothing here runs on the device."""
+state (`_state`, `_optim_state`). Nothing here launches a kernel of its own (grad_norms reads the stages' two
+device [norm, coef] pairs back)."""
 from __future__ import annotations
 
 from typing import Dict
@@ -157,6 +158,17 @@ class GraphedTrainer:
                 replay_on(self._graph_for(x.shape[0]), x, y)
         self.server.loss_log.note_step(self.global_step)
         self.global_step += 1
+
+    # ---- gradient clipping (optim.ClipNorm)
+    def grad_norms(self) -> Dict[str, tuple]:
+        """{"client": (norm, coef), "server": (norm, coef)} of the last step: each stage's global L2 gradient
+        norm before clipping and the coefficient its optimizer applied (1.0: not clipped). One host sync.
+        Needs `clip=` (ClipNorm(float("inf")) measures without clipping)."""
+        outs = [getattr(st, "clip_out", None) for st in (self.client, self.server)]
+        if any(o is None for o in outs):
+            raise RuntimeError("grad_norms: the trainer was built without clip= (optim.ClipNorm)")
+        (cn, cc), (sn, sc) = torch.stack(outs).tolist()
+        return {"client": (cn, cc), "server": (sn, sc)}
 
     # ---- optimizer state
     def optimizer_state(self) -> Dict[str, torch.Tensor]:

@@ -642,6 +642,86 @@ def adamw_multi_from_slabs(segments, lr_table, step, beta1, beta2, eps, weight_d
               float(beta2), float(eps), float(weight_decay), int(bool(decoupled)), _stream(segments[0][0]))
 
 
+# ---- global-norm gradient clipping: reduce + square-norm partials, then the clipped step (two launches)
+def reduce_sqnorm_nblk(n, nslab):
+    """Blocks (= square-norm partials) that reduce_sqnorm_multi spends on one [nslab, n] slab set."""
+    return _lib.query("slk_reduce_sqnorm_nblk", int(n), int(nslab))
+
+
+def clip_partials_needed(segments):
+    """Floats of partials one group of `segments` (each ending in its [nslab, n] slabs) needs."""
+    return sum(reduce_sqnorm_nblk(seg[-1].shape[1], seg[-1].shape[0]) for seg in segments)
+
+
+def _clip_args(groups, who, width):
+    """The host arrays both clip passes share. groups = [(partials, norm_out, segments)], one per stage;
+    a segment is `width` tensors (param, grad, state ..., slabs). grad None: the [1, n] slabs ARE the
+    gradient block (reduced earlier), read in place. Returns (columns of the tensors' pointers, nslab, n,
+    group ids, partials pointers, norm_out pointers, a tensor to take the stream from)."""
+    cols = [[] for _ in range(width)]
+    nslab, ns, gid, parts, outs = [], [], [], [], []
+    for g, (partials, norm_out, segments) in enumerate(groups):
+        if not segments:
+            raise ValueError(f"{who}: group {g} has no segment")
+        for seg in segments:
+            if len(seg) != width:
+                raise ValueError(f"{who}: a segment is {width} tensors")
+            sl = seg[-1]
+            nsl, n = sl.shape
+            grad = seg[1]
+            if grad is None:
+                if nsl != 1:
+                    raise ValueError(f"{who}: a segment without grad steps in place from ONE slab")
+                grad = sl.view(-1)
+            names = ("param", "grad") + ("state",) * (width - 3)
+            for c, t, name in zip(cols, (seg[0], grad) + tuple(seg[2:-1]), names):
+                c.append(_dev(t, name, (n,)) if t is not None else None)
+            cols[-1].append(_dev(sl, "slabs"))
+            nslab.append(int(nsl))
+            ns.append(int(n))
+            gid.append(g)
+        if _dev(partials, "partials") and partials.numel() < clip_partials_needed(segments):
+            raise ValueError(f"{who}: group {g} needs {clip_partials_needed(segments)} partials, got {partials.numel()}")
+        parts.append(partials.data_ptr())
+        outs.append(_dev(norm_out, "norm_out", (2,)))
+    if not 1 <= len(gid) <= 4:
+        raise ValueError(f"{who}: 1 to 4 segments")
+    return cols, nslab, ns, gid, parts, outs, groups[0][2][0][0]
+
+
+def reduce_sqnorm_multi(groups, loss=None):
+    """Pass 1 of a clipped step (slk_reduce_sqnorm_multi), ONE launch: every segment's grad = the fixed-order
+    sum of its slabs (bitwise what sgdm_from_slabs / adamw_from_slabs write) and one partial of sum g^2 per
+    block into its group's `partials`; plus loss_log(*loss). groups = [(partials, norm_out, segments)] as
+    for sgdm_clip_multi / adamw_clip_multi (norm_out is not written here)."""
+    width = len(groups[0][2][0])
+    cols, nslab, ns, gid, parts, _, like = _clip_args(groups, "reduce_sqnorm_multi", width)
+    _lib.call("slk_reduce_sqnorm_multi", *_host_arrays([cols[1], cols[-1], nslab, ns, gid], n_int=3), len(gid),
+              *_host_arrays([parts], n_int=0), len(groups), *_loss_args(loss), _stream(like))
+
+
+def sgdm_clip_multi(groups, max_norm, lr_table, step, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+    """Pass 2 for torch.optim.SGD (slk_sgdm_clip_multi), ONE launch after reduce_sqnorm_multi(groups): per
+    group (one stage) norm = sqrt(sum of its partials), coef = min(1, max_norm / (norm + 1e-6)) -> norm_out,
+    then sgdm_from_slabs' update from coef * grad. groups = [(partials, norm_out, [(param, grad, buf, slabs),
+    ...])]; grad stays the unclipped gradient; max_norm is a device f32[1] (optim.ClipNorm.value)."""
+    cols, nslab, ns, gid, parts, outs, like = _clip_args(groups, "sgdm_clip_multi", 4)
+    _lib.call("slk_sgdm_clip_multi", *_host_arrays(cols[:3] + [nslab, ns, gid], n_int=3), len(gid),
+              *_host_arrays([parts, outs], n_int=0), len(groups), _dev(max_norm, "max_norm", (1,)),
+              *_lr_args(lr_table, step), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+              _stream(like))
+
+
+def adamw_clip_multi(groups, max_norm, lr_table, step, beta1, beta2, eps, weight_decay=0.0, decoupled=True):
+    """Pass 2 for torch.optim.AdamW / Adam (slk_adamw_clip_multi): as sgdm_clip_multi with segments
+    (param, grad, m, v, slabs) and adamw_from_slabs' update from coef * grad."""
+    cols, nslab, ns, gid, parts, outs, like = _clip_args(groups, "adamw_clip_multi", 5)
+    _lib.call("slk_adamw_clip_multi", *_host_arrays(cols[:4] + [nslab, ns, gid], n_int=3), len(gid),
+              *_host_arrays([parts, outs], n_int=0), len(groups), _dev(max_norm, "max_norm", (1,)),
+              *_lr_args(lr_table, step), float(beta1), float(beta2), float(eps), float(weight_decay),
+              int(bool(decoupled)), _stream(like))
+
+
 def tick(counter):
     """++counter on the device (a stage's optimizer step counter; advances inside a captured graph)."""
     _lib.call("slk_tick", _dev(counter, "counter", (1,), torch.int32), _stream(counter))

@@ -10,10 +10,19 @@ without being recaptured and without a host sync.
     from splitcnn import optim
     sched = optim.LRSchedule.warmup_cosine(0.05, warmup=100, total=2000)
     tr = SplitTrainer(client, server, optim=optim.SGD(0.05, momentum=0.9, nesterov=True, weight_decay=5e-4),
-                      schedule=sched)
+                      schedule=sched, clip=optim.ClipNorm(1.0))
 
-Limits: one rate and one recipe per stage (no per-parameter groups), no gradient clipping, and the
-multi-GPU classes of dist.py take only stages built without a config.
+`ClipNorm` is torch.nn.utils.clip_grad_norm_ (L2 norm, error_if_nonfinite=False) in front of every optimizer
+step, per stage: each stage clips by the norm of its own gradient (the reference's two parties have two
+optimizers and the client never sees the server's gradient), also in the fused one-GPU trainers. With it the
+fused reduce + step launch becomes two (slk_reduce_sqnorm_multi, then slk_sgdm_clip_multi /
+slk_adamw_clip_multi): the whole norm must exist before the first parameter moves. Norm, coefficient and
+threshold stay on the device; trainer.grad_norms() reads the last step's. One deviation from torch:
+`stage.grads` keeps the UNCLIPPED reduced gradient (torch scales p.grad in place); the gradient the optimizer
+consumed is coef * grads. The clip tensors are no optimizer state (optimizer_state() keeps its keys).
+
+Limits: one rate and one recipe per stage (no per-parameter groups), L2 norm only (no clip_grad_value_), and
+the multi-GPU classes of dist.py take only stages built without a config.
 """
 from __future__ import annotations
 
@@ -75,6 +84,47 @@ class Adam:
     def __repr__(self):
         return (f"Adam(lr={self.lr}, betas={self.betas}, eps={self.eps}, weight_decay={self.weight_decay}, "
                 f"decoupled={self.decoupled})")
+
+
+class ClipNorm:
+    """torch.nn.utils.clip_grad_norm_(stage parameters, max_norm) (L2) before every optimizer step of a
+    stage, as a config: the threshold is a device f32[1] the clipped-step kernels read, so a captured HIP
+    graph follows `set_max_norm` without being recaptured. max_norm = inf clips nothing (coef = 1: bitwise
+    the unclipped configured step) but still measures the norms (trainer.grad_norms())."""
+
+    def __init__(self, max_norm: float, device="cuda"):
+        self.max_norm = self._checked(max_norm)
+        self.value = torch.full((1,), self.max_norm, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _checked(max_norm) -> float:
+        if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float, np.integer, np.floating)):
+            raise ValueError(f"Invalid max_norm: {max_norm!r}")
+        if not max_norm > 0.0:   # NaN fails this too
+            raise ValueError(f"Invalid max_norm: {max_norm} (need max_norm > 0; inf clips nothing)")
+        return float(max_norm)
+
+    def to(self, device) -> "ClipNorm":
+        """Move the threshold (a no-op on its own device); captured graphs hold its address, so move a
+        ClipNorm before the first step only."""
+        if self.value.device != torch.device(device):
+            self.value = self.value.to(device)
+        return self
+
+    def set_max_norm(self, max_norm: float) -> None:
+        """Overwrite the threshold in place: an asynchronous device write on the current stream, so the next
+        step — eager or a replay of an already captured graph — clips at `max_norm`."""
+        self.max_norm = self._checked(max_norm)
+        self.value.fill_(self.max_norm)
+
+    def __repr__(self):
+        return f"ClipNorm(max_norm={self.max_norm})"
+
+
+def check_clip(clip):
+    if clip is not None and not isinstance(clip, ClipNorm):
+        raise TypeError(f"clip: expected splitcnn.optim.ClipNorm or None, got {type(clip).__name__}")
+    return clip
 
 
 class LRSchedule:

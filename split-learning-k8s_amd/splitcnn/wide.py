@@ -36,7 +36,7 @@ from . import ops
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .ops import _dev, _stream
-from .optim import Adam, LRSchedule
+from .optim import Adam, ClipNorm, LRSchedule, check_clip
 
 P_DROP = 0.25
 KEEP_THRESHOLD = int(round(P_DROP * 4294967296.0))          # keep iff hash >= p * 2^32
@@ -344,26 +344,41 @@ class _AdamRecipe:
     """Optimizer recipe of a K5 stage. Without a config (optim=None, schedule=None) the stage runs
     torch.optim.Adam(lr, betas, eps) on slk_adam_*, `lr` a by-value kernel argument (frozen into a captured
     graph). With an optim.Adam config and / or an optim.LRSchedule it runs slk_adamw_*: weight decay
-    (AdamW or Adam's) and the rate read from the schedule's device table at the stage's step_ctr."""
+    (AdamW or Adam's) and the rate read from the schedule's device table at the stage's step_ctr. With an
+    optim.ClipNorm (`clip`, which like a schedule selects slk_adamw_*) every step is two launches,
+    slk_reduce_sqnorm_multi then slk_adamw_clip_multi: the stage's gradient is clipped by its own global L2
+    norm before weight decay; `grads` keeps the unclipped gradient, `clip_out` the last step's [norm, coef]."""
 
-    def _init_optim(self, optim, schedule):
+    def _init_optim(self, optim, schedule, clip=None):
         if optim is not None and not isinstance(optim, Adam):
             raise TypeError(f"optim: expected splitcnn.optim.Adam or None, got {type(optim).__name__}")
-        if optim is None and schedule is not None:
+        check_clip(clip)
+        if optim is None and (schedule is not None or clip is not None):
             optim = Adam(self.lr, self.betas, self.eps)
         self.optim, self.schedule = optim, None
+        self.clip = self.clip_out = None
         if optim is None:
             return
         self.lr, self.betas, self.eps = optim.lr, optim.betas, optim.eps
         self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
+        if clip is not None:
+            self.clip = clip.to(self.device)
+            self.clip_out = torch.zeros(2, dtype=_F32, device=self.device)   # [norm, coef] of the last step
 
     def _adamw(self, segments, write_grads=True, fuse=True):
         """slk_adamw_* on (lo, n, slabs) slices of this stage (slabs [nslab, n]): ONE launch (fuse) or one
-        per slice."""
+        per slice; with `clip` always the two clip launches over all slices (one group)."""
         segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
                  self.v[lo:lo + n], sl) for lo, n, sl in segments]
         kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
-        if fuse and len(segs) > 1:
+        if self.clip is not None:
+            need = self.clip_npart = ops.clip_partials_needed(segs)   # partials of this stage's last clipped step
+            groups = [(self._buf.get("clip_partials", (need,), _F32, self.device), self.clip_out, segs)]
+            with TIMER("reduce_sqnorm_multi"):
+                ops.reduce_sqnorm_multi(groups)
+            with TIMER("adamw_clip_multi"):
+                ops.adamw_clip_multi(groups, self.clip.value, **kw)
+        elif fuse and len(segs) > 1:
             with TIMER("adamw_multi_from_slabs"):
                 ops.adamw_multi_from_slabs(segs, **kw)
         else:
@@ -379,7 +394,8 @@ class WideClientStage(_AdamRecipe):
     OFF = {"W1": 0, "b1": 1728, "W2": 1792, "b2": 75520, "W3": 75648, "b3": 370560}
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
-                 eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None):
+                 eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None,
+                 clip: Optional[ClipNorm] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartA()).to(self.device)
         m = self.model
@@ -390,7 +406,7 @@ class WideClientStage(_AdamRecipe):
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps = lr, betas, eps
-        self._init_optim(optim, schedule)
+        self._init_optim(optim, schedule, clip)
         self.fuse_adam = True  # step_from_slabs: the three Adam segments in one launch
         self.sh = new_shadows(self.device)   # bf16 conv weight shadows (slk_wide_shadows layouts)
         self._buf = _Buffers()
@@ -503,7 +519,7 @@ class WideServerStage(_AdamRecipe):
 
     def __init__(self, model: Optional[WideModelPartB] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None, optim: Optional[Adam] = None,
-                 schedule: Optional[LRSchedule] = None):
+                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartB()).to(self.device)
         self.params, self.grads = _flat([self.model.fc.weight, self.model.fc.bias], self.device)
@@ -512,7 +528,7 @@ class WideServerStage(_AdamRecipe):
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
-        self._init_optim(optim, schedule)
+        self._init_optim(optim, schedule, clip)
         self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -642,17 +658,20 @@ class WideTrainer(GraphedTrainer):
     `optim` (optim.Adam) and `schedule` (optim.LRSchedule) replace Adam(lr=1e-3): both stages share the
     config and the schedule's device table, each indexing it with its own step counter (the server's also
     seeds the dropout mask), so the captured graph follows the schedule. Without them `lr` is a by-value
-    kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it)."""
+    kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it). `clip`
+    (optim.ClipNorm, shared by both stages) clips each stage's gradient by that stage's own global norm before
+    its Adam update; grad_norms() reads the last step's norms."""
 
     input_shape = (3, 32, 32)
 
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
-                 schedule: Optional[LRSchedule] = None):
+                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None):
+        check_clip(clip)
         super().__init__(device, graph)
-        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule)
+        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
-                                      schedule=self.client.schedule)
+                                      schedule=self.client.schedule, clip=self.client.clip)
 
     def _eager(self, x, y):
         c = self.client
