@@ -8,7 +8,8 @@
 // 3 f16 MFMAs (48 cycles) per 16x16x32 block instead of 8 f32 MFMAs (256 cycles).
 //
 // Scales (exact powers of two, so unscaling the f32 accumulator is exact):
-//   - weights: one per launch, from max|W2| (every workgroup reduces W2 itself in its prologue);
+//   - weights: one per launch, from max|W2| (every workgroup reduces W2 itself in its launch head, from the one
+//     coalesced read that also feeds its fragments through LDS);
 //   - data operands: one per SAMPLE, from a per-sample max |.| array (slk_row_amax, or fused into the
 //     producer), so that the largest element lands in [2^13, 2^14): nothing overflows f16's 65504 and
 //     nothing that matters reaches f16's subnormal range (values 2^-38 below a sample's max lose
@@ -108,6 +109,51 @@ __global__ __launch_bounds__(256) void row_amax_kernel(const float* __restrict__
     __syncthreads();
     if (threadIdx.x == 0) amax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
+
+#ifndef SLK_X3D_TRACE
+#define SLK_X3D_TRACE 0
+#endif
+// profiling only (wrong results): the launch heads' global reads replaced by values made from the index — bit 1 the
+// forward's W2 reads, bit 2 the dgrad's W2 reads, bit 4 the wgrads' act_amax / dp_amax reads. Against the product
+// build this bounds what the heads' memory latency costs per launch.
+#ifndef SLK_X3H_ABL
+#define SLK_X3H_ABL 0
+#endif
+// element e of a head's global operand (SLK_X3H_ABL bit set: a value made from the index, no load)
+template <int BIT>
+__device__ __forceinline__ float x3_head_ld(const float* __restrict__ p, int e) {
+    if constexpr ((SLK_X3H_ABL & BIT) != 0) return (float)((e & 1023) + 1) * 0x1p-12f;
+    else return p[e];
+}
+#if SLK_X3D_TRACE
+// profiling probe: per (workgroup, wave, unit) shader-clock stamps of the dgrad's phases (lane 0, vector stores)
+__device__ unsigned long long g_x3d_trace[256 * 8 * 128 * 8];
+#define X3_TS(buf, u, slot)                                                                                 \
+    do {                                                                                                   \
+        unsigned long long _t;                                                                             \
+        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");                          \
+        if (lane == 0 && (u) < 128) buf[(((size_t)blockIdx.x * 8 + wave) * 128 + (u)) * 8 + (slot)] = _t;  \
+    } while (0)
+#define X3D_TS(u, slot) X3_TS(g_x3d_trace, u, slot)
+#define X3Q_TS(u, slot) X3_TS(g_x3q_trace, u, slot)
+__device__ unsigned long long g_x3q_trace[256 * 8 * 128 * 8];
+extern "C" int slk_x3q_trace_read(void* dst) {
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3q_trace), sizeof(g_x3q_trace)) == hipSuccess ? 0 : 1;
+}
+// the forward's stamps: launch start (0, 7), weights in registers (1, 7), each unit's barrier (k, 0), end (127, 7)
+__device__ unsigned long long g_x3f_trace[256 * 8 * 128 * 8];
+#define X3F_TS(u, slot) X3_TS(g_x3f_trace, u, slot)
+extern "C" int slk_x3f_trace_read(void* dst) {
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3f_trace), sizeof(g_x3f_trace)) == hipSuccess ? 0 : 1;
+}
+extern "C" int slk_x3d_trace_read(void* dst) {
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3d_trace), sizeof(g_x3d_trace)) == hipSuccess ? 0 : 1;
+}
+#else
+#define X3D_TS(u, slot)
+#define X3Q_TS(u, slot)
+#define X3F_TS(u, slot)
+#endif
 
 // ============================================================================ conv2 forward + pool
 // Unit = (sample, third): output rows 8t..8t+7 (window rows 4t..4t+3), input rows 8t..8t+9 (the
@@ -277,6 +323,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
     const int ch = wave & 1, wr = wave >> 1;
     const int n16 = lane & 15, kc = lane >> 4;
     char* const raw0 = smem + 2 * X3F_BUF;
+    X3F_TS(0, 7);
 
     const int U = 3 * B;
     const int G = gridDim.x;
@@ -328,6 +375,17 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
         const int c = g / 65, r = g - (g / 65) * 65;
         voff[k] = (uint32_t)(c * A_PIX * 4 + r * 16);
     }
+    // W2, read ONCE per workgroup and coalesced: thread tid holds elements tid + 512 r (36 dwords — W2 is only 4-B
+    // aligned — every load in flight before the first wait, and ahead of the units' DMA). The weight scale's
+    // maximum and, through an LDS staging area, every lane's fragments come from these registers (below).
+    constexpr int WR = W2_N / X3F_THREADS;
+    static_assert(WR * X3F_THREADS == W2_N && WR % 2 == 0, "a thread's W2 dwords, half per co half");
+    float wv[WR];
+#pragma unroll
+    for (int r = 0; r < WR; ++r) wv[r] = x3_head_ld<1>(W2, tid + X3F_THREADS * r);
+    float bias[X3F_NT];
+#pragma unroll
+    for (int nt = 0; nt < X3F_NT; ++nt) bias[nt] = b2[32 * ch + 16 * nt + n16];
     // IN16: unit uu's image -> ring slot
     auto issue_img = [&](int uu, char* dstp) { x3_issue_unit_img(act16, uu, wave, lane, lds_u32(dstp)); };
     if constexpr (IN16) {
@@ -364,16 +422,58 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
     }
 
     // weight scale: max |W2| over the whole tensor
+    // (tried: the lane's maximum pinned before the DMA issue, so that hipcc's wait for these registers does not
+    // also cover two units' images — 0.1868 vs 0.1854 ms at B = 4096, 0.0378 vs 0.0385 at B = 512: inside the spread)
     float wm = 0.f;
-    for (int e = tid; e < W2_N; e += X3F_THREADS) wm = fmaxf(wm, fabsf(W2[e]));
+#pragma unroll
+    for (int r = 0; r < WR; ++r) wm = fmaxf(wm, fabsf(wv[r]));
     wm = wave_max(wm);
     if (lane == 0) red[wave] = wm;
-    __syncthreads();
-    wm = red[0];
+    // B fragments: lane (n16, kc) holds W2[co][8kc .. 8kc+7][tap], co = 32ch + 16nt + n16, gathered from an LDS
+    // copy of W2 instead of global memory (where one instruction's lanes sat in 64 different lines, after a serial
+    // loop of drained loads over the same bytes for the maximum). The copy goes where no DMA in flight lands — the
+    // third ring slot onward (IN16) or the f16 buffers (f32 rows) — 66,560 B, less than W2: one co half (a thread's
+    // first / last 18 dwords) per pass, gathered by the waves of that half. Row co' of a half starts at dword
+    // 313 co' and its kc chunk at + 80 kc, so the 32 lanes (16 n16, 2 kc) of a ds_read_b32 half hit banks
+    // 25 n16 + 16 kc: distinct (tools/lds_banks.py).
+    constexpr int WROW = C1 * 9 + 25, WKC = 72 + 8, WRH = WR / 2;
+    static_assert(WRH * X3F_THREADS == (C2 / 2) * C1 * 9 && (C2 / 2) * WROW * 4 <= 2 * X3F_BUF, "W2 half staging");
+    float* const wst = reinterpret_cast<float*>(IN16 ? smem + 2 * X3F_BUF : smem);
+    int sw = 0;
+    float wsc = 1.f;
+    f16x8 wh[X3F_NT][9], wl[X3F_NT][9];
 #pragma unroll
-    for (int i = 1; i < X3F_WAVES; ++i) wm = fmaxf(wm, red[i]);
-    const int sw = x3_exp(wm);
-    const float wsc = ldexpf(1.f, sw);
+    for (int p = 0; p < 2; ++p) {
+        if (p) __syncthreads();  // the first half's gathers are done before it is overwritten
+#pragma unroll
+        for (int r = 0; r < WRH; ++r) {
+            const int e = tid + X3F_THREADS * r, co = e / (C1 * 9), rem = e - co * (C1 * 9);
+            wst[co * WROW + (rem / 72) * WKC + rem % 72] = wv[WRH * p + r];
+        }
+        __syncthreads();
+        if (p == 0) {
+            wm = red[0];
+#pragma unroll
+            for (int i = 1; i < X3F_WAVES; ++i) wm = fmaxf(wm, red[i]);
+            sw = x3_exp(wm);
+            wsc = ldexpf(1.f, sw);
+        }
+        if (ch == p) {
+            const float* wg = wst + n16 * WROW + kc * WKC;
+#pragma unroll
+            for (int nt = 0; nt < X3F_NT; ++nt)
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    float v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = wg[nt * 16 * WROW + j * 9 + tap];
+                    x3_split8(v, wsc, wh[nt][tap], wl[nt][tap]);
+                    // 3 taps' reads in flight at a time: all 144 hoisted to the top took the head (not the unit
+                    // loop) to the register limit
+                    if (tap % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+                }
+        }
+    }
     auto red_amx_max = [&]() {
         float m = red_amx[0];
 #pragma unroll
@@ -407,21 +507,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
         else return x3_exp(amax[b]);
     };
 
-    // B fragments: lane (n16, kc) holds W2[co][8kc .. 8kc+7][tap], co = 16nt + n16
-    f16x8 wh[X3F_NT][9], wl[X3F_NT][9];
-    float bias[X3F_NT];
-#pragma unroll
-    for (int nt = 0; nt < X3F_NT; ++nt) {
-        const int co = 32 * ch + 16 * nt + n16;
-        bias[nt] = b2[co];
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = W2[(co * C1 + 8 * kc + j) * 9 + tap];
-            x3_split8(v, wsc, wh[nt][tap], wl[nt][tap]);
-        }
-    }
+    X3F_TS(1, 7);
     // A fragment bases per (mt, kx): M row m = n16 -> window wx = 4mt + (m >> 2), position q = m & 3;
     // the pixel's chunk slot is kc ^ (x & 2) (x = its column in the unit)
     int abase[3][3];
@@ -498,6 +584,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
         if constexpr (IN16) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE + 4) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE) : "memory");
         __syncthreads();
+        X3F_TS(k, 0);
         const int kr = k % 3;  // IN16 ring slot of unit u
         if constexpr (AMX) {
             if (u - 3 * (u / 3) == 0 && u > u0) am_cur = am_nxt;
@@ -632,6 +719,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
             x3f_store_row<CODE>(hm[0][nt], hm[1][nt], m2, hc[0][nt], hc[1][nt], c2, kc, pooled + ro, CODE ? code + ro : nullptr);
         }
     }
+    X3F_TS(127, 7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA outlives the workgroup
 }
 
@@ -670,9 +758,6 @@ constexpr int X3D_MPW = 4;                         // M tiles per wave and part 
 constexpr int X3D_GRID = 256;
 constexpr int X3D_ITEMS_MAX = 7 * P_HW * 8;        // (window, 4-co group) items of the largest part (672)
 static_assert(2 * X3D_IMG <= 163840, "LDS");
-#ifndef SLK_X3D_TRACE
-#define SLK_X3D_TRACE 0
-#endif
 // the fused dgrad's client epilogue on the f16 MFMA (split operands) instead of the f32 MFMA
 #ifndef SLK_X3D_EPI16
 #define SLK_X3D_EPI16 0
@@ -681,28 +766,6 @@ static_assert(2 * X3D_IMG <= 163840, "LDS");
 // bit 8 no dY global loads (the staging stores kept)
 #ifndef SLK_X3D_ABL
 #define SLK_X3D_ABL 0
-#endif
-#if SLK_X3D_TRACE
-// profiling probe: per (workgroup, wave, unit) shader-clock stamps of the dgrad's phases (lane 0, vector stores)
-__device__ unsigned long long g_x3d_trace[256 * 8 * 128 * 8];
-#define X3_TS(buf, u, slot)                                                                                 \
-    do {                                                                                                   \
-        unsigned long long _t;                                                                             \
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");                          \
-        if (lane == 0 && (u) < 128) buf[(((size_t)blockIdx.x * 8 + wave) * 128 + (u)) * 8 + (slot)] = _t;  \
-    } while (0)
-#define X3D_TS(u, slot) X3_TS(g_x3d_trace, u, slot)
-#define X3Q_TS(u, slot) X3_TS(g_x3q_trace, u, slot)
-__device__ unsigned long long g_x3q_trace[256 * 8 * 128 * 8];
-extern "C" int slk_x3q_trace_read(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3q_trace), sizeof(g_x3q_trace)) == hipSuccess ? 0 : 1;
-}
-extern "C" int slk_x3d_trace_read(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3d_trace), sizeof(g_x3d_trace)) == hipSuccess ? 0 : 1;
-}
-#else
-#define X3D_TS(u, slot)
-#define X3Q_TS(u, slot)
 #endif
 
 __device__ __forceinline__ int x3d_t0(int pt) { return pt == 0 ? 0 : (pt == 1 ? 15 : 29); }
@@ -766,40 +829,12 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
     const int G = gridDim.x;
     X3D_TS(0, 7);
 
-    // zero both images once: the leading pixels and columns 24-25 are never written again
-    for (int o = tid * 16; o < 2 * X3D_IMG; o += X3D_THREADS * 16) *reinterpret_cast<uint4*>(smem + o) = make_uint4(0, 0, 0, 0);
-
-    // weight scale (max |W2|), reduced through the tail of image 1 (outside every image pixel's h|l)
-    float* red = reinterpret_cast<float*>(smem + X3D_IMG + 128);  // pixel 0's pad is never read
-    float wm = 0.f;
-    for (int e = tid; e < W2_N; e += X3D_THREADS) wm = fmaxf(wm, fabsf(W2[e]));
-    wm = wave_max(wm);
-    __syncthreads();  // zeroing done before red[] is written into image 1
-    if (lane == 0) red[wave] = wm;
-    __syncthreads();
-    wm = red[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) wm = fmaxf(wm, red[i]);
-    __syncthreads();
-    if (tid < 8) red[tid] = 0.f;  // restore the zero image
-    const int sw = x3_exp(wm);
-    const float wsc = ldexpf(1.f, sw);
-    // B fragments: lane (n16, kc) holds W2[32h + 8kc + j][ci][tap], ci = 16nt + n16
+    // weight scale 2^sw (from max |W2|) and the B fragments: lane (n16, kc) holds W2[32h + 8kc + j][ci][tap],
+    // ci = 16nt + n16 — set by the launch head below, once the first unit's loads can be issued ahead of it
+    int sw;
+    float wsc;
     f16x8 wh[2][9], wl[2][9];
-    {
-        const int ci = 16 * nt + n16;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = W2[((32 * h + 8 * kc + j) * C1 + ci) * 9 + tap];
-                x3_split8(v, wsc, wh[h][tap], wl[h][tap]);
-            }
-    }
 
-    X3D_TS(1, 7);
     // expansion items of a unit: i = tid + 512 r -> 4-co group c4 = i & 7, window wi = i >> 3 (row-major
     // over the part's image window rows); rows outside 0..11 expand to zeros
     constexpr int NR = 2, SSTR = X3D_THREADS;
@@ -937,6 +972,54 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
             }
         }
     };
+    // Launch head. W2 is read ONCE per workgroup, coalesced: thread tid holds elements tid + 512 r (36 dwords,
+    // every load in flight before the first wait; dwords: W2 is only 4-B aligned). The scale's max |W2| comes from
+    // these registers; the same registers are staged in the (still unused) image area, and each lane gathers its
+    // 144 fragment values from there instead of from global memory (36-B runs over ~20 lines per instruction,
+    // after a serial loop of drained loads over the same bytes for the maximum). Staged element e sits at dword
+    // e + 16 (e / 2304): the four kc groups of a fragment read (8 co = 2,304 dwords apart, the same banks) land 16
+    // banks apart, so a 32-lane half (n16 x 9 dwords, 2 kc) reads 32 distinct banks (tools/lds_banks.py). The first
+    // unit's dY loads go out before the staging, so their latency hides behind it.
+    {
+        constexpr int WR = W2_N / X3D_THREADS, WKC = 8 * C1 * 9, WPAD = 16;  // 36 dwords a thread; a kc group
+        static_assert(WR * X3D_THREADS == W2_N && (W2_N + WPAD * (W2_N / WKC)) * 4 + 64 <= 2 * X3D_IMG, "W2 staging");
+        float wv[WR];
+#pragma unroll
+        for (int r = 0; r < WR; ++r) wv[r] = x3_head_ld<2>(W2, tid + X3D_THREADS * r);
+        if (pr < p1) load_dy(2 * pr);
+        float wm = 0.f;
+#pragma unroll
+        for (int r = 0; r < WR; ++r) wm = fmaxf(wm, fabsf(wv[r]));
+        wm = wave_max(wm);
+        float* const wst = reinterpret_cast<float*>(smem);
+        float* const red = wst + W2_N + WPAD * (W2_N / WKC);  // past the staged weights
+#pragma unroll
+        for (int r = 0; r < WR; ++r) {
+            const int e = tid + X3D_THREADS * r;
+            wst[e + WPAD * (e / WKC)] = wv[r];
+        }
+        if (lane == 0) red[wave] = wm;
+        __syncthreads();
+        wm = red[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) wm = fmaxf(wm, red[i]);
+        sw = x3_exp(wm);
+        wsc = ldexpf(1.f, sw);
+        const float* wg = wst + kc * (WKC + WPAD) + (16 * nt + n16) * 9;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = wg[h * 4 * (WKC + WPAD) + j * C1 * 9 + tap];
+                x3_split8(v, wsc, wh[h][tap], wl[h][tap]);
+            }
+        __syncthreads();  // every lane's gather done before the images are zeroed
+    }
+    // zero both images once: the leading pixels and columns 24-25 are never written again
+    for (int o = tid * 16; o < 2 * X3D_IMG; o += X3D_THREADS * 16) *reinterpret_cast<uint4*>(smem + o) = make_uint4(0, 0, 0, 0);
+    X3D_TS(1, 7);
     if (pack && pr < p1) issue_pk(pr, 0);
     if constexpr (C1W) {
         d1s[tid] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -944,8 +1027,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
         if (pr < p1) issue_xb(pr, 0);
     }
     if (pr < p1) {
-        load_dy(2 * pr);
-        __syncthreads();  // zeroing / red restore done before the first expansion
+        __syncthreads();  // zeroing done before the first expansion
         store_dy(2 * pr, smem);
         load_dy(2 * pr + 1);
     }
@@ -1627,8 +1709,8 @@ __global__ __launch_bounds__(X3Q_THREADS, 1) void conv2_wgrad_x3q_kernel(
     // launch scales: max over the batch of the per-sample maxima (as conv2_wgrad_x3_kernel)
     float ma = 0.f, md = 0.f;
     for (int i = tid; i < B; i += X3Q_THREADS) {
-        ma = fmaxf(ma, act_amax[i]);
-        md = fmaxf(md, dp_amax[i]);
+        ma = fmaxf(ma, x3_head_ld<4>(act_amax, i));
+        md = fmaxf(md, x3_head_ld<4>(dp_amax, i));
     }
     ma = wave_max(ma);
     md = wave_max(md);
@@ -1974,8 +2056,8 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     // launch scales: max over the batch of the per-sample maxima (as conv2_wgrad_x3q_kernel)
     float ma = 0.f, md = 0.f;
     for (int i = tid; i < B; i += X3P_THREADS) {
-        ma = fmaxf(ma, act_amax[i]);
-        md = fmaxf(md, dp_amax[i]);
+        ma = fmaxf(ma, x3_head_ld<4>(act_amax, i));
+        md = fmaxf(md, x3_head_ld<4>(dp_amax, i));
     }
     ma = wave_max(ma);
     md = wave_max(md);
@@ -2121,7 +2203,7 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     const int u0 = min(ks * per, U), u1 = min(u0 + per, U);
     sb0 = u0 / 3;
     const int nsb = u1 > u0 ? (u1 - 1) / 3 - sb0 + 1 : 0;
-    for (int j = tid; j < nsb; j += X3P_THREADS) sbt[j] = sd + sx - max(x3_exp(act_amax[sb0 + j]), sx);
+    for (int j = tid; j < nsb; j += X3P_THREADS) sbt[j] = sd + sx - max(x3_exp(x3_head_ld<4>(act_amax, sb0 + j)), sx);
     __syncthreads();
     int u = u0;
     if (u < u1) {

@@ -146,6 +146,26 @@ def wgrad_store_dy(flip):
     return 2 * tot  # h and l planes
 
 
+def w2_heads(fwd_row, fwd_kc, dg_pad):
+    """The x3 forward's and dgrad's launch heads: every lane gathers its 144 fragment values (ds_read_b32) from
+    an LDS copy of W2, written there by thread tid's elements tid + 512 r (ds_write_b32). Forward: a co half, row
+    co' at dword fwd_row co', its 8-ci chunk kc at + fwd_kc kc (288 / 72: plain W2 order). Dgrad: element e at dword
+    e + dg_pad (e // 2304). Returns the worst and the total extra cycles of (forward reads, forward stores, dgrad
+    reads, dgrad stores) per wave (forward) / workgroup thread row (stores)."""
+    def stats(per_instr):
+        ex = [extra_cycles32(d, B32_GROUPS) for d in per_instr]
+        return max(ex), sum(ex)
+    fr = [[[(16 * nt + (l & 15)) * fwd_row + (l >> 4) * fwd_kc + j * 9 + tap] for l in range(64)]
+          for nt, tap, j in itertools.product(range(2), range(9), range(8))]
+    fpos = lambda e: (e // 288) * fwd_row + ((e % 288) // 72) * fwd_kc + e % 72  # noqa: E731
+    fs = [[[fpos(64 * w + l + 512 * r)] for l in range(64)] for w, r in itertools.product(range(8), range(18))]
+    dr = [[[(4 * h + (l >> 4)) * (2304 + dg_pad) + j * 288 + (16 * nt + (l & 15)) * 9 + tap] for l in range(64)]
+          for nt, h, tap, j in itertools.product(range(2), range(2), range(9), range(8))]
+    ds = [[[e + dg_pad * (e // 2304) for e in [64 * w + l + 512 * r]] for l in range(64)]
+          for w, r in itertools.product(range(8), range(36))]
+    return stats(fr), stats(fs), stats(dr), stats(ds)
+
+
 SWIZZLES = {
     "c8 ^ (x & 2)  (round 2)": lambda c8, x: c8 ^ (x & 2),
     "c8 ^ (x & 2) ^ ((x >> 2) & 2)": lambda c8, x: c8 ^ (x & 2) ^ ((x >> 2) & 2),
@@ -164,3 +184,7 @@ if __name__ == "__main__":
           dgrad_epi(812, 7))
     print("wgrad dY staging stores, extra cycles per unit: same position order", wgrad_store_dy(False),
           "| odd windows pos ^ 1 (round 4):", wgrad_store_dy(True))
+    for name, a in (("plain W2 order", (288, 72, 0)), ("fwd rows 313 / kc 80, dgrad + 16 per 2304 (round 7)", (313, 80, 16))):
+        (fr, fs, dr, ds) = w2_heads(*a)
+        print(f"W2 head staging, {name}: (worst, total) extra cycles — fwd gather {fr} of 144 reads, fwd stores {fs} of "
+              f"144, dgrad gather {dr} of 288, dgrad stores {ds} of 288")

@@ -223,7 +223,9 @@ def main():
             times[k].append(e0.elapsed_time(e1))
     for k, v in sorted(times.items()):
         v.sort()
-        print(f"{k:24s} median {v[len(v) // 2]:.4f} ms  min {v[0]:.4f}", flush=True)
+        # the spread of a case's own rounds: its quartiles and extremes
+        print(f"{k:24s} median {v[len(v) // 2]:.4f} ms  min {v[0]:.4f}  q1 {v[len(v) // 4]:.4f}  "
+              f"q3 {v[(3 * len(v)) // 4]:.4f}  max {v[-1]:.4f}", flush=True)
     first = {}
     for k, t in outs.items():  # each library's output vs the first library's (same op)
         op = k.split()[0]

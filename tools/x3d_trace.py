@@ -4,7 +4,9 @@ unit) shader-clock stamps at the unit barrier, around the staging and the MFMA l
 conv1-gradient epilogue. Prints the mean cycles per phase per wave slot.
 --kernel wgrad: the same for conv2_wgrad_x3q_kernel (stamps at the unit barrier, after the first-half
 waves' dY routing + image DMA issue, after the MFMAs, after the second-half waves' routing).
-usage: python tools/x3d_trace.py build_abl/x3dtrace.so [--B 4096] [--kernel dgrad|wgrad]"""
+--kernel fwd: conv2_fwd_pool_x3_kernel<IN16> (slk_conv2_fwd_pool_x3i): launch start, weights in registers,
+every unit's barrier, end of the last unit — the head (start to the first unit barrier) against a unit.
+usage: python tools/x3d_trace.py build_abl/x3dtrace.so [--B 4096] [--kernel dgrad|wgrad|wgradp|fwd]"""
 import argparse
 import ctypes
 import os
@@ -23,7 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib")
     ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--kernel", default="dgrad", choices=["dgrad", "wgrad", "wgradp"])
+    ap.add_argument("--kernel", default="dgrad", choices=["dgrad", "wgrad", "wgradp", "fwd"])
     args = ap.parse_args()
     from splitcnn import ops
     from splitcnn.data import SyntheticMNIST, init_models
@@ -63,6 +65,11 @@ def main():
         L.slk_conv2_wgrad_x3s.argtypes = [P] * 6 + [ctypes.c_int, P]
         slw = torch.empty(L.slk_conv2_wgrad_x3_nslab(B), 18496, device=dev)
         run = lambda: L.slk_conv2_wgrad_x3s(p(a16), p(am1), p(dp), p(dpa), p(code), p(slw), B, st)  # noqa: E731
+    if args.kernel == "fwd":
+        L.slk_conv2_fwd_pool_x3i.restype = ctypes.c_int
+        L.slk_conv2_fwd_pool_x3i.argtypes = [P] * 6 + [ctypes.c_int, P]
+        po, co = torch.empty_like(pooled), torch.empty_like(code)
+        run = lambda: L.slk_conv2_fwd_pool_x3i(p(a16), p(am1), p(W2), p(b2), p(po), p(co), B, st)  # noqa: E731
     ms = []
     for i in range(12):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -73,7 +80,8 @@ def main():
         ms.append(e0.elapsed_time(e1))
     ms = sorted(ms[2:])
     buf = np.zeros(256 * 8 * NU * NS, dtype=np.uint64)
-    rd = L.slk_x3q_trace_read if args.kernel != "dgrad" else L.slk_x3d_trace_read
+    rd = {"dgrad": "slk_x3d_trace_read", "fwd": "slk_x3f_trace_read"}.get(args.kernel, "slk_x3q_trace_read")
+    rd = getattr(L, rd)
     assert rd(ctypes.c_void_p(buf.ctypes.data)) == 0
     T = buf.reshape(256, 8, NU, NS).astype(np.int64)
     t_start = T[:, :, 0, 7]
@@ -81,6 +89,9 @@ def main():
     span = (t_end.max() - t_start.min())
     print(f"kernel median {ms[len(ms) // 2]:.4f} ms; stamp span {span} ticks -> {span / (ms[len(ms) // 2] * 1e3):.1f} ticks/us")
     G = 256
+    if args.kernel == "fwd":
+        fwd_report(T, min((3 * B + G - 1) // G, NU - 1))
+        return
     if args.kernel == "wgrad":
         wgrad_report(T, (6 * B + G - 1) // G)
         return
@@ -128,6 +139,22 @@ def main():
             print(f"part {pt} h {h}: unit {unit[wgs, :, uus].mean():7.0f}  barrier wait by wave "
                   + " ".join(f"{bar[wgs, w, uus].mean():5.0f}" for w in range(8))
                   + "  mfma by wave " + " ".join(f"{(main_ + t3)[wgs, w, uus].mean():5.0f}" for w in range(8)))
+
+
+def fwd_report(T, nu):
+    """Workgroups with a full range only (the last ones of the grid may hold fewer units or none)."""
+    full = T[:, 0, nu - 1, 0] > 0
+    T = T[full]
+    wts = T[:, :, 1, 7] - T[:, :, 0, 7]
+    bar0 = T[:, :, 0, 0] - T[:, :, 1, 7]
+    head = T[:, :, 0, 0] - T[:, :, 0, 7]
+    unit = np.diff(T[:, :, :nu, 0], axis=2) if nu > 1 else np.zeros((1, 1, 1))
+    tail = T[:, :, 127, 7] - T[:, :, nu - 1, 0]
+    print(f"units per workgroup {nu}; {int(full.sum())} workgroups with a full range")
+    print(f"head: start -> weights in registers {wts.mean():.0f}  -> first unit barrier {bar0.mean():.0f}  "
+          f"(head total {head.mean():.0f}, max over waves {head.max(1).mean():.0f})")
+    print(f"unit (barrier to barrier) mean {unit.mean():.0f}  last barrier -> end {tail.mean():.0f}  "
+          f"workgroup span {(T[:, :, 127, 7].max(1) - T[:, :, 0, 7].min(1)).mean():.0f}")
 
 
 def wgrad_report(T, nu):
