@@ -397,6 +397,31 @@ int slk_sgdm_clip_multi(float* const* params, const float* const* grads, float* 
 int slk_mnist_batch(const uint8_t* images, const uint8_t* labels, int n_images, const int64_t* idx,
                     int B, float mean, float std, float* x, int64_t* y, int* err_flag, void* stream);
 
+/* Training batch with augmentation from an HBM-resident u8 dataset images [n_images][C][H][W] (4-byte aligned)
+ * and labels [n_images], one launch: for b < B and i = idx[b], torchvision's
+ *   RandomCrop(H, padding=pad, fill 0) -> RandomHorizontalFlip(0.5) -> ToTensor() -> Normalize(mean[C], std[C])
+ * as x f32 [B,C,H,W] (16-byte aligned) and y[b] = labels[i] (i64). With the sample's draws dy, dx in [0, 2*pad]
+ * and flip in {0, 1}:
+ *   xs = (flip ? W-1-xo : xo) + dx - pad;  ys = yo + dy - pad
+ *   p  = (0 <= xs < W && 0 <= ys < H) ? images[i][c][ys][xs] : 0        (u8: the padding is in pixel space)
+ *   x[b][c][yo][xo] = ((float)p / 255.0f - mean[c]) / std[c]            (f32, IEEE division, as slk_mnist_batch)
+ * so a padded pixel is (0 - mean[c]) / std[c], not 0. The draws are a counter-based hash of the DATASET index,
+ * not of the batch position b (all uint32 arithmetic, lowbias32 as in the K5 dropout mask):
+ *   e  = (uint32)i * 0x9E3779B1 + epoch * 0x85EBCA77 + seed * 0xC2B2AE3D
+ *   h0 = lowbias32(e);  h1 = lowbias32(h0 + 0x9E3779B9);  h2 = lowbias32(h1 + 0x9E3779B9)
+ *   dy = ((uint64)h0 * (2*pad+1)) >> 32;  dx = ((uint64)h1 * (2*pad+1)) >> 32;  flip = flip_enabled ? h2 >> 31 : 0
+ * so a sample's augmentation in an epoch does not depend on batch size, shuffle order or a ragged last batch.
+ * The same distribution as torchvision's transforms from another random stream. pad = 0, flip_enabled = 0 is
+ * plain gather + normalise (evaluation), bitwise slk_mnist_batch for (1,28,28).
+ * (C,H,W) is (3,32,32) or (1,28,28); anything else, pad outside [0, 8], a null or misaligned pointer returns the
+ * invalid-argument status without a launch; B == 0 returns 0. mean and std are HOST arrays of C floats, read
+ * during the call and passed by value (like seed, epoch, pad, flip_enabled: a captured graph would keep them).
+ * An idx outside [0, n_images) sets *err_flag (if non-null) and reads image 0 with image 0's draws. No byte
+ * outside the dataset is ever addressed. */
+int slk_image_batch(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                    const int64_t* idx, int B, const float* mean, const float* std, int pad, int flip_enabled,
+                    uint32_t seed, uint32_t epoch, float* x, int64_t* y, int* err_flag, void* stream);
+
 
 /* ================================================================ lossless cut-exchange codec (K3 / K4)
  * The multi-GPU topologies move the cut over RCCL instead of the reference's pickled HTTP body

@@ -51,6 +51,17 @@ __device__ __forceinline__ float slk_lr_at(const float* __restrict__ lr_table, i
     return lr_table[min(max(step, 0), lr_len - 1)];
 }
 
+// The counter-based hash behind the K5 dropout mask (slk_wide_head.hip) and the augmentation draws
+// (slk_data.hip): a pure function of its 32-bit input, so a draw depends on what it is keyed on alone.
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
 // f32-input MFMA wrappers (exact f32, k-ordered fma chain; cdna_hip_programming.md §3).
 // 32x32x2: lane l supplies A[i=l&31][k=l>>5] and B[k=l>>5][j=l&31];
 //          D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5), r in [0,16).

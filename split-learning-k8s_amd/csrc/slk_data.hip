@@ -1,4 +1,5 @@
-// slk_data.hip — the MNIST batch loader as one HBM-resident gather.
+// slk_data.hip — the batch loaders as one HBM-resident gather each: slk_mnist_batch (K2) and
+// slk_image_batch (K5's CIFAR-10 path with crop + flip augmentation, and MNIST with a crop).
 //
 // The reference builds batches with DataLoader(train_dataset, batch_size=64, shuffle=True)
 // (client_part.py:98) over torchvision MNIST with ToTensor() + Normalize((0.1307,), (0.3081,))
@@ -51,4 +52,153 @@ extern "C" int slk_mnist_batch(const uint8_t* images, const uint8_t* labels, int
         reinterpret_cast<const uint32_t*>(images), labels, n_images, idx, B, mean, stdv,
         reinterpret_cast<float4*>(x), y, err_flag);
     return slk_launch_status();
+}
+
+// ---------------------------------------------------------------------------------- slk_image_batch
+// RandomCrop(H, padding=pad, fill 0) -> RandomHorizontalFlip(0.5) -> ToTensor -> Normalize(mean[C], std[C])
+// of the rows idx[b] of a u8 dataset [N][C][H][W], one launch per batch. The per-sample draws come from
+// lowbias32 keyed on the DATASET index (slk.h), so they do not depend on the batch a sample lands in.
+//
+// A quad is four consecutive output pixels of one row, stored as one aligned float4. A thread makes
+// U quads of one sample, 1/U of the sample apart (the lanes of a wave stay on consecutive quads), so the
+// sample's draws are hashed once and 2U loads are in flight per thread. A quad's four
+// source bytes are consecutive too (read backwards when flipped), start at any byte offset and may hang
+// over either edge of the row: the thread loads the two aligned words around them, v_alignbyte cuts the
+// four bytes out, v_perm reverses them for a flip, and the columns outside the row are masked to the
+// padding value 0. A word index is clamped into the dataset BEFORE the load; a clamped word only ever
+// supplies masked columns, since a byte in a column inside the row lies inside the dataset and so does
+// its word. Rows above or below the image, and quads entirely beside it, issue no load.
+// HBM-bound like mnist_batch: C*H*W bytes read, 4*C*H*W written per sample.
+
+// Quads per thread (A/B switches): 4 for CIFAR; 1 for MNIST, whose B = 4096 batch has too few quads to fill
+// the device four to a thread.
+#ifndef SLK_IMAGE_QUADS_CIFAR
+#define SLK_IMAGE_QUADS_CIFAR 4
+#endif
+#ifndef SLK_IMAGE_QUADS_MNIST
+#define SLK_IMAGE_QUADS_MNIST 1
+#endif
+
+namespace {
+constexpr int IMAGE_MAX_C = 3;
+constexpr int IMAGE_MAX_PAD = 8;
+struct ImageNorm {
+    float mean[IMAGE_MAX_C], stdv[IMAGE_MAX_C];
+};
+}  // namespace
+
+template <int C, int H, int W, int U>
+__global__ __launch_bounds__(256) void image_batch_kernel(const uint32_t* __restrict__ words,
+                                                          const uint8_t* __restrict__ labels, int n_images,
+                                                          const int64_t* __restrict__ idx, int B, ImageNorm nrm,
+                                                          int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                                                          float4* __restrict__ x, int64_t* __restrict__ y,
+                                                          int* __restrict__ err) {
+    static_assert(W % 4 == 0 && (C * H * W) % 4 == 0 && C <= IMAGE_MAX_C, "quads of one row, whole words per image");
+    constexpr int QW = W / 4;            // quads per row
+    constexpr int QS = C * H * QW;       // quads per sample
+    constexpr int TS = QS / U;           // threads per sample; thread r0 makes quads r0 + u * TS
+    static_assert(QS % U == 0, "every thread of a sample makes U quads");
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)B * TS) return;
+    const int s = (int)(t / TS), r0 = (int)(t - (int64_t)s * TS);
+    int64_t i = idx[s];
+    if (i < 0 || i >= n_images) {        // out-of-range index: flag it, read row 0 (with row 0's draws)
+        if (r0 == 0 && err) *err = 1;
+        i = 0;
+    }
+    // loaded by every thread (one address per sample) and stored last by one: a load under `r0 == 0` would be
+    // waited for at the end of its branch, in front of the pixel loads
+    const int64_t label = (int64_t)labels[i];
+
+    const uint32_t h0 = lowbias32((uint32_t)i * 0x9E3779B1u + epoch * 0x85EBCA77u + seed * 0xC2B2AE3Du);
+    const uint32_t h1 = lowbias32(h0 + 0x9E3779B9u);
+    const uint32_t h2 = lowbias32(h1 + 0x9E3779B9u);
+    const uint32_t span = 2u * (uint32_t)pad + 1u;
+    const int dy = (int)(((uint64_t)h0 * span) >> 32), dx = (int)(((uint64_t)h1 * span) >> 32);
+    const bool flip = flip_enabled && (h2 >> 31);
+    const int64_t last = (int64_t)n_images * (C * H * W / 4) - 1;   // the dataset's last word
+
+    // Quad u: the four source bytes are columns x0 .. x0+3 of row ys, output pixel k taking x0+k (x0+3-k if
+    // flipped). All loads of the thread are issued before the first is used: the launch is bound by how many
+    // loads are in flight, not by arithmetic.
+    int x0[U], sh[U];
+    uint32_t lo[U], hi[U];
+    bool ld[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW), yo = (r / QW) % H, q = r % QW;
+        const int ys = yo + dy - pad;
+        x0[u] = (flip ? W - 4 - 4 * q : 4 * q) + dx - pad;
+        ld[u] = (unsigned)ys < (unsigned)H && x0[u] > -4 && x0[u] < W;
+        lo[u] = hi[u] = 0;
+        sh[u] = 0;
+        if (ld[u]) {
+            const int64_t a = (((int64_t)i * C + c) * H + ys) * W + x0[u];     // byte address, may be < 0
+            const int64_t wi = a >> 2;
+            sh[u] = (int)(a & 3);
+            lo[u] = words[min(max(wi, (int64_t)0), last)];
+            hi[u] = words[min(max(wi + 1, (int64_t)0), last)];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW);
+        uint32_t w = 0;
+        if (ld[u]) {
+            w = __builtin_amdgcn_alignbyte(hi[u], lo[u], (uint32_t)sh[u]);
+            uint32_t keep = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) keep |= (unsigned)(x0[u] + k) < (unsigned)W ? 0xffu << (8 * k) : 0u;
+            w &= keep;
+            if (flip) w = __builtin_amdgcn_perm(w, w, 0x00010203u);             // byte k <- byte 3-k
+        }
+        // selects, not an index: a per-lane index into the by-value struct would move it to scratch
+        const float mean = c == 0 ? nrm.mean[0] : c == 1 ? nrm.mean[1] : nrm.mean[2];
+        const float stdv = c == 0 ? nrm.stdv[0] : c == 1 ? nrm.stdv[1] : nrm.stdv[2];
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float f = (float)((w >> (8 * k)) & 0xffu) / 255.0f;   // ToTensor
+            v[k] = (f - mean) / stdv;                                     // Normalize
+        }
+        x[(int64_t)s * QS + r] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    if (r0 == 0) y[s] = label;
+}
+
+template <int C, int H, int W, int U>
+static int image_batch_launch(const uint8_t* images, const uint8_t* labels, int n_images, const int64_t* idx, int B,
+                              const ImageNorm& nrm, int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                              float* x, int64_t* y, int* err_flag, void* stream) {
+    const int64_t total = (int64_t)B * (C * H * (W / 4) / U);
+    SLK_CHECK_ARG((total + 255) / 256 <= 0x7fffffff);
+    image_batch_kernel<C, H, W, U><<<(unsigned)((total + 255) / 256), 256, 0, slk_stream(stream)>>>(
+        reinterpret_cast<const uint32_t*>(images), labels, n_images, idx, B, nrm, pad, flip_enabled, seed, epoch,
+        reinterpret_cast<float4*>(x), y, err_flag);
+    return slk_launch_status();
+}
+
+extern "C" int slk_image_batch(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                               const int64_t* idx, int B, const float* mean, const float* stdv, int pad,
+                               int flip_enabled, uint32_t seed, uint32_t epoch, float* x, int64_t* y,
+                               int* err_flag, void* stream) {
+    const bool cifar = C == 3 && H == 32 && W == 32, mnist = C == 1 && H == 28 && W == 28;
+    SLK_CHECK_ARG(cifar || mnist);
+    SLK_CHECK_ARG(B >= 0 && n_images > 0 && pad >= 0 && pad <= IMAGE_MAX_PAD);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(images && labels && idx && x && y && mean && stdv);
+    SLK_CHECK_ARG(((uintptr_t)images & 3) == 0 && ((uintptr_t)x & 15) == 0);
+    ImageNorm nrm = {};
+    for (int c = 0; c < C; ++c) {
+        nrm.mean[c] = mean[c];
+        nrm.stdv[c] = stdv[c];
+    }
+    if (cifar)
+        return image_batch_launch<3, 32, 32, SLK_IMAGE_QUADS_CIFAR>(images, labels, n_images, idx, B, nrm, pad, flip_enabled, seed, epoch, x,
+                                             y, err_flag, stream);
+    return image_batch_launch<1, 28, 28, SLK_IMAGE_QUADS_MNIST>(images, labels, n_images, idx, B, nrm, pad, flip_enabled, seed, epoch, x, y,
+                                         err_flag, stream);
 }

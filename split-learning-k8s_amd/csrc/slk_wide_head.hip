@@ -18,15 +18,6 @@ constexpr int NCH = CUTF / 8;     // 2048 chunks of 8 channels (C8 order: chunk 
 constexpr int NC = 10;
 }  // namespace
 
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // keep bits of the 8 features of chunk fc (C8 order) of sample b: feature index (torch flatten) of
 // element k is (plane*8 + k)*64 + pixel.
 __device__ __forceinline__ uint32_t keep_bits(uint32_t b, int fc, uint32_t step, uint32_t seed, uint32_t thresh) {

@@ -97,6 +97,7 @@ _SIGS = {
     "slk_sgdm_clip_multi": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _I, _P],
     "slk_adamw_clip_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _F, _I, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
+    "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)
     "slk_wide_conv1_fwd": [_P, _P, _P, _P, _P, _I, _P],
     "slk_wide_relu_bits": [_P, _P, _I, _P],

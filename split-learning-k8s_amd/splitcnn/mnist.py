@@ -75,20 +75,27 @@ class MnistIDX:
         return int(self.images.shape[0])
 
 
-class DeviceLoader:
-    """DataLoader(dataset, batch_size, shuffle) with the dataset resident in HBM.
+class ResidentLoader:
+    """DataLoader(dataset, batch_size, shuffle) with a u8 dataset resident in HBM: what DeviceLoader (MNIST)
+    and cifar.CifarLoader share. A subclass names `sample_shape` and launches one batch in `_batch`.
 
     Each epoch draws one permutation (torch.randperm with this loader's generator), copies it to the
-    device once, and yields (x f32 [B,1,28,28], y i64 [B]) per batch; the last batch is ragged like
-    the reference's (drop_last=False). Batches are written into two alternating device buffers, so
-    a consumer must finish with a batch before asking for the one after next."""
+    device once, and yields (x f32 [B, *sample_shape], y i64 [B]) per batch; the last batch is ragged like
+    the reference's (drop_last=False). Batches are written into two alternating device buffer pairs per
+    batch size, the same ones in every epoch (a GraphedTrainer gives each a graph of its own), so a consumer
+    must finish with a batch before asking for the one after next. `epoch` counts the completed passes (the
+    augmentation draws are keyed on it; set_epoch(n) sets it); `err` is set by an out-of-range index."""
 
-    def __init__(self, dataset: MnistIDX, batch_size: int = 64, shuffle: bool = True,
-                 seed: Optional[int] = None, device="cuda", drop_last: bool = False):
+    sample_shape: tuple = ()
+
+    def __init__(self, dataset, batch_size: int = 64, shuffle: bool = True, seed: Optional[int] = None,
+                 device="cuda", drop_last: bool = False, augment=None):
         self.device = torch.device(device)
         self.batch_size = int(batch_size)
         self.shuffle = shuffle
         self.drop_last = drop_last
+        self.augment = augment
+        self.epoch = 0
         self.gen = torch.Generator()
         if seed is not None:
             self.gen.manual_seed(seed)
@@ -96,11 +103,14 @@ class DeviceLoader:
         self.labels = torch.from_numpy(np.ascontiguousarray(dataset.labels)).to(self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n = len(dataset)
-        self._bufs = [None, None]
+        self._bufs = {}
 
     def __len__(self):
         full, rem = divmod(self.n, self.batch_size)
         return full + (1 if rem and not self.drop_last else 0)
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
 
     def order(self) -> torch.Tensor:
         if self.shuffle:
@@ -108,12 +118,21 @@ class DeviceLoader:
         return torch.arange(self.n)
 
     def _buf(self, k: int, B: int):
-        b = self._bufs[k]
-        if b is None or b[0].shape[0] != B:
-            b = (torch.empty((B, 1, 28, 28), dtype=torch.float32, device=self.device),
+        b = self._bufs.get((k, B))
+        if b is None:
+            b = (torch.empty((B,) + self.sample_shape, dtype=torch.float32, device=self.device),
                  torch.empty((B,), dtype=torch.int64, device=self.device))
-            self._bufs[k] = b
+            self._bufs[(k, B)] = b
         return b
+
+    def _augment_args(self) -> dict:
+        a = self.augment
+        if a is None:
+            return dict(pad=0, flip=False, seed=0, epoch=0)
+        return dict(pad=a.pad, flip=a.flip, seed=a.seed, epoch=self.epoch)
+
+    def _batch(self, idx, x, y):
+        raise NotImplementedError
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         perm = self.order().to(self.device, non_blocking=False)
@@ -122,4 +141,23 @@ class DeviceLoader:
             if idx.numel() < self.batch_size and self.drop_last:
                 break
             x, y = self._buf(k & 1, idx.numel())
-            yield ops.mnist_batch(self.images, self.labels, idx, x=x, y=y, err_flag=self.err)
+            yield self._batch(idx, x, y)
+        self.epoch += 1
+
+
+class DeviceLoader(ResidentLoader):
+    """ResidentLoader over MnistIDX: x f32 [B,1,28,28] by one slk_mnist_batch launch per batch. With
+    `augment` (cifar.Augment, e.g. Augment(pad=2, flip=False)) the batch comes from slk_image_batch<1,28,28>
+    instead: RandomCrop(28, padding=pad) (+ flip) before the same ToTensor + Normalize."""
+
+    sample_shape = (1, 28, 28)
+
+    def __init__(self, dataset: MnistIDX, batch_size: int = 64, shuffle: bool = True,
+                 seed: Optional[int] = None, device="cuda", drop_last: bool = False, augment=None):
+        super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment)
+
+    def _batch(self, idx, x, y):
+        if self.augment is None:
+            return ops.mnist_batch(self.images, self.labels, idx, x=x, y=y, err_flag=self.err)
+        return ops.image_batch(self.images, self.labels, idx, mean=(ops.MNIST_MEAN,), std=(ops.MNIST_STD,), x=x,
+                               y=y, err_flag=self.err, **self._augment_args())

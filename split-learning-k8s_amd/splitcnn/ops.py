@@ -770,3 +770,31 @@ def mnist_batch(images, labels, idx, x=None, y=None, err_flag=None, mean=MNIST_M
               float(mean), float(std), x.data_ptr(), y.data_ptr(),
               None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
     return x, y
+
+
+def image_batch(images, labels, idx, *, mean, std, pad=0, flip=False, seed=0, epoch=0, x=None, y=None,
+                err_flag=None):
+    """RandomCrop(H, padding=pad) + RandomHorizontalFlip (if `flip`) + ToTensor + Normalize(mean, std) of the
+    rows `idx` of the HBM-resident u8 dataset `images` [N,C,H,W] ([N,H,W]: C = 1), one slk_image_batch launch;
+    the draws are keyed on (dataset index, epoch, seed) (include/slk.h; cifar.augment_draws is their host
+    twin). pad=0, flip=False is plain gather + normalise. The library decides which (C,H,W) and pad it serves:
+    anything else raises _lib.SLKError (invalid argument)."""
+    if images.dim() == 3:
+        images = images.unsqueeze(1)
+    if images.dim() != 4:
+        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
+    n, C, H, W = (int(d) for d in images.shape)
+    if labels.shape != (n,):
+        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C:
+        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
+    B = int(idx.shape[0])
+    x = _out(x, (B, C, H, W), images, name="x")
+    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    _lib.call("slk_image_batch", _dev(images, "images", dtype=torch.uint8),
+              _dev(labels, "labels", dtype=torch.uint8), n, C, H, W, _dev(idx, "idx", (B,), torch.int64), B,
+              (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), int(pad), int(bool(flip)),
+              int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, x.data_ptr(), y.data_ptr(),
+              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+    return x, y
