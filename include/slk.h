@@ -100,7 +100,8 @@ int slk_conv2_fwd_pool_direct(const float* act, const float* W2, const float* b2
 int slk_fc_fwd(const float* pooled, const float* W3, const float* b3, float* logits, int B,
                void* stream);
 
-/* Cross-entropy (mean reduction, no label smoothing) forward+backward from logits:
+/* Cross-entropy (mean reduction, hard labels, no label smoothing: slk_xent_soft_fwd_bwd has both) forward+backward
+ * from logits:
  * loss_i[b] = logsumexp(z_b) - z_b[y_b];  dlogits = (softmax(z) - onehot(y)) * grad_scale.
  * grad_scale = 1/B reproduces nn.CrossEntropyLoss()'s mean (src/server_part.py:16,49,51).
  * An out-of-range label writes NaN loss/dlogits for that row and sets *err_flag (may be NULL). */
@@ -131,6 +132,43 @@ int slk_fc_xent(const float* pooled, const float* W3, const float* b3, const int
 int slk_fc_xent_amax(const float* pooled, const float* W3, const float* b3, const int64_t* labels, float* logits,
                      float* loss_i, float* dlogits, float* dpooled, float* dp_amax, float grad_scale, int* err_flag,
                      int B, void* stream);
+
+/* ---- soft targets: label smoothing and mixed labels (the soft forms of the four cross-entropy entries)
+ * A target stays one int64 per sample. A MIXED LABEL packs two classes and a weight:
+ *   y = a | (b << 8) | ((int64)float_bits(wb) << 32)       a, b in [0, 10); bits 16-31 zero; wb an f32 in [0, 1]
+ * wb is the weight of class b, 1 - wb that of class a. A plain label a < 10 is the case b = 0, wb = 0, so every
+ * hard-label tensor is a valid mixed label; one with wb != 0 is >= 2^32, which the hard-label entries above flag as
+ * out of range. With smoothing eps in [0, 1] (by value: a captured graph keeps it) and C = 10 the row's target is
+ *   t_j = (1 - eps) * ((j == a ? 1 - wb : 0) + (j == b ? wb : 0)) + eps / C
+ *   loss_i = logsumexp(z) - sum_j t_j z_j;   dlogits_j = (softmax(z)_j - t_j) * grad_scale
+ * i.e. torch.nn.functional.cross_entropy(z, probs, label_smoothing=eps) for the two-class probability target, and
+ * nn.CrossEntropyLoss(label_smoothing=eps) on class indices when wb = 0. In float32, operation by operation (fl = one
+ * rounding; lse = m + logf(se) and expf(z_j - lse) exactly as in the hard-label entries):
+ *   wa = fl(1 - wb);  keep = fl(1 - eps);  flat = fl(eps / 10)                      (IEEE subtraction / division)
+ *   u_j = (j == a ? wa : 0) + (j == b ? wb : 0)                                    (selects, then one addition)
+ *   t_j = fmaf(keep, u_j, flat)
+ *   S = 0;  for j = 0..9 ascending:  if (t_j != 0) S = fmaf(t_j, z_j, S)            (t_j == 0 contributes nothing,
+ *                                                                                    also at z_j = -inf)
+ *   loss_i = fl(lse - S);   dlogits_j = fl(fl(expf(z_j - lse) - t_j) * grad_scale)
+ * With eps = 0 and plain labels t is exactly one-hot and S = z_a, so every soft entry writes bit for bit what its
+ * hard-label twin writes (on -inf logits off the label too). A target is malformed when a >= 10, b >= 10, a bit of
+ * 16-31 is set, y < 0, or wb is NaN or outside [0, 1]: it sets *err_flag (may be NULL) and that row's loss_i and
+ * dlogits are NaN, other rows unaffected — as an out-of-range label in the hard entries. smoothing outside [0, 1]
+ * or NaN returns the invalid-argument status without a launch. Evaluation (slk_fc_eval, slk_eval_logits) stays the
+ * plain cross-entropy on plain labels, as a model.eval() loop reports it. */
+
+/* slk_xent_fwd_bwd with soft targets. */
+int slk_xent_soft_fwd_bwd(const float* logits, const int64_t* labels, float* loss_i, float* dlogits, float grad_scale,
+                          float smoothing, int* err_flag, int B, void* stream);
+/* slk_fc_logits_xent with soft targets: the same logits (bitwise), then the soft loss_i and dlogits. The default K2
+ * step's head when the trainer is built with loss=SoftCrossEntropy(...). */
+int slk_fc_logits_xent_soft(const float* pooled, const float* W3, const float* b3, const int64_t* labels,
+                            float* logits, float* loss_i, float* dlogits, float grad_scale, float smoothing,
+                            int* err_flag, int B, void* stream);
+/* slk_fc_xent / slk_fc_xent_amax with soft targets in one entry: dp_amax may be NULL (then it is not written). */
+int slk_fc_xent_soft(const float* pooled, const float* W3, const float* b3, const int64_t* labels, float* logits,
+                     float* loss_i, float* dlogits, float* dpooled, float* dp_amax, float grad_scale, float smoothing,
+                     int* err_flag, int B, void* stream);
 
 /* fc1 weight/bias gradient partials: slabs [slk_fc_wgrad_nslab(B)][92170] laid out as
  * [dW3 (10*9216) | db3 (10)], i.e. the tail of the server flat block. */
@@ -422,6 +460,32 @@ int slk_image_batch(const uint8_t* images, const uint8_t* labels, int n_images, 
                     const int64_t* idx, int B, const float* mean, const float* std, int pad, int flip_enabled,
                     uint32_t seed, uint32_t epoch, float* x, int64_t* y, int* err_flag, void* stream);
 
+/* slk_image_batch with CutMix (Yun et al. 2019 with lam ~ Beta(1, 1), the paper's setting), one launch, the same two
+ * shapes. For batch position s, i = idx[s] is the primary sample and i2 = idx2[s] (i64 [B]) its partner. Both get
+ * their own crop and flip draws exactly as in slk_image_batch (h0..h2 of their own dataset index). The box comes
+ * from the PRIMARY sample's hash chain, continued, all in integers (64-bit products):
+ *   h3..h7 = lowbias32(previous + 0x9E3779B9), after h2
+ *   apply  = (uint64)h3 < (uint64)(prob * 4294967296.0)         (the threshold is computed once on the host in double)
+ *   side   = max((h4 * H) >> 32, (h5 * H) >> 32)                 (the max of two uniforms has density 2r: the law of
+ *                                                                 sqrt(1 - lam) for lam ~ U(0, 1))
+ *   cy = (h6 * H) >> 32;  cx = (h7 * W) >> 32
+ *   y1 = clip(cy - side/2, 0, H);  y2 = clip(cy + side/2, 0, H)   (integer halves, as the paper's rand_bbox)
+ *   x1 = clip(cx - side/2, 0, W);  x2 = clip(cx + side/2, 0, W)
+ *   area = apply ? (y2 - y1) * (x2 - x1) : 0;   wb = (float)area / (float)(H * W)          (IEEE division)
+ * Output pixel (c, yo, xo) is, for y1 <= yo < y2 and x1 <= xo < x2 (and apply), the u8 pixel sample i2 would have
+ * at (c, yo, xo) under i2's own crop and flip, otherwise sample i's; then the same ToTensor / Normalize arithmetic.
+ * y[s] = labels[i] | labels[i2] << 8 | (int64)float_bits(wb) << 32 (a mixed label, "soft targets" above); an
+ * unapplied or empty box gives the plain label labels[i]. The box is keyed on (dataset index, epoch, seed) like the
+ * crop, so it does not depend on batch size or order; only the partner does. prob = 0 gives bit for bit
+ * slk_image_batch's x and plain labels; idx2 = idx gives its x and labels with a == b. prob outside [0, 1] or NaN
+ * returns the invalid-argument status, as do slk_image_batch's own bad arguments and a null idx2. An idx2 outside
+ * [0, n_images) behaves like an idx outside it (flag, then row 0 with row 0's draws). No byte outside the dataset
+ * is ever addressed, for either source. Other Beta parameters and MixUp (a float blend) are not provided. */
+int slk_image_batch_mix(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                        const int64_t* idx, const int64_t* idx2, int B, const float* mean, const float* std, int pad,
+                        int flip_enabled, uint32_t seed, uint32_t epoch, double prob, float* x, int64_t* y,
+                        int* err_flag, void* stream);
+
 
 /* ================================================================ lossless cut-exchange codec (K3 / K4)
  * The multi-GPU topologies move the cut over RCCL instead of the reference's pickled HTTP body
@@ -507,6 +571,13 @@ int slk_wide_head(const uint16_t* cut, const float* wf8, const float* bf, const 
                   int B, void* stream);
 int slk_wide_head_nslab(int B);
 int slk_wide_head_work(int B);
+/* slk_wide_head with soft targets (mixed labels and `smoothing`: "soft targets" above, the same float32 expression
+ * and the same malformed-target rule): the same dropout, logits, dcut, slabs and work; dcut and the slabs are what
+ * slk_wide_head_bwd writes from this entry's dlogits, bit for bit. */
+int slk_wide_head_soft(const uint16_t* cut, const float* wf8, const float* bf, const int64_t* labels, const int* step,
+                       unsigned seed, unsigned keep_threshold, float keep_scale, float grad_scale, float smoothing,
+                       float* logits, float* loss_i, float* dlogits, uint16_t* dcut, float* slabs, float* work,
+                       int* err_flag, int b0, int B, void* stream);
 /* slk_wide_head split at the loss, for the module path (WideModelPartB.forward -> criterion ->
  * loss.backward(), server_part.py:48-51): _fwd writes the logits (dropout + fc, the same kernel and
  * sum order as slk_wide_head, so bit-identical logits); _bwd takes dlogits from any loss and writes dcut and the fc slabs

@@ -62,6 +62,31 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
     return x;
 }
 
+// The soft-target heads (slk_*_soft, include/slk.h "mixed label"): decode y = a | b << 8 | bits(wb) << 32, validate
+// it, and build the row's target distribution t[10] in the documented float32 order:
+//   u_j = (j == a ? fl(1 - wb) : 0) + (j == b ? wb : 0);  t_j = fmaf(fl(1 - smoothing), u_j, fl(smoothing / 10)).
+// Returns whether the target is well formed (NaN and negative wb fail the compares; y < 0 is wb's sign bit).
+__device__ __forceinline__ bool slk_soft_target(int64_t y, float smoothing, float (&t)[10]) {
+    const uint32_t lo = (uint32_t)(uint64_t)y, hi = (uint32_t)((uint64_t)y >> 32);
+    const uint32_t a = lo & 0xffu, b = (lo >> 8) & 0xffu;
+    const float wb = __uint_as_float(hi);
+    const bool ok = y >= 0 && a < 10u && b < 10u && (lo >> 16) == 0u && wb >= 0.f && wb <= 1.f;
+    const float wa = 1.f - wb, keep = 1.f - smoothing, flat = smoothing / 10.f;
+#pragma unroll
+    for (uint32_t j = 0; j < 10u; ++j) {
+        const float u = (j == a ? wa : 0.f) + (j == b ? wb : 0.f);
+        t[j] = __builtin_fmaf(keep, u, flat);
+    }
+    return ok;
+}
+// S = sum_j t_j z_j over ascending j by fmaf from S = 0, classes with t_j == 0 skipped (a select: 0 * -inf is NaN).
+__device__ __forceinline__ float slk_soft_dot(const float (&t)[10], const float (&z)[10]) {
+    float S = 0.f;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) S = t[j] != 0.f ? __builtin_fmaf(t[j], z[j], S) : S;
+    return S;
+}
+
 // f32-input MFMA wrappers (exact f32, k-ordered fma chain; cdna_hip_programming.md §3).
 // 32x32x2: lane l supplies A[i=l&31][k=l>>5] and B[k=l>>5][j=l&31];
 //          D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5), r in [0,16).

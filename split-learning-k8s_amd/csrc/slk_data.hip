@@ -1,5 +1,6 @@
 // slk_data.hip — the batch loaders as one HBM-resident gather each: slk_mnist_batch (K2) and
-// slk_image_batch (K5's CIFAR-10 path with crop + flip augmentation, and MNIST with a crop).
+// slk_image_batch (K5's CIFAR-10 path with crop + flip augmentation, and MNIST with a crop), plus
+// slk_image_batch_mix, the same gather with CutMix and mixed labels.
 //
 // The reference builds batches with DataLoader(train_dataset, batch_size=64, shuffle=True)
 // (client_part.py:98) over torchvision MNIST with ToTensor() + Normalize((0.1307,), (0.3081,))
@@ -201,4 +202,182 @@ extern "C" int slk_image_batch(const uint8_t* images, const uint8_t* labels, int
                                              y, err_flag, stream);
     return image_batch_launch<1, 28, 28, SLK_IMAGE_QUADS_MNIST>(images, labels, n_images, idx, B, nrm, pad, flip_enabled, seed, epoch, x, y,
                                          err_flag, stream);
+}
+
+// ---------------------------------------------------------------------------------- slk_image_batch_mix
+// slk_image_batch with CutMix (Yun et al. 2019, lam ~ Beta(1, 1)): batch position s shows sample i = idx[s] with a
+// box of sample i2 = idx2[s] pasted in, each under its OWN crop and flip draws, and y[s] is the mixed label
+// a | b << 8 | bits(wb) << 32 (slk.h). The box comes from the primary sample's hash chain continued (h3..h7), all
+// in integers. The selection is made on the u8 pixels, then the same ToTensor / Normalize arithmetic runs.
+//
+// The quad gather is image_batch_kernel's, once per source: a quad on a row outside the box, or with its four
+// columns all outside it, loads only source i; a quad wholly inside loads only source i2; only the at most two
+// quads of a box row that straddle an edge load both, and take their bytes by a mask AFTER each source's own
+// alignbyte / column mask / flip permute (byte k of either word is output pixel k by then). All of a thread's
+// loads are issued before the first use. The clamped-word argument holds per source: each source's word indices
+// are clamped into the dataset before the load, and a clamped word only ever supplies columns that source masks.
+namespace {
+struct ImageDraws {
+    int dy, dx;
+    bool flip;
+    uint32_t h2;
+};
+__device__ __forceinline__ ImageDraws image_draws(int64_t i, uint32_t seed, uint32_t epoch, int pad, int flip_enabled) {
+    const uint32_t h0 = lowbias32((uint32_t)i * 0x9E3779B1u + epoch * 0x85EBCA77u + seed * 0xC2B2AE3Du);
+    const uint32_t h1 = lowbias32(h0 + 0x9E3779B9u);
+    const uint32_t h2 = lowbias32(h1 + 0x9E3779B9u);
+    const uint32_t span = 2u * (uint32_t)pad + 1u;
+    ImageDraws d;
+    d.dy = (int)(((uint64_t)h0 * span) >> 32);
+    d.dx = (int)(((uint64_t)h1 * span) >> 32);
+    d.flip = flip_enabled && (h2 >> 31);
+    d.h2 = h2;
+    return d;
+}
+// the four source bytes of one quad after alignbyte, the column mask and the flip permute: byte k = output pixel k
+__device__ __forceinline__ uint32_t quad_bytes(uint32_t lo, uint32_t hi, int sh, int x0, int W, bool flip) {
+    uint32_t w = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)sh);
+    uint32_t keep = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) keep |= (unsigned)(x0 + k) < (unsigned)W ? 0xffu << (8 * k) : 0u;
+    w &= keep;
+    return flip ? __builtin_amdgcn_perm(w, w, 0x00010203u) : w;
+}
+}  // namespace
+
+template <int C, int H, int W, int U>
+__global__ __launch_bounds__(256) void image_batch_mix_kernel(const uint32_t* __restrict__ words,
+                                                              const uint8_t* __restrict__ labels, int n_images,
+                                                              const int64_t* __restrict__ idx,
+                                                              const int64_t* __restrict__ idx2, int B, ImageNorm nrm,
+                                                              int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                                                              uint64_t apply_below, float4* __restrict__ x,
+                                                              int64_t* __restrict__ y, int* __restrict__ err) {
+    static_assert(W % 4 == 0 && (C * H * W) % 4 == 0 && C <= IMAGE_MAX_C, "quads of one row, whole words per image");
+    constexpr int QW = W / 4, QS = C * H * QW, TS = QS / U;
+    static_assert(QS % U == 0, "every thread of a sample makes U quads");
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)B * TS) return;
+    const int s = (int)(t / TS), r0 = (int)(t - (int64_t)s * TS);
+    int64_t i = idx[s], i2 = idx2[s];
+    if (i < 0 || i >= n_images) {        // out-of-range index: flag it, read row 0 (with row 0's draws)
+        if (r0 == 0 && err) *err = 1;
+        i = 0;
+    }
+    if (i2 < 0 || i2 >= n_images) {      // the partner likewise
+        if (r0 == 0 && err) *err = 1;
+        i2 = 0;
+    }
+    // both labels loaded by every thread and stored last by one (see image_batch_kernel)
+    const int64_t la = (int64_t)labels[i], lb = (int64_t)labels[i2];
+
+    const ImageDraws da = image_draws(i, seed, epoch, pad, flip_enabled);
+    const ImageDraws db = image_draws(i2, seed, epoch, pad, flip_enabled);
+    // the box: the primary sample's chain continued
+    const uint32_t h3 = lowbias32(da.h2 + 0x9E3779B9u), h4 = lowbias32(h3 + 0x9E3779B9u);
+    const uint32_t h5 = lowbias32(h4 + 0x9E3779B9u), h6 = lowbias32(h5 + 0x9E3779B9u);
+    const uint32_t h7 = lowbias32(h6 + 0x9E3779B9u);
+    const bool apply = (uint64_t)h3 < apply_below;
+    const int side = max((int)(((uint64_t)h4 * H) >> 32), (int)(((uint64_t)h5 * H) >> 32)), half = side / 2;
+    const int cy = (int)(((uint64_t)h6 * H) >> 32), cx = (int)(((uint64_t)h7 * W) >> 32);
+    const int y1 = min(max(cy - half, 0), H), y2 = apply ? min(max(cy + half, 0), H) : y1;   // unapplied: empty
+    const int x1 = min(max(cx - half, 0), W), x2 = min(max(cx + half, 0), W);
+    const int area = (y2 - y1) * (x2 - x1);
+    const int64_t last = (int64_t)n_images * (C * H * W / 4) - 1;   // the dataset's last word
+
+    int xa[U], xb[U], sa[U], sb[U];
+    uint32_t loa[U], hia[U], lob[U], hib[U], msk[U];   // msk: bytes of the quad that lie inside the box
+    bool lda[U], ldb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW), yo = (r / QW) % H, q = r % QW;
+        uint32_t m = 0;
+        if (yo >= y1 && yo < y2) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m |= (4 * q + k >= x1 && 4 * q + k < x2) ? 0xffu << (8 * k) : 0u;
+        }
+        msk[u] = m;
+        const int ysa = yo + da.dy - pad, ysb = yo + db.dy - pad;
+        xa[u] = (da.flip ? W - 4 - 4 * q : 4 * q) + da.dx - pad;
+        xb[u] = (db.flip ? W - 4 - 4 * q : 4 * q) + db.dx - pad;
+        lda[u] = m != 0xffffffffu && (unsigned)ysa < (unsigned)H && xa[u] > -4 && xa[u] < W;
+        ldb[u] = m != 0u && (unsigned)ysb < (unsigned)H && xb[u] > -4 && xb[u] < W;
+        loa[u] = hia[u] = lob[u] = hib[u] = 0;
+        sa[u] = sb[u] = 0;
+        if (lda[u]) {
+            const int64_t a = (((int64_t)i * C + c) * H + ysa) * W + xa[u];    // byte address, may be < 0
+            const int64_t wi = a >> 2;
+            sa[u] = (int)(a & 3);
+            loa[u] = words[min(max(wi, (int64_t)0), last)];
+            hia[u] = words[min(max(wi + 1, (int64_t)0), last)];
+        }
+        if (ldb[u]) {
+            const int64_t a = (((int64_t)i2 * C + c) * H + ysb) * W + xb[u];
+            const int64_t wi = a >> 2;
+            sb[u] = (int)(a & 3);
+            lob[u] = words[min(max(wi, (int64_t)0), last)];
+            hib[u] = words[min(max(wi + 1, (int64_t)0), last)];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW);
+        const uint32_t wa = lda[u] ? quad_bytes(loa[u], hia[u], sa[u], xa[u], W, da.flip) : 0u;
+        const uint32_t wb = ldb[u] ? quad_bytes(lob[u], hib[u], sb[u], xb[u], W, db.flip) : 0u;
+        const uint32_t w = (wa & ~msk[u]) | (wb & msk[u]);
+        const float mean = c == 0 ? nrm.mean[0] : c == 1 ? nrm.mean[1] : nrm.mean[2];
+        const float stdv = c == 0 ? nrm.stdv[0] : c == 1 ? nrm.stdv[1] : nrm.stdv[2];
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float f = (float)((w >> (8 * k)) & 0xffu) / 255.0f;   // ToTensor
+            v[k] = (f - mean) / stdv;                                     // Normalize
+        }
+        x[(int64_t)s * QS + r] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    if (r0 == 0) {
+        const float wgt = (float)area / (float)(H * W);                   // IEEE division; 0 for an empty box
+        y[s] = area > 0 ? (int64_t)((uint64_t)la | ((uint64_t)lb << 8) | ((uint64_t)__float_as_uint(wgt) << 32)) : la;
+    }
+}
+
+template <int C, int H, int W, int U>
+static int image_batch_mix_launch(const uint8_t* images, const uint8_t* labels, int n_images, const int64_t* idx,
+                                  const int64_t* idx2, int B, const ImageNorm& nrm, int pad, int flip_enabled,
+                                  uint32_t seed, uint32_t epoch, uint64_t apply_below, float* x, int64_t* y,
+                                  int* err_flag, void* stream) {
+    const int64_t total = (int64_t)B * (C * H * (W / 4) / U);
+    SLK_CHECK_ARG((total + 255) / 256 <= 0x7fffffff);
+    image_batch_mix_kernel<C, H, W, U><<<(unsigned)((total + 255) / 256), 256, 0, slk_stream(stream)>>>(
+        reinterpret_cast<const uint32_t*>(images), labels, n_images, idx, idx2, B, nrm, pad, flip_enabled, seed, epoch,
+        apply_below, reinterpret_cast<float4*>(x), y, err_flag);
+    return slk_launch_status();
+}
+
+extern "C" int slk_image_batch_mix(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                                   const int64_t* idx, const int64_t* idx2, int B, const float* mean,
+                                   const float* stdv, int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                                   double prob, float* x, int64_t* y, int* err_flag, void* stream) {
+    const bool cifar = C == 3 && H == 32 && W == 32, mnist = C == 1 && H == 28 && W == 28;
+    SLK_CHECK_ARG(cifar || mnist);
+    SLK_CHECK_ARG(B >= 0 && n_images > 0 && pad >= 0 && pad <= IMAGE_MAX_PAD);
+    SLK_CHECK_ARG(prob >= 0.0 && prob <= 1.0);   // NaN fails both compares
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(images && labels && idx && idx2 && x && y && mean && stdv);
+    SLK_CHECK_ARG(((uintptr_t)images & 3) == 0 && ((uintptr_t)x & 15) == 0);
+    ImageNorm nrm = {};
+    for (int c = 0; c < C; ++c) {
+        nrm.mean[c] = mean[c];
+        nrm.stdv[c] = stdv[c];
+    }
+    const uint64_t apply_below = (uint64_t)(prob * 4294967296.0);   // apply iff h3 < prob * 2^32 (1.0: always)
+    if (cifar)
+        return image_batch_mix_launch<3, 32, 32, SLK_IMAGE_QUADS_CIFAR>(images, labels, n_images, idx, idx2, B, nrm, pad,
+                                                                      flip_enabled, seed, epoch, apply_below, x, y,
+                                                                      err_flag, stream);
+    return image_batch_mix_launch<1, 28, 28, SLK_IMAGE_QUADS_MNIST>(images, labels, n_images, idx, idx2, B, nrm, pad,
+                                                                  flip_enabled, seed, epoch, apply_below, x, y, err_flag,
+                                                                  stream);
 }

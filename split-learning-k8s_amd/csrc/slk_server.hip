@@ -507,6 +507,8 @@ extern "C" int slk_conv2_wgrad_direct_nslab(int B) { return B > 0 ? (2 * B < C2W
 // MODE bits: 1 = fc forward (logits), 2 = cross-entropy fwd+bwd, 4 = fc input gradient (dpooled =
 // dlogits @ W3, + dp_amax = per-sample max |dpooled| when asked), 8 = evaluation (with 1 only: loss_i and
 // pred = argmax from the logits just reduced, slk_eval_row; logits / labels may be null).
+// SOFT (with bit 2) swaps the hard-label cross-entropy for the soft-target one (mixed labels + label smoothing,
+// slk_soft_target / slk_soft_dot in slk_common.h); the hard-label instantiations compile to what they were.
 // Logits on v_mfma_f32_16x16x4_f32 (A = 16 samples x 4 features, B = 4 features x 16 classes, 10 used):
 // wave w owns features [1152 w, 1152 (w + 1)) and streams them in 18 chunks of 64 features — the 16
 // sample rows and W3's 10 rows of the chunk — by LDS-DMA into its own two slots (no barrier in the
@@ -547,13 +549,14 @@ __device__ __forceinline__ void fch_vmwait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int MODE>
+template <int MODE, bool SOFT = false>  // SOFT (with MODE bit 2): mixed labels + label smoothing (slk_*_soft)
 __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
     const float* __restrict__ pooled, const float* __restrict__ W3, const float* __restrict__ b3,
     const int64_t* __restrict__ labels, float* __restrict__ logits, float* __restrict__ loss_i,
     float* __restrict__ dlogits, float* __restrict__ dpooled, float grad_scale, int* err_flag, int B,
-    float* __restrict__ dp_amax, int64_t* __restrict__ pred = nullptr) {
+    float* __restrict__ dp_amax, int64_t* __restrict__ pred = nullptr, float smoothing = 0.f) {
     static_assert((MODE & 8) == 0 || MODE == 9, "evaluation mode = the logits stage + loss_i / pred, nothing else");
+    static_assert(!SOFT || (MODE & 2) != 0, "soft targets belong to the cross-entropy stage");
     __shared__ __attribute__((aligned(1024))) char smem[(MODE & 1) ? FCH_W * FCH_NS * FCH_SLOT : 16];
     __shared__ __attribute__((aligned(16))) f32x4 red[(MODE & 1) ? FCH_W * 64 : 1];
     __shared__ float zl[FCH_S][NCLS];
@@ -679,18 +682,31 @@ __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
             for (int jj = 0; jj < NCLS; ++jj) se += expf(z[jj] - m);
             const float lse = m + logf(se);
             const int64_t y = labels[s0 + s];
-            const bool ok = (y >= 0 && y < NCLS);
-            if (!ok && err_flag) atomicOr(err_flag, 1);
-            float yz = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < NCLS; ++jj) yz = (jj == y) ? z[jj] : yz;
             const float nanv = __builtin_nanf("");
-            loss_i[s0 + s] = ok ? (lse - yz) : nanv;
+            if constexpr (SOFT) {  // loss = lse - sum_j t_j z_j, dlogits = (softmax - t) * grad_scale (slk.h)
+                float t[NCLS];
+                const bool ok = slk_soft_target(y, smoothing, t);
+                if (!ok && err_flag) atomicOr(err_flag, 1);
+                loss_i[s0 + s] = ok ? (lse - slk_soft_dot(t, z)) : nanv;
 #pragma unroll
-            for (int jj = 0; jj < NCLS; ++jj) {
-                const float g = ok ? (expf(z[jj] - lse) - (jj == y ? 1.f : 0.f)) * grad_scale : nanv;
-                dl[s][jj] = g;
-                dlogits[(size_t)(s0 + s) * NCLS + jj] = g;
+                for (int jj = 0; jj < NCLS; ++jj) {
+                    const float g = ok ? (expf(z[jj] - lse) - t[jj]) * grad_scale : nanv;
+                    dl[s][jj] = g;
+                    dlogits[(size_t)(s0 + s) * NCLS + jj] = g;
+                }
+            } else {
+                const bool ok = (y >= 0 && y < NCLS);
+                if (!ok && err_flag) atomicOr(err_flag, 1);
+                float yz = 0.f;
+#pragma unroll
+                for (int jj = 0; jj < NCLS; ++jj) yz = (jj == y) ? z[jj] : yz;
+                loss_i[s0 + s] = ok ? (lse - yz) : nanv;
+#pragma unroll
+                for (int jj = 0; jj < NCLS; ++jj) {
+                    const float g = ok ? (expf(z[jj] - lse) - (jj == y ? 1.f : 0.f)) * grad_scale : nanv;
+                    dl[s][jj] = g;
+                    dlogits[(size_t)(s0 + s) * NCLS + jj] = g;
+                }
             }
         }
         __syncthreads();
@@ -926,6 +942,45 @@ extern "C" int slk_fc_xent_amax(const float* pooled, const float* W3, const floa
     SLK_CHECK_ARG(pooled && W3 && b3 && labels && logits && loss_i && dlogits && dpooled && dp_amax);
     fc_head16_kernel<7><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
         pooled, W3, b3, labels, logits, loss_i, dlogits, dpooled, grad_scale, err_flag, B, dp_amax);
+    return slk_launch_status();
+}
+
+// ---- the soft-target forms (mixed labels + label smoothing): the same kernel, SOFT = true
+#define SLK_CHECK_SMOOTHING(e) SLK_CHECK_ARG((e) >= 0.f && (e) <= 1.f)  // NaN fails both compares
+
+extern "C" int slk_xent_soft_fwd_bwd(const float* logits, const int64_t* labels, float* loss_i, float* dlogits,
+                                     float grad_scale, float smoothing, int* err_flag, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    SLK_CHECK_SMOOTHING(smoothing);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(logits && labels && loss_i && dlogits);
+    fc_head16_kernel<2, true><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
+        nullptr, nullptr, nullptr, labels, const_cast<float*>(logits), loss_i, dlogits, nullptr, grad_scale, err_flag, B,
+        nullptr, nullptr, smoothing);
+    return slk_launch_status();
+}
+
+extern "C" int slk_fc_logits_xent_soft(const float* pooled, const float* W3, const float* b3, const int64_t* labels,
+                                       float* logits, float* loss_i, float* dlogits, float grad_scale, float smoothing,
+                                       int* err_flag, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    SLK_CHECK_SMOOTHING(smoothing);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(pooled && W3 && b3 && labels && logits && loss_i && dlogits);
+    fc_head16_kernel<3, true><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
+        pooled, W3, b3, labels, logits, loss_i, dlogits, nullptr, grad_scale, err_flag, B, nullptr, nullptr, smoothing);
+    return slk_launch_status();
+}
+
+extern "C" int slk_fc_xent_soft(const float* pooled, const float* W3, const float* b3, const int64_t* labels,
+                                float* logits, float* loss_i, float* dlogits, float* dpooled, float* dp_amax,
+                                float grad_scale, float smoothing, int* err_flag, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    SLK_CHECK_SMOOTHING(smoothing);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(pooled && W3 && b3 && labels && logits && loss_i && dlogits && dpooled);
+    fc_head16_kernel<7, true><<<(B + FCH_S - 1) / FCH_S, FCH_T, 0, slk_stream(stream)>>>(
+        pooled, W3, b3, labels, logits, loss_i, dlogits, dpooled, grad_scale, err_flag, B, dp_amax, nullptr, smoothing);
     return slk_launch_status();
 }
 

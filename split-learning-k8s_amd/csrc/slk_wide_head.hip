@@ -114,13 +114,15 @@ constexpr int WH_KBS = NCH + 16;    // LDS row stride of the dropout bits (16 ro
 constexpr int WH_PF = SLK_WH_PF;    // blocks in flight per lane (cut + Wf registers)
 static_assert(NCH % WH_W == 0 && (WH_CPW / 4) % WH_PF == 0 && NCH % WH_T == 0, "head16 tiling");
 
-template <bool TRAIN>  // false: logits only (WideModelPartB.forward; labels .. dcut unused)
+// SOFT (with TRAIN): mixed labels + label smoothing (slk_wide_head_soft); `smoothing` is read by nothing else
+template <bool TRAIN, bool SOFT = false>  // TRAIN false: logits only (WideModelPartB.forward; labels .. dcut unused)
 __global__ __launch_bounds__(WH_T) void wide_head16_kernel(
     const uint16_t* __restrict__ cut, const float* __restrict__ wf8, const float* __restrict__ bf,
     const int64_t* __restrict__ labels, const int* __restrict__ step_ptr, uint32_t seed, uint32_t thresh,
     float keep_scale, float grad_scale, float* __restrict__ logits, float* __restrict__ loss_i,
     float* __restrict__ dlogits, uint16_t* __restrict__ dcut, uint8_t* __restrict__ kbits, int* __restrict__ err_flag,
-    int b0, int B) {
+    int b0, int B, float smoothing = 0.f) {
+    static_assert(!SOFT || TRAIN, "soft targets belong to the training head");
     __shared__ __attribute__((aligned(16))) uint8_t kbl[WH_S * WH_KBS];
     __shared__ __attribute__((aligned(16))) f32x4 red[WH_W * 64];
     __shared__ float zl[WH_S][NC];
@@ -200,16 +202,30 @@ __global__ __launch_bounds__(WH_T) void wide_head16_kernel(
             for (int j = 0; j < NC; ++j) se += expf(z[j] - m);
             const float lse = m + logf(se);
             const int64_t y = labels[b];
-            const bool ok = y >= 0 && y < NC;
-            if (!ok && err_flag) atomicOr(err_flag, 1);
+            if constexpr (SOFT) {  // loss = lse - sum_j t_j z_j, dlogits = (softmax - t) * grad_scale (slk.h)
+                float t[NC];
+                const bool ok = slk_soft_target(y, smoothing, t);
+                if (!ok && err_flag) atomicOr(err_flag, 1);
 #pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const float g = ok ? (expf(z[j] - lse) - (j == y ? 1.f : 0.f)) * grad_scale : __builtin_nanf("");
-                logits[(size_t)b * NC + j] = z[j];
-                dlogits[(size_t)b * NC + j] = g;
-                dls[s][j] = g;
+                for (int j = 0; j < NC; ++j) {
+                    const float g = ok ? (expf(z[j] - lse) - t[j]) * grad_scale : __builtin_nanf("");
+                    logits[(size_t)b * NC + j] = z[j];
+                    dlogits[(size_t)b * NC + j] = g;
+                    dls[s][j] = g;
+                }
+                loss_i[b] = ok ? lse - slk_soft_dot(t, z) : __builtin_nanf("");
+            } else {
+                const bool ok = y >= 0 && y < NC;
+                if (!ok && err_flag) atomicOr(err_flag, 1);
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    const float g = ok ? (expf(z[j] - lse) - (j == y ? 1.f : 0.f)) * grad_scale : __builtin_nanf("");
+                    logits[(size_t)b * NC + j] = z[j];
+                    dlogits[(size_t)b * NC + j] = g;
+                    dls[s][j] = g;
+                }
+                loss_i[b] = ok ? lse - z[(int)y] : __builtin_nanf("");
             }
-            loss_i[b] = ok ? lse - z[(int)y] : __builtin_nanf("");
         }
     }
     __syncthreads();
@@ -595,7 +611,25 @@ extern "C" int slk_wide_head(const uint16_t* cut, const float* wf8, const float*
     hipStream_t st = slk_stream(stream);
     hipLaunchKernelGGL(wide_head16_kernel<true>, dim3((B + WH_S - 1) / WH_S), dim3(WH_T), 0, st, cut, wf8, bf, labels, step, seed,
                        keep_threshold, keep_scale, grad_scale, logits, loss_i, dlogits, dcut, (uint8_t*)work, err_flag,
-                       b0, B);
+                       b0, B, 0.f);
+    hipLaunchKernelGGL(wide_head_back_kernel<false>, dim3(HSLICE * ng), dim3(256), 0, st, cut, wf8, dlogits, step, seed,
+                       keep_threshold, keep_scale, dcut, slabs, (const uint8_t*)work, b0, B);
+    return slk_launch_status();
+}
+extern "C" int slk_wide_head_soft(const uint16_t* cut, const float* wf8, const float* bf, const int64_t* labels,
+                                  const int* step, unsigned seed, unsigned keep_threshold, float keep_scale,
+                                  float grad_scale, float smoothing, float* logits, float* loss_i, float* dlogits,
+                                  uint16_t* dcut, float* slabs, float* work, int* err_flag, int b0, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0 && b0 >= 0 && cut && wf8 && bf && labels && step && logits && loss_i && dlogits && dcut &&
+                  slabs && work);
+    SLK_CHECK_ARG(((uintptr_t)work & 15) == 0);
+    SLK_CHECK_ARG(smoothing >= 0.f && smoothing <= 1.f);  // NaN fails both compares
+    if (B == 0) return 0;
+    const int ng = slk_wide_head_nslab(B);
+    hipStream_t st = slk_stream(stream);
+    hipLaunchKernelGGL((wide_head16_kernel<true, true>), dim3((B + WH_S - 1) / WH_S), dim3(WH_T), 0, st, cut, wf8, bf, labels,
+                       step, seed, keep_threshold, keep_scale, grad_scale, logits, loss_i, dlogits, dcut, (uint8_t*)work,
+                       err_flag, b0, B, smoothing);
     hipLaunchKernelGGL(wide_head_back_kernel<false>, dim3(HSLICE * ng), dim3(256), 0, st, cut, wf8, dlogits, step, seed,
                        keep_threshold, keep_scale, dcut, slabs, (const uint8_t*)work, b0, B);
     return slk_launch_status();
@@ -607,7 +641,7 @@ extern "C" int slk_wide_head_fwd(const uint16_t* cut, const float* wf8, const fl
     if (B == 0) return 0;
     hipStream_t st = slk_stream(stream);
     hipLaunchKernelGGL(wide_head16_kernel<false>, dim3((B + WH_S - 1) / WH_S), dim3(WH_T), 0, st, cut, wf8, bf, nullptr, step,
-                       seed, keep_threshold, keep_scale, 0.f, logits, nullptr, nullptr, nullptr, nullptr, nullptr, b0, B);
+                       seed, keep_threshold, keep_scale, 0.f, logits, nullptr, nullptr, nullptr, nullptr, nullptr, b0, B, 0.f);
     return slk_launch_status();
 }
 

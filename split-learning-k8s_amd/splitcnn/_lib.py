@@ -51,6 +51,13 @@ _SIGS = {
     "slk_fc_dgrad_amax": [_P, _P, _P, _P, _I, _P],
     "slk_fc_xent": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _P],
     "slk_fc_xent_amax": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _P],
+    # soft targets (splitcnn.loss): `smoothing` by value after grad_scale
+    "slk_xent_soft_fwd_bwd": [_P, _P, _P, _P, _F, _F, _P, _I, _P],
+    "slk_fc_logits_xent_soft": [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _P],
+    "slk_fc_xent_soft": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _P],
+    "slk_wide_head_soft": [_P, _P, _P, _P, _P, _U, _U, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "slk_image_batch_mix": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _U, _U, ctypes.c_double, _P, _P, _P,
+                            _P],
     "slk_fc_wgrad": [_P, _P, _P, _I, _P],
     "slk_fc_wgrad_nslab": [_I],
     "slk_conv2_dgrad": [_P, _P, _P, _P, _I, _P],

@@ -174,16 +174,19 @@ class CifarLoader(ResidentLoader):
     """ResidentLoader over CifarBin (any dataset with u8 `images` [N,3,32,32] and `labels` [N]): x f32
     [B,3,32,32] and y i64 [B] by one slk_image_batch launch per batch, eagerly, so every batch sees the
     loader's current `epoch`. `augment=None` (use it for the test split) is no crop and no flip: gather +
-    ToTensor + Normalize(mean, std)."""
+    ToTensor + Normalize(mean, std). `mix=CutMix(...)` (splitcnn.loss) pastes a box of the previous sample of the
+    batch into each sample in the same launch (slk_image_batch_mix) and yields mixed labels."""
 
     sample_shape = (3, 32, 32)
 
     def __init__(self, dataset, batch_size: int = 64, shuffle: bool = True, seed: Optional[int] = None,
                  device="cuda", drop_last: bool = False, augment: Optional[Augment] = None, mean=CIFAR_MEAN,
-                 std=CIFAR_STD):
-        super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment)
+                 std=CIFAR_STD, mix=None):
+        super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment, mix)
         self.mean, self.std = tuple(mean), tuple(std)
 
     def _batch(self, idx, x, y):
+        if self.mix is not None:
+            return self._mix_batch(idx, x, y, self.mean, self.std)
         return ops.image_batch(self.images, self.labels, idx, mean=self.mean, std=self.std, x=x, y=y,
                                err_flag=self.err, **self._augment_args())

@@ -103,6 +103,9 @@ def _default_optimizer_only(who: str, *stages) -> None:
     a stage built with an optimizer config, a schedule or gradient clipping (splitcnn.optim) instead of
     ignoring it."""
     for st in stages:
+        if getattr(st, "loss", None) is not None:
+            raise ValueError(f"dist.{who}: {type(st).__name__} carries a soft-target loss (splitcnn.loss); the "
+                             "multi-GPU classes run the hard-label heads only — build the stage without loss=")
         if any(getattr(st, a, None) is not None for a in ("optim", "schedule", "clip")):
             raise ValueError(f"dist.{who}: {type(st).__name__} carries an optimizer config / learning-rate schedule "
                              "/ gradient clipping (splitcnn.optim); the multi-GPU classes take only the default "

@@ -29,6 +29,7 @@ import torch.nn as nn
 
 from . import ops
 from .graphs import GraphedTrainer
+from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .model_def import ModelPartA, ModelPartB
 from .optim import SGD, ClipNorm, LRSchedule, check_clip
 
@@ -358,8 +359,11 @@ class ServerStage(_SgdRecipe):
     def __init__(self, model: Optional[ModelPartB] = None, lr: float = LR, device="cuda",
                  loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT,
                  optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None):
+                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None):
         self.device = torch.device(device)
+        # loss=SoftCrossEntropy(eps): every head path below calls its soft entry (mixed labels + label smoothing,
+        # splitcnn.loss); eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
+        self.loss = check_loss(loss)
         self.conv = conv
         self.impl_fwd, self.impl_dgrad, self.impl_wgrad = CONV_PRESETS[conv]
         self.share_images = True  # x3: the forward's split input images feed the wgrad (act16)
@@ -437,16 +441,26 @@ class ServerStage(_SgdRecipe):
                 pooled, code = ops.conv2_fwd_pool(act, W2, b2, pooled=pooled_b, code=code_b, impl=fi,
                                                   act_amax=act_amax, act16=act16)
         split = self.fc_split and dp_amax is not None
+        soft = None if self.loss is None else float(self.loss.label_smoothing)
         if split:
             with TIMER("fc_xent"):
-                if self.fc_one_launch:
+                if self.fc_one_launch and soft is None:
                     _, loss_i, dlogits = ops.fc_logits_xent(
                         pooled, W3, b3, labels, grad_scale, logits=self._b("logits", (B, 10)),
                         loss_i=self._b("loss_i", (B,)), dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
+                elif self.fc_one_launch:
+                    _, loss_i, dlogits = ops.fc_logits_xent_soft(
+                        pooled, W3, b3, labels, grad_scale, soft, logits=self._b("logits", (B, 10)),
+                        loss_i=self._b("loss_i", (B,)), dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
                 else:
                     logits = ops.fc_fwd(pooled, W3, b3, out=self._b("logits", (B, 10)))
-                    loss_i, dlogits = ops.xent_fwd_bwd(logits, labels, grad_scale, loss_i=self._b("loss_i", (B,)),
-                                                       dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
+                    if soft is None:
+                        loss_i, dlogits = ops.xent_fwd_bwd(logits, labels, grad_scale, loss_i=self._b("loss_i", (B,)),
+                                                           dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
+                    else:
+                        loss_i, dlogits = ops.xent_soft_fwd_bwd(
+                            logits, labels, grad_scale, soft, loss_i=self._b("loss_i", (B,)),
+                            dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
             with TIMER("fc_wgrad"):
                 s3 = ops.fc_wgrad_slabs(dlogits, pooled, slabs=self._b("s3", (ops.fc_wgrad_nslab(B), ops.FC_SLAB)))
             dpooled = self._b("dpooled", (B, 64, 12, 12))
@@ -454,10 +468,16 @@ class ServerStage(_SgdRecipe):
                 ops.fc_dgrad(dlogits, W3, out=dpooled.view(B, 9216), dp_amax=dp_amax)
         else:
             with TIMER("fc_xent"):
-                _, loss_i, dlogits, dpooled = ops.fc_xent(
-                    pooled, W3, b3, labels, grad_scale, logits=self._b("logits", (B, 10)),
-                    loss_i=self._b("loss_i", (B,)), dlogits=self._b("dlogits", (B, 10)),
-                    dpooled=self._b("dpooled", (B, 64, 12, 12)), err_flag=self.err_flag, dp_amax=dp_amax)
+                if soft is None:
+                    _, loss_i, dlogits, dpooled = ops.fc_xent(
+                        pooled, W3, b3, labels, grad_scale, logits=self._b("logits", (B, 10)),
+                        loss_i=self._b("loss_i", (B,)), dlogits=self._b("dlogits", (B, 10)),
+                        dpooled=self._b("dpooled", (B, 64, 12, 12)), err_flag=self.err_flag, dp_amax=dp_amax)
+                else:
+                    _, loss_i, dlogits, dpooled = ops.fc_xent_soft(
+                        pooled, W3, b3, labels, grad_scale, soft, logits=self._b("logits", (B, 10)),
+                        loss_i=self._b("loss_i", (B,)), dlogits=self._b("dlogits", (B, 10)),
+                        dpooled=self._b("dpooled", (B, 64, 12, 12)), err_flag=self.err_flag, dp_amax=dp_amax)
         # launch order dgrad -> wgrad -> fc wgrad (measured fastest: DESIGN.md §3a "Launch order")
         if self.fc_wgrad_early and not split:
             with TIMER("fc_wgrad"):
@@ -574,9 +594,10 @@ class ServerStage(_SgdRecipe):
         return cut_grad, loss_i
 
     def check_labels(self):
-        """Raise if any label seen so far was outside [0, 10) (torch raises IndexError there)."""
+        """Raise if any label seen so far was outside [0, 10) (torch raises IndexError there) or, with loss=, any
+        target was malformed (splitcnn.loss)."""
         if int(self.err_flag.item()) != 0:
-            raise IndexError("splitcnn: a label was out of range [0, 10)")
+            raise IndexError(LABEL_ERROR)
 
     def evaluate(self, act: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, *,
                  act16: Optional[torch.Tensor] = None, act_amax: Optional[torch.Tensor] = None,
@@ -640,7 +661,9 @@ class SplitTrainer(GraphedTrainer):
     stage's `lr` attribute after the first step does not reach a captured graph (use a schedule and
     LRSchedule.set_lr). `clip` (optim.ClipNorm, shared by both stages; selects the configured kernels like a
     schedule) clips each stage's gradient by that stage's own global norm before its update; grad_norms()
-    reads the last step's norms."""
+    reads the last step's norms. `loss` (loss.SoftCrossEntropy) makes the server's head take mixed labels with label
+    smoothing; the smoothing is a by-value constant of the launch, kept by a captured graph, with no setter.
+    Evaluation stays the plain cross-entropy on plain labels."""
 
     input_shape = (1, 28, 28)
 
@@ -648,12 +671,12 @@ class SplitTrainer(GraphedTrainer):
                  lr: float = LR, device="cuda", graph: bool = True, loss_log: Optional[LossLog] = None,
                  conv: str = CONV_DEFAULT, act16: bool = True, fuse_client_backward: bool = True,
                  graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None):
+                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None):
         check_clip(clip)
         super().__init__(device, graph, graph_inputs)
         self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule, clip=clip)
         self.server = ServerStage(server, lr, self.device, loss_log, conv=conv, optim=self.client.optim,
-                                  schedule=self.client.schedule, clip=self.client.clip)
+                                  schedule=self.client.schedule, clip=self.client.clip, loss=loss)
         if self.server.optim is not None:
             self.client.step_ctr = self.server.step_ctr
             self.client.auto_tick = self.server.auto_tick = False   # _eager ticks the shared counter

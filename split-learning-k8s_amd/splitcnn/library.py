@@ -13,8 +13,10 @@ The ops and the reference calls they replace (src/model_def.py, src/server_part.
   conv2_relu_pool(act, W2, b2) -> (pooled, code, amax, act16) model_def.py:25-26 (x3 kernels by default)
   linear(flat, W3, b3) -> logits                            fc1 (model_def.py:22,28)
   cross_entropy(logits, labels) -> loss                     nn.CrossEntropyLoss() (server_part.py:16,49)
+  cross_entropy_soft(logits, labels, label_smoothing) -> loss   nn.CrossEntropyLoss(label_smoothing=...) on plain or
+                                                            mixed labels (splitcnn.loss)
 and their backward helpers conv1_wgrad, row_amax, conv2_dgrad(_x3), conv2_wgrad(_x3), linear_dgrad,
-linear_wgrad, cross_entropy_grad.
+linear_wgrad, cross_entropy_grad, cross_entropy_soft_grad.
 """
 from __future__ import annotations
 
@@ -365,6 +367,50 @@ def _xent_backward(ctx, gloss, K=None):
 cross_entropy.register_autograd(_xent_backward, setup_context=_xent_setup)
 
 
+# ----------------------------------------------------------------------------------- soft cross-entropy
+# nn.CrossEntropyLoss(label_smoothing=eps) on mixed labels (splitcnn.loss: two classes and a weight in one int64),
+# mean reduction: slk_xent_soft_fwd_bwd. The backward recomputes dlogits from the saved logits and labels (one
+# thread per sample over ten classes); a malformed target gives a NaN loss, as an out-of-range label does above.
+@torch.library.custom_op(f"{_NS}::cross_entropy_soft", mutates_args=())
+def cross_entropy_soft(logits: Tensor, labels: Tensor, label_smoothing: float) -> Tensor:
+    """Mean soft-target cross-entropy as a 0-d tensor."""
+    logits, labels = logits.contiguous(), labels.contiguous()
+    loss_i, _ = ops.xent_soft_fwd_bwd(logits, labels, 1.0 / logits.shape[0], label_smoothing)
+    return ops.loss_mean(loss_i).view(())
+
+
+@cross_entropy_soft.register_fake
+def _(logits, labels, label_smoothing):
+    return logits.new_empty(())
+
+
+@torch.library.custom_op(f"{_NS}::cross_entropy_soft_grad", mutates_args=())
+def cross_entropy_soft_grad(logits: Tensor, labels: Tensor, label_smoothing: float, gloss: Tensor) -> Tensor:
+    """d loss / d logits = (softmax - t) / B * gloss."""
+    logits, labels = logits.contiguous(), labels.contiguous()
+    _, dlogits = ops.xent_soft_fwd_bwd(logits, labels, 1.0 / logits.shape[0], label_smoothing)
+    return dlogits * gloss
+
+
+@cross_entropy_soft_grad.register_fake
+def _(logits, labels, label_smoothing, gloss):
+    return torch.empty_like(logits)
+
+
+def _xent_soft_setup(ctx, inputs, output):
+    logits, labels, ctx.label_smoothing = inputs
+    ctx.save_for_backward(logits, labels)
+
+
+def _xent_soft_backward(ctx, gloss, K=None):
+    K = K or torch.ops.splitcnn
+    logits, labels = ctx.saved_tensors
+    return K.cross_entropy_soft_grad(logits, labels, ctx.label_smoothing, gloss), None, None
+
+
+cross_entropy_soft.register_autograd(_xent_soft_backward, setup_context=_xent_soft_setup)
+
+
 # ----------------------------------------------------------------------------------- eager fast path
 # The same implementations and backward formulas as the ops above, as plain autograd.Functions, for eager
 # calls on real tensors (the reference's own step code on the drop-in modules): a torch.library custom-op
@@ -378,7 +424,7 @@ class _Direct:
 
 
 for _n in ("conv1_wgrad", "row_amax", "conv2_dgrad", "conv2_dgrad_x3", "conv2_wgrad", "conv2_wgrad_x3",
-           "linear_dgrad", "linear_wgrad", "cross_entropy_grad"):
+           "linear_dgrad", "linear_wgrad", "cross_entropy_grad", "cross_entropy_soft_grad"):
     setattr(_Direct, _n, staticmethod(globals()[_n]._init_fn))
 _EAGER = os.environ.get("SLK_EAGER_OPS", "1") != "0"
 
@@ -436,3 +482,15 @@ class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         return _xent_backward(ctx, gloss, _Direct)
+
+
+class CrossEntropySoftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, label_smoothing):
+        out = cross_entropy_soft._init_fn(logits, labels, label_smoothing)
+        _xent_soft_setup(ctx, (logits, labels, label_smoothing), out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gloss):
+        return _xent_soft_backward(ctx, gloss, _Direct)

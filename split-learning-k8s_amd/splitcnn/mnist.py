@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .loss import CutMix
 
 _FILES = {True: ("train-images-idx3-ubyte", "train-labels-idx1-ubyte"),
           False: ("t10k-images-idx3-ubyte", "t10k-labels-idx1-ubyte")}
@@ -84,17 +85,25 @@ class ResidentLoader:
     the reference's (drop_last=False). Batches are written into two alternating device buffer pairs per
     batch size, the same ones in every epoch (a GraphedTrainer gives each a graph of its own), so a consumer
     must finish with a batch before asking for the one after next. `epoch` counts the completed passes (the
-    augmentation draws are keyed on it; set_epoch(n) sets it); `err` is set by an out-of-range index."""
+    augmentation draws are keyed on it; set_epoch(n) sets it); `err` is set by an out-of-range index.
+
+    `mix` (loss.CutMix) makes each batch one slk_image_batch_mix launch: sample s of a batch gets a box of its
+    partner idx.roll(1)[s] (the previous sample of the same batch, the ragged last one rolling within itself; the
+    permutation is already random, so no second one is drawn), and y holds mixed labels for a trainer built with
+    loss=SoftCrossEntropy(...). Without `augment` the crop and flip are off (pad 0) and mix.seed keys the boxes."""
 
     sample_shape: tuple = ()
 
     def __init__(self, dataset, batch_size: int = 64, shuffle: bool = True, seed: Optional[int] = None,
-                 device="cuda", drop_last: bool = False, augment=None):
+                 device="cuda", drop_last: bool = False, augment=None, mix=None):
         self.device = torch.device(device)
         self.batch_size = int(batch_size)
         self.shuffle = shuffle
         self.drop_last = drop_last
         self.augment = augment
+        if mix is not None and not isinstance(mix, CutMix):
+            raise TypeError(f"mix: expected splitcnn.loss.CutMix or None, got {type(mix).__name__}")
+        self.mix = mix
         self.epoch = 0
         self.gen = torch.Generator()
         if seed is not None:
@@ -128,8 +137,15 @@ class ResidentLoader:
     def _augment_args(self) -> dict:
         a = self.augment
         if a is None:
+            if self.mix is not None:   # the boxes are keyed on (index, epoch, seed) like a crop would be
+                return dict(pad=0, flip=False, seed=self.mix.seed, epoch=self.epoch)
             return dict(pad=0, flip=False, seed=0, epoch=0)
         return dict(pad=a.pad, flip=a.flip, seed=a.seed, epoch=self.epoch)
+
+    def _mix_batch(self, idx, x, y, mean, std):
+        """One slk_image_batch_mix launch: partners are the batch rolled by one."""
+        return ops.image_batch_mix(self.images, self.labels, idx, idx.roll(1), mean=mean, std=std, prob=self.mix.prob,
+                                   x=x, y=y, err_flag=self.err, **self._augment_args())
 
     def _batch(self, idx, x, y):
         raise NotImplementedError
@@ -148,15 +164,18 @@ class ResidentLoader:
 class DeviceLoader(ResidentLoader):
     """ResidentLoader over MnistIDX: x f32 [B,1,28,28] by one slk_mnist_batch launch per batch. With
     `augment` (cifar.Augment, e.g. Augment(pad=2, flip=False)) the batch comes from slk_image_batch<1,28,28>
-    instead: RandomCrop(28, padding=pad) (+ flip) before the same ToTensor + Normalize."""
+    instead: RandomCrop(28, padding=pad) (+ flip) before the same ToTensor + Normalize. With `mix` (loss.CutMix)
+    every batch is one slk_image_batch_mix<1,28,28> launch, with or without `augment`."""
 
     sample_shape = (1, 28, 28)
 
     def __init__(self, dataset: MnistIDX, batch_size: int = 64, shuffle: bool = True,
-                 seed: Optional[int] = None, device="cuda", drop_last: bool = False, augment=None):
-        super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment)
+                 seed: Optional[int] = None, device="cuda", drop_last: bool = False, augment=None, mix=None):
+        super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment, mix)
 
     def _batch(self, idx, x, y):
+        if self.mix is not None:   # slk_image_batch_mix<1,28,28>, with or without augment
+            return self._mix_batch(idx, x, y, (ops.MNIST_MEAN,), (ops.MNIST_STD,))
         if self.augment is None:
             return ops.mnist_batch(self.images, self.labels, idx, x=x, y=y, err_flag=self.err)
         return ops.image_batch(self.images, self.labels, idx, mean=(ops.MNIST_MEAN,), std=(ops.MNIST_STD,), x=x,

@@ -29,7 +29,8 @@ from . import ops
 # registrations with fake kernels and autograd formulas over libslk.so), so the modules trace under
 # torch.export / make_fx as opaque differentiable operators.
 from . import library  # noqa: E402,F401  (registers torch.ops.splitcnn.*)
-from .library import Conv1ReluFn, Conv2ReluPoolFn, CrossEntropyFn, LinearFn, eager  # noqa: E402
+from .library import (Conv1ReluFn, Conv2ReluPoolFn, CrossEntropyFn, CrossEntropySoftFn, LinearFn,  # noqa: E402
+                      eager)
 
 _OPS = torch.ops.splitcnn
 
@@ -106,11 +107,26 @@ class FullModel(nn.Module):
 
 
 class CrossEntropyLoss(nn.Module):
-    """Drop-in for nn.CrossEntropyLoss() as the reference uses it (mean, integer class labels)."""
+    """Drop-in for nn.CrossEntropyLoss() as the reference uses it (mean, integer class labels), and for
+    nn.CrossEntropyLoss(label_smoothing=eps) on plain or mixed labels (splitcnn.loss.pack_mixed, what a loader with
+    mix=CutMix(...) yields). With the defaults the call is exactly the hard-label one (splitcnn::cross_entropy); with
+    label_smoothing > 0, or mixed=True, it is splitcnn::cross_entropy_soft (slk_xent_soft_fwd_bwd). Which of the two
+    runs is decided by the constructor, never by looking at the labels (that would cost a host sync per call): a mixed
+    label fed to the hard-label form gives a NaN loss. Mean reduction only."""
+
+    def __init__(self, label_smoothing: float = 0.0, mixed: bool = False):
+        super().__init__()
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"CrossEntropyLoss: label_smoothing must be in [0, 1], got {label_smoothing}")
+        self.label_smoothing, self.mixed = float(label_smoothing), bool(mixed)
 
     def forward(self, logits, labels):
         _require_device(logits, "CrossEntropyLoss")
-        return CrossEntropyFn.apply(logits, labels) if eager(logits, labels) else _OPS.cross_entropy(logits, labels)
+        if self.label_smoothing == 0.0 and not self.mixed:
+            return CrossEntropyFn.apply(logits, labels) if eager(logits, labels) else _OPS.cross_entropy(logits, labels)
+        if eager(logits, labels):
+            return CrossEntropySoftFn.apply(logits, labels, self.label_smoothing)
+        return _OPS.cross_entropy_soft(logits, labels, self.label_smoothing)
 
 
 def get_model(role="client"):

@@ -353,6 +353,50 @@ def fc_xent(pooled, W3, b3, labels, grad_scale, logits=None, loss_i=None, dlogit
     return logits, loss_i, dlogits, dpooled
 
 
+# ---- soft targets (splitcnn.loss): mixed labels + label smoothing, the soft forms of the entries above
+def xent_soft_fwd_bwd(logits, labels, grad_scale, smoothing, loss_i=None, dlogits=None, err_flag=None):
+    """xent_fwd_bwd on mixed labels with label smoothing (slk_xent_soft_fwd_bwd); smoothing 0 on plain labels is
+    bitwise xent_fwd_bwd. A malformed target sets err_flag and writes NaN for its row."""
+    B = batch_of(logits, (10,), "logits")
+    loss_i = _out(loss_i, (B,), logits, name="loss_i")
+    dlogits = _out(dlogits, (B, 10), logits, name="dlogits")
+    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    _lib.call("slk_xent_soft_fwd_bwd", _dev(logits, "logits"), _labels(labels, B), _dev(loss_i, "loss_i"),
+              _dev(dlogits, "dlogits"), float(grad_scale), float(smoothing), eptr, B, _stream(logits))
+    return loss_i, dlogits
+
+
+def fc_logits_xent_soft(pooled, W3, b3, labels, grad_scale, smoothing, logits=None, loss_i=None, dlogits=None,
+                        err_flag=None):
+    """fc_logits_xent on mixed labels with label smoothing in one launch (slk_fc_logits_xent_soft)."""
+    B = _pooled_batch(pooled)
+    logits = _out(logits, (B, 10), pooled, name="logits")
+    loss_i = _out(loss_i, (B,), pooled, name="loss_i")
+    dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
+    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    _lib.call("slk_fc_logits_xent_soft", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
+              _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"), _dev(loss_i, "loss_i"),
+              _dev(dlogits, "dlogits"), float(grad_scale), float(smoothing), eptr, B, _stream(pooled))
+    return logits, loss_i, dlogits
+
+
+def fc_xent_soft(pooled, W3, b3, labels, grad_scale, smoothing, logits=None, loss_i=None, dlogits=None,
+                 dpooled=None, err_flag=None, dp_amax=None):
+    """fc_xent on mixed labels with label smoothing (slk_fc_xent_soft); dp_amax as in fc_xent."""
+    B = _pooled_batch(pooled)
+    logits = _out(logits, (B, 10), pooled, name="logits")
+    loss_i = _out(loss_i, (B,), pooled, name="loss_i")
+    dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
+    dpooled = _out(dpooled, tuple(pooled.shape), pooled, name="dpooled")
+    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    _lib.call("slk_fc_xent_soft", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
+              _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"), _dev(loss_i, "loss_i"),
+              _dev(dlogits, "dlogits"), _dev(dpooled, "dpooled"),
+              _dev(dp_amax, "dp_amax", (B,)) if dp_amax is not None else None, float(grad_scale), float(smoothing),
+              eptr, B, _stream(pooled))
+    return logits, loss_i, dlogits, dpooled
+
+
 def fc_wgrad_nslab(B: int) -> int:
     return _lib.query("slk_fc_wgrad_nslab", B)
 
@@ -798,3 +842,46 @@ def image_batch(images, labels, idx, *, mean, std, pad=0, flip=False, seed=0, ep
               int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, x.data_ptr(), y.data_ptr(),
               None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
     return x, y
+
+
+def image_batch_mix(images, labels, idx, idx2, *, mean, std, prob=1.0, pad=0, flip=False, seed=0, epoch=0, x=None,
+                    y=None, err_flag=None):
+    """image_batch with CutMix (slk_image_batch_mix): batch position s shows row idx[s] with a box of row idx2[s]
+    pasted in, each under its own crop and flip; y holds mixed labels (splitcnn.loss.unpack_mixed). The box is keyed
+    on (idx[s], epoch, seed) and applied with probability `prob` (loss.cutmix_draws is the host twin). prob=0 is
+    bitwise image_batch."""
+    if images.dim() == 3:
+        images = images.unsqueeze(1)
+    if images.dim() != 4:
+        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
+    n, C, H, W = (int(d) for d in images.shape)
+    if labels.shape != (n,):
+        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C:
+        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
+    B = int(idx.shape[0])
+    x = _out(x, (B, C, H, W), images, name="x")
+    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    _lib.call("slk_image_batch_mix", _dev(images, "images", dtype=torch.uint8),
+              _dev(labels, "labels", dtype=torch.uint8), n, C, H, W, _dev(idx, "idx", (B,), torch.int64),
+              _dev(idx2, "idx2", (B,), torch.int64), B, (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std),
+              int(pad), int(bool(flip)), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, float(prob), x.data_ptr(),
+              y.data_ptr(), None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+    return x, y
+
+
+# ------------------------------------------------------------------------------------ widened head, soft targets
+def wide_head_soft(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale, grad_scale, smoothing, logits,
+                   loss_i, dlogits, dcut, slabs, work, err_flag=None, b0=0):
+    """slk_wide_head on mixed labels with label smoothing (slk_wide_head_soft): every buffer is the caller's (the
+    shapes of wide.WideServerStage.forward_backward). Returns (dcut, loss_i, slabs)."""
+    B = int(cut.shape[0])
+    _lib.call("slk_wide_head_soft", _dev(cut, "cut", dtype=torch.bfloat16), _dev(wf8, "wf8", (163840,)),
+              _dev(bf, "fc.bias", (10,)), _labels(labels, B), _dev(step, "step", (1,), torch.int32),
+              int(seed) & 0xFFFFFFFF, int(keep_threshold) & 0xFFFFFFFF, float(keep_scale), float(grad_scale),
+              float(smoothing), _dev(logits, "logits", (B, 10)), _dev(loss_i, "loss_i", (B,)),
+              _dev(dlogits, "dlogits", (B, 10)), _dev(dcut, "dcut", tuple(cut.shape), torch.bfloat16),
+              _dev(slabs, "slabs"), _dev(work, "work"),
+              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), int(b0), B, _stream(cut))
+    return dcut, loss_i, slabs

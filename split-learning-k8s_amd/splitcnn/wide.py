@@ -35,6 +35,7 @@ from . import _lib
 from . import ops
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
+from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
 from .optim import Adam, ClipNorm, LRSchedule, check_clip
 
@@ -519,8 +520,12 @@ class WideServerStage(_AdamRecipe):
 
     def __init__(self, model: Optional[WideModelPartB] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None, optim: Optional[Adam] = None,
-                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None):
+                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
+                 loss: Optional[SoftCrossEntropy] = None):
         self.device = torch.device(device)
+        # loss=SoftCrossEntropy(eps): the head is slk_wide_head_soft (mixed labels + label smoothing, splitcnn.loss);
+        # eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
+        self.loss = check_loss(loss)
         self.model = (model if model is not None else WideModelPartB()).to(self.device)
         self.params, self.grads = _flat([self.model.fc.weight, self.model.fc.bias], self.device)
         assert self.params.numel() == SERVER_NPARAM
@@ -578,10 +583,16 @@ class WideServerStage(_AdamRecipe):
         _dev(dcut, "dcut", (B,) + CUT_SHAPE, _BF)
         sf = self._b("sf", (_q("slk_wide_head_nslab", B), SERVER_NPARAM), _F32)
         work = self._b("work", (_q("slk_wide_head_work", B),), _F32)
-        _k("wide_head", cut.data_ptr(), self.wf8.data_ptr(), self.params[163840:].data_ptr(),
-           labels.data_ptr(), self.step_ctr.data_ptr(), self.seed, KEEP_THRESHOLD, KEEP_SCALE,
-           float(grad_scale), logits.data_ptr(), loss_i.data_ptr(), dlogits.data_ptr(), dcut.data_ptr(),
-           sf.data_ptr(), work.data_ptr(), self.err_flag.data_ptr(), int(b0), B, s)
+        if self.loss is None:
+            _k("wide_head", cut.data_ptr(), self.wf8.data_ptr(), self.params[163840:].data_ptr(),
+               labels.data_ptr(), self.step_ctr.data_ptr(), self.seed, KEEP_THRESHOLD, KEEP_SCALE,
+               float(grad_scale), logits.data_ptr(), loss_i.data_ptr(), dlogits.data_ptr(), dcut.data_ptr(),
+               sf.data_ptr(), work.data_ptr(), self.err_flag.data_ptr(), int(b0), B, s)
+        else:
+            with TIMER("wide_head"):
+                ops.wide_head_soft(cut, self.wf8, self.params[163840:], labels, self.step_ctr, self.seed,
+                                   KEEP_THRESHOLD, KEEP_SCALE, grad_scale, self.loss.label_smoothing, logits, loss_i,
+                                   dlogits, dcut, sf, work, err_flag=self.err_flag, b0=b0)
         self._logits, self._dlogits = logits, dlogits
         return dcut, loss_i, sf
 
@@ -614,8 +625,9 @@ class WideServerStage(_AdamRecipe):
         return dcut, loss_i
 
     def check_labels(self):
+        """Raise if any label seen so far was outside [0, 10) or, with loss=, any target was malformed."""
         if int(self.err_flag.item()) != 0:
-            raise IndexError("splitcnn: a label was out of range [0, 10)")
+            raise IndexError(LABEL_ERROR)
 
     # --- micro-batched / multi-client steps (dist.WideHub): accumulate, then one Adam step
     def accumulate(self, cut, labels, grad_scale: float, b0: int, k: int, nparts: int, dcut=None):
@@ -660,18 +672,21 @@ class WideTrainer(GraphedTrainer):
     seeds the dropout mask), so the captured graph follows the schedule. Without them `lr` is a by-value
     kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it). `clip`
     (optim.ClipNorm, shared by both stages) clips each stage's gradient by that stage's own global norm before
-    its Adam update; grad_norms() reads the last step's norms."""
+    its Adam update; grad_norms() reads the last step's norms. `loss` (loss.SoftCrossEntropy) makes the head take
+    mixed labels (loss.CutMix in the loader) with label smoothing, a by-value constant a captured graph keeps (no
+    setter); evaluation stays the plain cross-entropy on plain labels."""
 
     input_shape = (3, 32, 32)
 
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
-                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None):
+                 schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
+                 loss: Optional[SoftCrossEntropy] = None):
         check_clip(clip)
         super().__init__(device, graph)
         self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
-                                      schedule=self.client.schedule, clip=self.client.clip)
+                                      schedule=self.client.schedule, clip=self.client.clip, loss=loss)
 
     def _eager(self, x, y):
         c = self.client
