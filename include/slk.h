@@ -644,6 +644,70 @@ int slk_adamw_clip_multi(float* const* params, const float* const* grads, float*
                          float* const* norm_out, int ngroup, const float* max_norm, const float* lr_table,
                          int lr_len, const int* step, float beta1, float beta2, float eps, float weight_decay,
                          int decoupled, void* stream);
+/* Layer-wise trust ratios: LARS (You, Gitman, Ginsburg 2017) on slk_sgdm_*'s arithmetic and LAMB (You et al.
+ * 2019, algorithm 2) on slk_adamw_*'s. A TENSOR is one weight or one bias; a segment is one [W | b] pair:
+ * elements [0, nw[s]) are the weight tensor, [nw[s], n[s]) the bias (nw = n: no bias; 0 <= nw <= n). Each
+ * tensor's step is scaled by a ratio of two of its own L2 norms, which must exist before its first element
+ * moves, so the fused reduce + step is two launches, both without atomics and bit-reproducible:
+ *   LARS  1. slk_reduce_tnorm_multi   2. slk_lars_multi
+ *   LAMB  1. slk_lamb_moments_multi   2. slk_lamb_multi
+ * Segments, groups (a group = one stage), nslab, n and group are those of the clip launches above; both passes
+ * must be given the same nslab, n, nw and group. Partials: block blk (< slk_reduce_sqnorm_nblk(n[s], nslab[s]))
+ * of segment s owns the FOUR floats [x2_W, p2_W, x2_b, p2_b] at partials[group[s]][4 * (off + blk)], off the
+ * block count of the group's earlier segments; a group's buffer holds 4 * (the sum of its segments' counts)
+ * floats, 16-byte aligned. x is the reduced gradient g (LARS) or the update direction u (LAMB), p the parameter
+ * before the step. trust_out[g] is f32 [2 * (segments of group g)][3]: rows 2k and 2k + 1 are
+ * [w_norm, x_norm, ratio] of the weight and of the bias of the group's k-th segment, written by pass 2 (the
+ * row of an empty tensor is not written). With exclude_bias != 0 a bias tensor runs at ratio = 1 and weight
+ * decay 0 (its row reports the norms and ratio 1).
+ *
+ * Pass 1, float32 order. grads[s][i] = the fixed-order slab sum (bitwise slk_sgdm_from_slabs' /
+ * slk_adamw_from_slabs'; grads[s] == slabs[s] with nslab 1: read in place, nothing written). The thread that
+ * owns column i forms x2 = fl(x * x) and p2 = fl(p * p), each rounded on its own, and holds them in the weight
+ * pair (i < nw) or the bias pair of its four values, the other pair 0 (a select: a NaN stays in its tensor);
+ * every other thread holds four zeros (the owners are the threads slk_reduce_sqnorm_multi names). Each of the
+ * four values is then summed over the block exactly as slk_reduce_sqnorm_multi's partial (the tree inside each
+ * wave, the 16 waves ascending) and thread 0 writes the four sums. A block that straddles nw contributes to
+ * both tensors. LAMB's owner first moves the moments with slk_adamw_from_slabs' expressions at weight decay 0,
+ *   m = m + (1 - b1)(g - m);  v = v * b2 + g * g * (1 - b2)   (stored),
+ * and forms, with t = *step + 1 and the bias corrections in double rounded to float32 as slk_adamw_from_slabs,
+ *   denom = sqrt(v) / (float)sqrt(1 - b2^t) + eps;  c = fl(m / denom);
+ *   u = fl(c * (float)(1 / (1 - b1^t))) + fl(wd * p)   (each product rounded on its own; wd = 0: the first).
+ *
+ * Pass 2: thread = element, 1024 per block. Every block sums its SEGMENT's partials, per component: thread j
+ * adds partials j, j + 1024, ... ascending from 0, then the block sum as in pass 1 — a fixed function of the
+ * segment's own partials, whatever shares the launch. w_norm = sqrt(sum p2), x_norm = sqrt(sum x2), then
+ *   LARS  ratio = (w_norm > 0 && g_norm > 0) ? fl(trust_coef * w_norm) / ((g_norm + fl(wd * w_norm)) + eps) : 1
+ *         d = fl(ratio * (g + fl(wd * p)))   (wd = 0: fl(ratio * g))
+ *         then slk_sgdm_from_slabs' momentum / dampening / Nesterov arithmetic on d at weight decay 0:
+ *         p -= lr * (that). An excluded bias has d = g: bitwise slk_sgdm_multi_from_slabs at weight decay 0.
+ *   LAMB  ratio = (w_norm > 0 && u_norm > 0) ? w_norm / u_norm : 1
+ *         u recomputed from the stored m, v and the unmodified p (pass 1's expression, the same bits),
+ *         p = p - fl(fl(lr * ratio) * u).
+ *         An excluded bias, and a tensor with w_norm == 0 (every p is 0: ratio 1 and no decay term), take the
+ *         same update in slk_adamw_from_slabs' own expression p + (-(float)(lr / (1 - b1^t))) * (m / denom):
+ *         bitwise slk_adamw_multi_from_slabs at weight decay 0.
+ * A NaN norm fails both compares (ratio 1); the rate is lr_table[min(*step, lr_len - 1)]; the caller ticks
+ * `step` after pass 2. When loss_values != NULL pass 1 runs one more block, slk_loss_log. */
+int slk_reduce_tnorm_multi(float* const* grads, const float* const* params, const float* const* slabs,
+                           const int* nslab, const int* n, const int* nw, const int* group, int nseg,
+                           float* const* partials, int ngroup, const float* loss_values, int loss_n,
+                           float loss_scale, float* ring, int capacity, int* counter, void* stream);
+int slk_lars_multi(float* const* params, const float* const* grads, float* const* bufs, const int* nslab,
+                   const int* n, const int* nw, const int* group, int nseg, const float* const* partials,
+                   float* const* trust_out, int ngroup, const float* lr_table, int lr_len, const int* step,
+                   float momentum, float dampening, float weight_decay, int nesterov, float trust_coef, float eps,
+                   int exclude_bias, void* stream);
+int slk_lamb_moments_multi(float* const* grads, const float* const* params, float* const* m, float* const* v,
+                           const float* const* slabs, const int* nslab, const int* n, const int* nw,
+                           const int* group, int nseg, float* const* partials, int ngroup, const int* step,
+                           float beta1, float beta2, float eps, float weight_decay, int exclude_bias,
+                           const float* loss_values, int loss_n, float loss_scale, float* ring, int capacity,
+                           int* counter, void* stream);
+int slk_lamb_multi(float* const* params, float* const* m, float* const* v, const int* nslab, const int* n,
+                   const int* nw, const int* group, int nseg, const float* const* partials,
+                   float* const* trust_out, int ngroup, const float* lr_table, int lr_len, const int* step,
+                   float beta1, float beta2, float eps, float weight_decay, int exclude_bias, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -169,6 +169,80 @@ static inline bool slk_clip_layout(const int* nslab, const int* n, const int* gr
     return true;
 }
 
+// Layer-wise trust ratios (slk_reduce_tnorm_multi -> slk_lars_multi, slk_lamb_moments_multi -> slk_lamb_multi).
+// A segment is one [W | b] pair: elements [0, nw) are the weight tensor, [nw, n) the bias. Block blk of a
+// segment's pass 1 leaves four partials [x2_W, p2_W, x2_b, p2_b] at partials[group][4 * (off + blk)], x the
+// gradient (LARS) or the update direction (LAMB), p the parameter before the step.
+//
+// Four block sums at once, each the bits of slk_block_sum_1024 (one barrier; red is [4][16] floats of LDS).
+__device__ __forceinline__ void slk_block_sum4_1024(float (&v)[4], float (*red)[16]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = wave_sum(v[k]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float t = red[k][0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) t += red[k][w];
+        v[k] = t;
+    }
+}
+// The four totals of one segment from its npart blocks' partials, in slk_clip_coef's order per component:
+// thread j adds partials j, j + 1024, ... ascending from 0, then the block sum. A fixed function of the
+// segment's own partials, so every block of every launch holds the same bits.
+__device__ __forceinline__ void slk_tensor_totals(const float* __restrict__ partials, int npart, float (*red)[16],
+                                                  float (&tot)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tot[k] = 0.f;
+    for (int j = threadIdx.x; j < npart; j += 1024) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(partials + 4 * (size_t)j);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tot[k] += q[k];
+    }
+    slk_block_sum4_1024(tot, red);
+}
+// LARS (You, Gitman, Ginsburg 2017): wn = sqrt(sum p^2), gn = sqrt(sum g^2),
+// ratio = fl(trust_coef * wn) / ((gn + fl(wd * wn)) + eps) where wn > 0 and gn > 0, else 1 (a NaN norm fails
+// the compare). Both products are rounded on their own.
+__device__ __forceinline__ float slk_lars_ratio(float sum_g2, float sum_p2, float trust_coef, float wd, float eps,
+                                                float& wn, float& gn) {
+    wn = sqrtf(sum_p2);
+    gn = sqrtf(sum_g2);
+    float num = trust_coef * wn, dw = wd * wn;
+    slk_keep(num);
+    slk_keep(dw);
+    const float r = num / ((gn + dw) + eps);
+    return (wn > 0.f && gn > 0.f) ? r : 1.f;
+}
+// LAMB (You et al. 2019): ratio = wn / un where both are > 0, else 1.
+__device__ __forceinline__ float slk_lamb_ratio(float sum_u2, float sum_p2, float& wn, float& un) {
+    wn = sqrtf(sum_p2);
+    un = sqrtf(sum_u2);
+    const float r = wn / un;
+    return (wn > 0.f && un > 0.f) ? r : 1.f;
+}
+
+// Host side of the layer-wise passes: slk_clip_layout's block counts and offsets (in blocks: a block owns four
+// floats of partials), plus the checks on nw and each segment's index inside its group (its two rows of the
+// group's trust_out).
+struct SlkTrustLayout {
+    SlkClipLayout c;
+    int slot[SLK_CLIP_MAXSEG];
+};
+static inline bool slk_trust_layout(const int* nslab, const int* n, const int* nw, const int* group, int nseg,
+                                    int ngroup, SlkTrustLayout& L) {
+    if (!nw || !slk_clip_layout(nslab, n, group, nseg, ngroup, L.c)) return false;
+    for (int s = 0; s < nseg; ++s) {
+        if (nw[s] < 0 || nw[s] > n[s]) return false;
+        L.slot[s] = (s > 0 && group[s] == group[s - 1]) ? L.slot[s - 1] + 1 : 0;
+    }
+    return true;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

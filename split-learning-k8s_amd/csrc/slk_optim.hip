@@ -5,6 +5,7 @@
 // one launch updates all of them, and the weight-gradient slabs written by the wgrad kernels are
 // summed (fixed order, bit-stable) in the same pass that applies the update.
 #include "slk_common.h"
+#include "slk_adam.h"
 
 // Deterministic slab reduction (+ optional SGD). A 1024-thread block owns 64 columns; wave w sums
 // slabs w, w+16, w+32, ... of those columns in order (8 loads in flight), then wave 0 adds the 16
@@ -385,6 +386,227 @@ __global__ __launch_bounds__(1024) void sgdm_clip_multi_kernel(const SgdmClipMul
     }
 }
 
+// ---------------------------------------------------------------------------- layer-wise trust ratios
+// LARS (on SgdmApply) and LAMB (on slk_adam.h's arithmetic): a segment is one [W | b] pair, elements [0, nw) the
+// weight tensor and [nw, n) the bias, and each tensor's step is scaled by a ratio of two of its own norms. Two
+// launches where the configured step runs one, as with clipping, neither with atomics.
+//
+// Pass 1, one block: slab_reduce on its columns (grad gets slk_sgdm_from_slabs' / slk_adamw_from_slabs' bits);
+// the applying thread of column i forms x^2 and p^2, each rounded on its own, and holds them in the weight pair
+// (i < nw) or the bias pair of [x2_W, p2_W, x2_b, p2_b]; every other thread holds four zeros. LAMB's thread
+// first moves and stores m and v and forms x = u (lamb_direction). Then four block sums (slk_block_sum_1024's
+// order each); thread 0 writes the block's four partials. A block that straddles nw contributes to both tensors.
+struct TnormSeg {
+    float* grad;  // NULL: in place (the one slab is the gradient block)
+    const float* param;
+    float* m;     // LAMB only
+    float* v;
+    const float* slabs;
+    float* partials;  // this segment's [nblk][4]
+    int nslab, n, nw, nblk;
+};
+// the owning thread's two squares into the weight pair or the bias pair (selects: a NaN stays in its own tensor)
+__device__ __forceinline__ void trust_squares(bool w, float x2, float p2, float* q) {
+    q[0] = w ? x2 : 0.f;
+    q[1] = w ? p2 : 0.f;
+    q[2] = w ? 0.f : x2;
+    q[3] = w ? 0.f : p2;
+}
+struct LarsSqApply {
+    float* __restrict__ grad;
+    const float* __restrict__ param;
+    int nw;
+    float* q;  // the thread's [x2_W, p2_W, x2_b, p2_b]
+    __device__ __forceinline__ void operator()(int i, float t) const {
+        if (grad) grad[i] = t;
+        const float p = param[i];
+        trust_squares(i < nw, t * t, p * p, q);
+    }
+};
+struct LambMomentsApply {
+    float* __restrict__ grad;
+    const float* __restrict__ param;
+    float* __restrict__ m_;
+    float* __restrict__ v_;
+    int nw;
+    AdamHyper h;
+    int exclude_bias;
+    float* q;
+    __device__ __forceinline__ void operator()(int i, float t) const {
+        if (grad) grad[i] = t;
+        const float p = param[i];
+        const AdamBias bc = adam_bias<true>(h.b1, h.b2, h.step, 0.f);
+        float m = m_[i], v = v_[i];
+        adam_moments(t, m, v, h.b1, h.b2);
+        m_[i] = m;
+        v_[i] = v;
+        const bool w = i < nw;
+        const float u = lamb_direction(m, v, p, bc, h.eps, (w || !exclude_bias) ? h.wd : 0.f);
+        trust_squares(w, u * u, p * p, q);
+    }
+};
+struct TnormMulti {
+    TnormSeg seg[SGD_MAXSEG];
+    int nseg;
+    AdamHyper h;  // LAMB only
+    int exclude_bias;
+    LossLogArgs loss;
+};
+
+template <bool LAMB>
+__global__ __launch_bounds__(1024) void reduce_tnorm_multi_kernel(const TnormMulti a) {
+    __shared__ float red[4][16];
+    int blk = blockIdx.x;
+    if (a.loss.v) {
+        if (blk == 0) {
+            loss_log_block(a.loss);
+            return;
+        }
+        --blk;
+    }
+#pragma unroll
+    for (int s = 0; s < SGD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const TnormSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float q[4] = {0.f, 0.f, 0.f, 0.f};
+                if (LAMB)
+                    slab_reduce(nullptr, g.slabs, g.nslab, g.n, blk,
+                                LambMomentsApply{g.grad, g.param, g.m, g.v, g.nw, a.h, a.exclude_bias, q});
+                else
+                    slab_reduce(nullptr, g.slabs, g.nslab, g.n, blk, LarsSqApply{g.grad, g.param, g.nw, q});
+#pragma unroll
+                for (int k = 0; k < 4; ++k) slk_keep(q[k]);  // every square is rounded on its own
+                slk_block_sum4_1024(q, red);
+                if (threadIdx.x == 0) *reinterpret_cast<f32x4*>(g.partials + 4 * (size_t)blk) = f32x4{q[0], q[1], q[2], q[3]};
+                return;
+            }
+            blk -= g.nblk;
+        }
+    }
+}
+
+// Pass 2: thread = element, 1024 per block. Every block sums its segment's partials (slk_tensor_totals: one
+// fixed order per component), forms the weight's and the bias's ratio and steps its elements; block 0 reports
+// the weight tensor, the block that holds element nw the bias: [w_norm, x_norm, ratio] each.
+struct TrustSeg {
+    float* param;
+    const float* grad;  // LARS only
+    float* s1;          // LARS: momentum buffer; LAMB: m
+    float* s2;          // LAMB: v
+    const float* partials;
+    float* out;  // this segment's [2][3]: the weight's row, then the bias's
+    int n, nw, nblk, npart;
+};
+struct LarsMulti {
+    TrustSeg seg[SGD_MAXSEG];
+    int nseg;
+    SgdmHyper h;
+    float trust_coef, eps;
+    int exclude_bias;
+};
+struct LambMulti {
+    TrustSeg seg[SGD_MAXSEG];
+    int nseg;
+    AdamHyper h;
+    int exclude_bias;
+};
+__device__ __forceinline__ void trust_report(const TrustSeg& g, int blk, const float (&w)[3], const float (&b)[3]) {
+    if (threadIdx.x != 0) return;
+    if (blk == 0 && g.nw > 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.out[k] = w[k];
+    }
+    if (blk == g.nw / 1024 && g.nw < g.n) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.out[3 + k] = b[k];
+    }
+}
+
+// LARS: d = fl(ratio * (g + fl(wd * p))), then SgdmApply's momentum / dampening / Nesterov arithmetic on d
+// at weight decay 0. An excluded bias runs at ratio 1 and weight decay 0: d = g, slk_sgdm_from_slabs' bits.
+__global__ __launch_bounds__(1024) void lars_multi_kernel(const LarsMulti a) {
+    __shared__ float red[4][16];
+    int blk = blockIdx.x;
+#pragma unroll
+    for (int s = 0; s < SGD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const TrustSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float tot[4], w[3], b[3];
+                slk_tensor_totals(g.partials, g.npart, red, tot);
+                const float wd = a.h.weight_decay, wd_b = a.exclude_bias ? 0.f : wd;
+                w[2] = slk_lars_ratio(tot[0], tot[1], a.trust_coef, wd, a.eps, w[0], w[1]);
+                b[2] = slk_lars_ratio(tot[2], tot[3], a.trust_coef, wd_b, a.eps, b[0], b[1]);
+                if (a.exclude_bias) b[2] = 1.f;
+                trust_report(g, blk, w, b);
+                const int i = blk * 1024 + threadIdx.x;
+                if (i < g.n) {
+                    const bool isw = i < g.nw;
+                    const float ratio = isw ? w[2] : b[2], wde = isw ? wd : wd_b;
+                    float d = g.grad[i];
+                    if (wde != 0.f) {
+                        float wp = wde * g.param[i];
+                        slk_keep(wp);
+                        d = d + wp;
+                    }
+                    d = ratio * d;
+                    slk_keep(d);
+                    SgdmHyper h0 = a.h;
+                    h0.weight_decay = 0.f;
+                    SgdmApply{g.param, nullptr, g.s1, h0}(i, d);
+                }
+                return;
+            }
+            blk -= g.nblk;
+        }
+    }
+}
+
+// LAMB: u from the stored m, v and the still unmodified p (pass 1's expression and bits), then
+// p = p - fl(fl(lr * ratio) * u). An excluded bias, and a tensor whose parameters are all zero (w_norm = 0:
+// ratio 1 and no decay term), step by adam_step: slk_adamw_from_slabs' bits at weight decay 0.
+__global__ __launch_bounds__(1024) void lamb_multi_kernel(const LambMulti a) {
+    __shared__ float red[4][16];
+    int blk = blockIdx.x;
+#pragma unroll
+    for (int s = 0; s < SGD_MAXSEG; ++s) {
+        if (s < a.nseg) {
+            const TrustSeg& g = a.seg[s];
+            if (blk < g.nblk) {
+                float tot[4], w[3], b[3];
+                slk_tensor_totals(g.partials, g.npart, red, tot);
+                w[2] = slk_lamb_ratio(tot[0], tot[1], w[0], w[1]);
+                b[2] = slk_lamb_ratio(tot[2], tot[3], b[0], b[1]);
+                if (a.exclude_bias) b[2] = 1.f;
+                trust_report(g, blk, w, b);
+                const int i = blk * 1024 + threadIdx.x;
+                if (i < g.n) {
+                    const bool isw = i < g.nw;
+                    const float lr = slk_lr_at(a.h.lr_table, a.h.lr_len, *a.h.step);
+                    const AdamBias bc = adam_bias<true>(a.h.b1, a.h.b2, a.h.step, lr);
+                    const float p = g.param[i], m = g.s1[i], v = g.s2[i];
+                    const bool excluded = !isw && a.exclude_bias;
+                    if (excluded || (isw ? w[0] : b[0]) == 0.f) {
+                        // ratio 1 and no decay term (p = 0 throughout, or an excluded bias): the same update
+                        // in slk_adamw_from_slabs' own expression, so its bits at weight decay 0
+                        g.param[i] = adam_step(p, m, adam_denom(v, bc.bc2s, a.h.eps), bc.step_size);
+                    } else {
+                        const float u = lamb_direction(m, v, p, bc, a.h.eps, a.h.wd);
+                        float r = lr * (isw ? w[2] : b[2]);
+                        slk_keep(r);
+                        float ru = r * u;
+                        slk_keep(ru);
+                        g.param[i] = p - ru;
+                    }
+                }
+                return;
+            }
+            blk -= g.nblk;
+        }
+    }
+}
+
 static inline int grid_for(int n) {
     int g = (n + 255) / 256;
     return g > 2048 ? 2048 : (g < 1 ? 1 : g);
@@ -523,6 +745,122 @@ extern "C" int slk_sgdm_clip_multi(float* const* params, const float* const* gra
     a.h = SgdmHyper{lr_table, lr_len, step, momentum, dampening, weight_decay, nesterov ? 1 : 0};
     if (nblk == 0) return 0;
     sgdm_clip_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+// ---- layer-wise trust ratios: host side
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// pass 1 of either recipe (m, v NULL: LARS)
+static int tnorm_launch(bool lamb, float* const* grads, const float* const* params, float* const* m, float* const* v,
+                        const float* const* slabs, const int* nslab, const int* n, const int* nw, const int* group,
+                        int nseg, float* const* partials, int ngroup, const AdamHyper& h, int exclude_bias,
+                        const LossLogArgs& loss, void* stream) {
+    SLK_CHECK_ARG(grads && params && slabs && partials && (!lamb || (m && v)));
+    SLK_CHECK_ARG(!loss.v || (loss.n > 0 && loss.capacity > 0 && loss.ring && loss.counter));
+    SlkTrustLayout L;
+    SLK_CHECK_ARG(slk_trust_layout(nslab, n, nw, group, nseg, ngroup, L));
+    TnormMulti a{};
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        float* part = partials[group[s]];
+        SLK_CHECK_ARG(grads[s] && params[s] && slabs[s] && part && aligned16(part) && (!lamb || (m[s] && v[s])));
+        const bool in_place = grads[s] == slabs[s];
+        SLK_CHECK_ARG(!in_place || nslab[s] == 1);
+        a.seg[s] = TnormSeg{in_place ? nullptr : grads[s], params[s], lamb ? m[s] : nullptr, lamb ? v[s] : nullptr,
+                            slabs[s], part + 4 * (size_t)L.c.off[s], nslab[s], n[s], nw[s], L.c.nblk[s]};
+        nblk += L.c.nblk[s];
+    }
+    a.nseg = nseg;
+    a.h = h;
+    a.exclude_bias = exclude_bias ? 1 : 0;
+    a.loss = loss;
+    if (loss.v) ++nblk;
+    if (nblk == 0) return 0;
+    if (lamb)
+        reduce_tnorm_multi_kernel<true><<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    else
+        reduce_tnorm_multi_kernel<false><<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+// the segments of pass 2 (s1, s2: buf, NULL or m, v); returns the launch's block count or -1
+static int trust_segs(TrustSeg* seg, float* const* params, const float* const* grads, float* const* s1,
+                      float* const* s2, const int* nslab, const int* n, const int* nw, const int* group, int nseg,
+                      const float* const* partials, float* const* trust_out, int ngroup) {
+    if (!params || !partials || !trust_out) return -1;
+    SlkTrustLayout L;
+    if (!slk_trust_layout(nslab, n, nw, group, nseg, ngroup, L)) return -1;
+    int nblk = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const float* part = partials[group[s]];
+        float* out = trust_out[group[s]];
+        if (!params[s] || !part || !aligned16(part) || !out || (grads && !grads[s]) || (s1 && !s1[s]) ||
+            (s2 && !s2[s]))
+            return -1;
+        seg[s] = TrustSeg{params[s], grads ? grads[s] : nullptr, s1 ? s1[s] : nullptr, s2 ? s2[s] : nullptr,
+                          part + 4 * (size_t)L.c.off[s], out + 6 * L.slot[s], n[s], nw[s], (n[s] + 1023) / 1024,
+                          L.c.nblk[s]};
+        nblk += seg[s].nblk;
+    }
+    return nblk;
+}
+
+extern "C" int slk_reduce_tnorm_multi(float* const* grads, const float* const* params, const float* const* slabs,
+                                      const int* nslab, const int* n, const int* nw, const int* group, int nseg,
+                                      float* const* partials, int ngroup, const float* loss_values, int loss_n,
+                                      float loss_scale, float* ring, int capacity, int* counter, void* stream) {
+    static_assert(SGD_MAXSEG == SLK_CLIP_MAXSEG, "trust layout");
+    return tnorm_launch(false, grads, params, nullptr, nullptr, slabs, nslab, n, nw, group, nseg, partials, ngroup,
+                        AdamHyper{}, 0, LossLogArgs{loss_values, loss_n, loss_scale, ring, capacity, counter}, stream);
+}
+
+extern "C" int slk_lars_multi(float* const* params, const float* const* grads, float* const* bufs, const int* nslab,
+                              const int* n, const int* nw, const int* group, int nseg, const float* const* partials,
+                              float* const* trust_out, int ngroup, const float* lr_table, int lr_len,
+                              const int* step, float momentum, float dampening, float weight_decay, int nesterov,
+                              float trust_coef, float eps, int exclude_bias, void* stream) {
+    SLK_CHECK_ARG(grads && lr_table && lr_len >= 1 && step && (bufs || momentum == 0.f));
+    LarsMulti a{};
+    const int nblk = trust_segs(a.seg, params, grads, momentum != 0.f ? bufs : nullptr, nullptr, nslab, n, nw, group,
+                                nseg, partials, trust_out, ngroup);
+    SLK_CHECK_ARG(nblk >= 0);
+    a.nseg = nseg;
+    a.h = SgdmHyper{lr_table, lr_len, step, momentum, dampening, weight_decay, nesterov ? 1 : 0};
+    a.trust_coef = trust_coef;
+    a.eps = eps;
+    a.exclude_bias = exclude_bias ? 1 : 0;
+    if (nblk == 0) return 0;
+    lars_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
+    return slk_launch_status();
+}
+
+extern "C" int slk_lamb_moments_multi(float* const* grads, const float* const* params, float* const* m,
+                                      float* const* v, const float* const* slabs, const int* nslab, const int* n,
+                                      const int* nw, const int* group, int nseg, float* const* partials, int ngroup,
+                                      const int* step, float beta1, float beta2, float eps, float weight_decay,
+                                      int exclude_bias, const float* loss_values, int loss_n, float loss_scale,
+                                      float* ring, int capacity, int* counter, void* stream) {
+    SLK_CHECK_ARG(step);
+    return tnorm_launch(true, grads, params, m, v, slabs, nslab, n, nw, group, nseg, partials, ngroup,
+                        AdamHyper{0.f, nullptr, 0, weight_decay, 0, beta1, beta2, eps, step}, exclude_bias,
+                        LossLogArgs{loss_values, loss_n, loss_scale, ring, capacity, counter}, stream);
+}
+
+extern "C" int slk_lamb_multi(float* const* params, float* const* m, float* const* v, const int* nslab,
+                              const int* n, const int* nw, const int* group, int nseg, const float* const* partials,
+                              float* const* trust_out, int ngroup, const float* lr_table, int lr_len,
+                              const int* step, float beta1, float beta2, float eps, float weight_decay,
+                              int exclude_bias, void* stream) {
+    SLK_CHECK_ARG(m && v && lr_table && lr_len >= 1 && step);
+    LambMulti a{};
+    const int nblk = trust_segs(a.seg, params, nullptr, m, v, nslab, n, nw, group, nseg, partials, trust_out, ngroup);
+    SLK_CHECK_ARG(nblk >= 0);
+    a.nseg = nseg;
+    a.h = AdamHyper{0.f, lr_table, lr_len, weight_decay, 0, beta1, beta2, eps, step};
+    a.exclude_bias = exclude_bias ? 1 : 0;
+    if (nblk == 0) return 0;
+    lamb_multi_kernel<<<nblk, 1024, 0, slk_stream(stream)>>>(a);
     return slk_launch_status();
 }
 

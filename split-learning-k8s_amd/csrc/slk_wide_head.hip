@@ -11,6 +11,7 @@
 // fixed-order reduction of the wgrad slabs, plus the kernels that rebuild the bf16 weight shadows the
 // MFMA convolutions read and the C8-ordered f32 copy of the fc weight the head reads.
 #include "slk_common.h"
+#include "slk_adam.h"
 
 namespace {
 constexpr int CUTF = 16384;       // features per sample
@@ -329,47 +330,6 @@ constexpr int AD_WAVES = 16;
 constexpr int AD_COLS_MAX = SLK_AD_MID ? 16 : 64, AD_MID_MAX = 64;
 __host__ __device__ constexpr int adam_cols_per_block(int nslab) {
     return nslab <= AD_COLS_MAX ? 1024 : (nslab <= AD_MID_MAX ? 256 : 64);
-}
-
-// Hyper-parameters of one Adam launch. TABLE = false is torch.optim.Adam(lr) as above (lr by value);
-// TABLE = true (slk_adamw_*) reads the rate from a device table at *step (slk_lr_at) and applies weight
-// decay: decoupled (torch.optim.AdamW: p *= 1 - lr * wd before the update, the factor in double like torch's
-// Python float) or coupled (torch.optim.Adam(weight_decay): g += wd * p before the moments).
-struct AdamHyper {
-    float lr;
-    const float* lr_table;
-    int lr_len;
-    float wd;
-    int decoupled;
-    float b1, b2, eps;
-    const int* step;
-};
-
-// the Adam update of element i from its summed gradient t (shared by the reduction forms below)
-template <bool TABLE>
-__device__ __forceinline__ void adam_apply(int i, float t, float* __restrict__ param, float* __restrict__ grad,
-                                           float* __restrict__ m_, float* __restrict__ v_, const AdamHyper& h) {
-    if (grad) grad[i] = t;
-    const float b1 = h.b1, b2 = h.b2, eps = h.eps;
-    const float lr = TABLE ? slk_lr_at(h.lr_table, h.lr_len, *h.step) : h.lr;
-    float p = param[i];
-    if (TABLE && h.wd != 0.f) {
-        if (h.decoupled)
-            p = p * (float)(1.0 - (double)lr * (double)h.wd);
-        else
-            t = t + h.wd * p;
-    }
-    const double tt = (double)(*h.step + 1);
-    const double bc1 = 1.0 - pow((double)b1, tt);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(1.0 - pow((double)b2, tt));
-    float m = m_[i], v = v_[i];
-    m = m + (1.f - b1) * (t - m);
-    v = v * b2 + t * t * (1.f - b2);
-    const float denom = sqrtf(v) / bc2s + eps;
-    param[i] = p + (-step_size) * (m / denom);
-    m_[i] = m;
-    v_[i] = v;
 }
 
 template <bool TABLE>

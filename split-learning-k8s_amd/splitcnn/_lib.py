@@ -103,6 +103,12 @@ _SIGS = {
     "slk_reduce_sqnorm_multi": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _F, _P, _I, _P, _P],
     "slk_sgdm_clip_multi": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _I, _P],
     "slk_adamw_clip_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _F, _I, _P],
+    # layer-wise trust ratios (optim.LARS / optim.LAMB): per-tensor norm partials, then the scaled step
+    "slk_reduce_tnorm_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _F, _P, _I, _P, _P],
+    "slk_lars_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _F, _F, _F, _I, _F, _F, _I, _P],
+    "slk_lamb_moments_multi": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P, _I, _F,
+                               _P, _I, _P, _P],
+    "slk_lamb_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

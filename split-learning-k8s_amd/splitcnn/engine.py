@@ -31,7 +31,7 @@ from . import ops
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .model_def import ModelPartA, ModelPartB
-from .optim import SGD, ClipNorm, LRSchedule, check_clip
+from .optim import LARS, SGD, ClipNorm, LRSchedule, check_clip, is_layerwise
 
 LR = 0.01  # optim.SGD(lr=0.01) on both sides (client_part.py:17, server_part.py:15)
 
@@ -96,7 +96,9 @@ class _SgdRecipe:
     (auto_tick False). With an optim.ClipNorm (`clip`, which like a schedule selects slk_sgdm_*) every step is
     two launches, slk_reduce_sqnorm_multi then slk_sgdm_clip_multi: the stage's gradient is clipped by its own
     global L2 norm before weight decay; `grads` keeps the unclipped gradient and `clip_out` the last step's
-    device [norm, coef]."""
+    device [norm, coef]. With an optim.LARS every step is slk_reduce_tnorm_multi then slk_lars_multi over the
+    stage's [weight | bias] pairs (PAIRS: (lo, hi, weight elements) of the flat block); `trust_out` keeps
+    every tensor's [w_norm, g_norm, ratio] of the last step in TENSORS' order."""
 
     def _init_optim(self, lr, optim, schedule, clip=None):
         if optim is not None and not isinstance(optim, SGD):
@@ -104,8 +106,11 @@ class _SgdRecipe:
         check_clip(clip)
         if optim is None and (schedule is not None or clip is not None):
             optim = SGD(lr)
+        if is_layerwise(optim) and clip is not None:
+            raise ValueError(f"{type(optim).__name__} is not combined with clip= (the trust ratio already bounds "
+                             "every tensor's step by its own norms)")
         self.optim, self.schedule = optim, None
-        self.clip = self.clip_out = None
+        self.clip = self.clip_out = self.trust_out = None
         self.buf = self.step_ctr = None
         self.auto_tick = True
         if optim is None:
@@ -117,6 +122,27 @@ class _SgdRecipe:
         if clip is not None:
             self.clip = clip.to(self.device)
             self.clip_out = torch.zeros(2, dtype=torch.float32, device=self.device)   # [norm, coef] of the last step
+        if isinstance(optim, LARS):   # [w_norm, g_norm, ratio] of every tensor's last step, in TENSORS' order
+            self.trust_out = torch.zeros(2 * len(self.PAIRS), 3, dtype=torch.float32, device=self.device)
+
+    def _trust_group(self, segs):
+        """This stage's [W | b] pairs as one group of the LARS launches: its own partials and trust_out. A
+        (param, grad, buf, slabs) tuple over the whole stage (step(): the gradient block in place; a fused
+        trainer's client segment) becomes one slice per pair."""
+        out = []
+        for g in segs:
+            if g[0].numel() == self.PAIRS[-1][1] and len(self.PAIRS) > 1:
+                out += [tuple(t[lo:hi] if t is not None else None for t in g[:3]) + (g[3][:, lo:hi], nw)
+                        for lo, hi, nw in self.PAIRS]
+            else:
+                lo = g[0].storage_offset() - self.params.storage_offset()
+                nw = {(a, b): w for a, b, w in self.PAIRS}.get((lo, lo + g[0].numel()))
+                if nw is None:
+                    raise ValueError(f"{type(self.optim).__name__}: a segment must be one [weight | bias] pair")
+                out.append(g + (nw,))
+        need = ops.trust_partials_needed(out)
+        self.trust_nblk = [ops.reduce_sqnorm_nblk(g[3].shape[1], g[3].shape[0]) for g in out]   # partials per pair
+        return (self._buf.get("trust_partials", (need,), torch.float32, self.device), self.trust_out, out)
 
     def _clip_group(self, segs):
         """This stage's segments as one group of the clip launches: its own partials and [norm, coef]."""
@@ -128,13 +154,19 @@ class _SgdRecipe:
         (param, grad, buf, slabs) tuples: separate launches, or ONE with the loss log (multi). With `clip`
         always the two clip launches (the loss log rides in the first); another clipped stage's
         optim_segment joins them as a group of its own."""
-        if any(len(g) == (4 if self.clip is not None else 5) and g[0] is not self.params for g in segments):
+        grouped = self.clip is not None or is_layerwise(self.optim)   # another stage joins as its own group
+        if any(len(g) == (4 if grouped else 5) and g[0] is not self.params for g in segments):
             raise ValueError("a segment of another stage must share this stage's clip= (both clipped by one "
-                             "optim.ClipNorm, or neither)")
+                             "optim.ClipNorm, or neither) and its layer-wise recipe")
         segs = [(self.params[g[0]:g[1]], self.grads[g[0]:g[1]], self.buf[g[0]:g[1]], g[2]) if len(g) == 3 else g
                 for g in segments]
         kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
-        if self.clip is not None:
+        if is_layerwise(self.optim):
+            groups = [self._trust_group([g for g in segs if len(g) == 4])]
+            groups += [g[4]._trust_group([g[:4]]) for g in segs if len(g) == 5]
+            ops.reduce_tnorm_multi(groups, loss=loss)
+            ops.lars_multi(groups, **kw)
+        elif self.clip is not None:
             groups = [self._clip_group([g for g in segs if len(g) == 4])]
             groups += [g[4]._clip_group([g[:4]]) for g in segs if len(g) == 5]
             ops.reduce_sqnorm_multi(groups, loss=loss)
@@ -153,7 +185,7 @@ class _SgdRecipe:
         """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch; with
         `clip` (shared with that stage) a group of its own in that stage's two clip launches."""
         seg = (self.params, self.grads, self.buf, slabs)
-        return seg if self.clip is None else seg + (self,)
+        return seg if self.clip is None and not is_layerwise(self.optim) else seg + (self,)
 
 
 class _Buffers:
@@ -229,6 +261,9 @@ class ClientStage(_SgdRecipe):
     reference's `activations.backward(grads); optimizer.step()`), or backward(cut_grad,
     accumulate=...) into the flat gradient block followed by step() (micro-batched / all-reduced
     topologies)."""
+
+    PAIRS = ((0, ops.CLIENT_NPARAM, 288),)
+    TENSORS = ("conv1.weight", "conv1.bias")
 
     def __init__(self, model: Optional[ModelPartA] = None, lr: float = LR, device="cuda",
                  optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
@@ -355,6 +390,9 @@ class ClientStage(_SgdRecipe):
 
 class ServerStage(_SgdRecipe):
     """Server half: ModelPartB + CrossEntropyLoss + SGD + loss log (src/server_part.py:14-16,25-58)."""
+
+    PAIRS = ((0, ops.CONV2_SLAB, 18432), (ops.CONV2_SLAB, ops.SERVER_NPARAM, 92160))
+    TENSORS = ("conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias")
 
     def __init__(self, model: Optional[ModelPartB] = None, lr: float = LR, device="cuda",
                  loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT,
@@ -661,7 +699,9 @@ class SplitTrainer(GraphedTrainer):
     stage's `lr` attribute after the first step does not reach a captured graph (use a schedule and
     LRSchedule.set_lr). `clip` (optim.ClipNorm, shared by both stages; selects the configured kernels like a
     schedule) clips each stage's gradient by that stage's own global norm before its update; grad_norms()
-    reads the last step's norms. `loss` (loss.SoftCrossEntropy) makes the server's head take mixed labels with label
+    reads the last step's norms. An optim.LARS config scales every tensor's step by its trust ratio (two launches
+    per step like clipping, not combined with `clip`); trust_ratios() reads the last step's norms and ratios.
+    `loss` (loss.SoftCrossEntropy) makes the server's head take mixed labels with label
     smoothing; the smoothing is a by-value constant of the launch, kept by a captured graph, with no setter.
     Evaluation stays the plain cross-entropy on plain labels."""
 

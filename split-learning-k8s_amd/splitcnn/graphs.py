@@ -170,6 +170,21 @@ class GraphedTrainer:
         (cn, cc), (sn, sc) = torch.stack(outs).tolist()
         return {"client": (cn, cc), "server": (sn, sc)}
 
+    # ---- layer-wise trust ratios (optim.LARS / optim.LAMB)
+    def trust_ratios(self) -> Dict[str, Dict[str, tuple]]:
+        """{"client": {"conv1.weight": (w_norm, x_norm, ratio), "conv1.bias": ...}, "server": {...}} of the last
+        step: every tensor's parameter norm before the step, the norm of its gradient (LARS) or update direction
+        (LAMB) and the ratio its step was scaled by (1.0 for a bias under exclude_bias). One host sync."""
+        stages = (("client", self.client), ("server", self.server))
+        if any(getattr(st, "trust_out", None) is None for _, st in stages):
+            raise RuntimeError("trust_ratios: the trainer was built without optim.LARS / optim.LAMB")
+        rows = torch.cat([st.trust_out for _, st in stages]).tolist()
+        out, k = {}, 0
+        for name, st in stages:
+            out[name] = {t: tuple(rows[k + j]) for j, t in enumerate(st.TENSORS)}
+            k += len(st.TENSORS)
+        return out
+
     # ---- optimizer state
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
         """CPU copies of the optimizer state, by name (empty where the optimizer has none). With the

@@ -766,6 +766,100 @@ def adamw_clip_multi(groups, max_norm, lr_table, step, beta1, beta2, eps, weight
               int(bool(decoupled)), _stream(like))
 
 
+# ---- layer-wise trust ratios (LARS / LAMB): per-tensor norm partials, then the scaled step (two launches)
+def trust_partials_needed(segments):
+    """Floats of partials one group of layer-wise `segments` (each ending in its [nslab, n] slabs and nw) needs:
+    four per block of reduce_tnorm_multi / lamb_moments_multi."""
+    return 4 * sum(reduce_sqnorm_nblk(seg[-2].shape[1], seg[-2].shape[0]) for seg in segments)
+
+
+def _trust_args(groups, who, width):
+    """The host arrays both layer-wise passes share. groups = [(partials, trust_out, segments)], one per stage; a
+    segment is `width` tensors (param, grad, state ..., slabs) and nw, the number of weight elements of the
+    [W | b] pair (the rest is the bias). grad None: the [1, n] slabs ARE the gradient block, read in place.
+    Returns (columns of the tensors' pointers, nslab, n, nw, group ids, partials pointers, trust_out pointers, a
+    tensor to take the stream from)."""
+    cols = [[] for _ in range(width)]
+    nslab, ns, nws, gid, parts, outs = [], [], [], [], [], []
+    for g, (partials, trust_out, segments) in enumerate(groups):
+        if not segments:
+            raise ValueError(f"{who}: group {g} has no segment")
+        for seg in segments:
+            if len(seg) != width + 1:
+                raise ValueError(f"{who}: a segment is {width} tensors and nw")
+            sl, nw = seg[-2], int(seg[-1])
+            nsl, n = sl.shape
+            if not 0 <= nw <= n:
+                raise ValueError(f"{who}: nw = {nw} outside [0, n = {n}]")
+            grad = seg[1]
+            if grad is None:
+                if nsl != 1:
+                    raise ValueError(f"{who}: a segment without grad steps in place from ONE slab")
+                grad = sl.view(-1)
+            names = ("param", "grad") + ("state",) * (width - 3)
+            for c, t, name in zip(cols, (seg[0], grad) + tuple(seg[2:-2]), names):
+                c.append(_dev(t, name, (n,)) if t is not None else None)
+            cols[-1].append(_dev(sl, "slabs"))
+            nslab.append(int(nsl))
+            ns.append(int(n))
+            nws.append(nw)
+            gid.append(g)
+        need = trust_partials_needed(segments)
+        if _dev(partials, "partials") % 16 or partials.numel() < need:
+            raise ValueError(f"{who}: group {g} needs {need} partials (16-byte aligned), got {partials.numel()}")
+        if _dev(trust_out, "trust_out") and trust_out.numel() < 6 * len(segments):
+            raise ValueError(f"{who}: group {g} needs a trust_out of [{2 * len(segments)}, 3]")
+        parts.append(partials.data_ptr())
+        outs.append(trust_out.data_ptr())
+    if not 1 <= len(gid) <= 4:
+        raise ValueError(f"{who}: 1 to 4 segments")
+    return cols, nslab, ns, nws, gid, parts, outs, groups[0][2][0][0]
+
+
+def reduce_tnorm_multi(groups, loss=None):
+    """Pass 1 of a LARS step (slk_reduce_tnorm_multi), ONE launch: every segment's grad = the fixed-order sum of
+    its slabs and four partials per block, [g2_W, p2_W, g2_b, p2_b], into its group's `partials`; plus
+    loss_log(*loss). groups = [(partials, trust_out, [(param, grad, buf, slabs, nw), ...])] as for lars_multi
+    (trust_out is not written here)."""
+    cols, nslab, ns, nws, gid, parts, _, like = _trust_args(groups, "reduce_tnorm_multi", 4)
+    _lib.call("slk_reduce_tnorm_multi", *_host_arrays([cols[1], cols[0], cols[-1], nslab, ns, nws, gid], n_int=4),
+              len(gid), *_host_arrays([parts], n_int=0), len(groups), *_loss_args(loss), _stream(like))
+
+
+def lars_multi(groups, lr_table, step, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+               trust_coef=1e-3, eps=1e-8, exclude_bias=True):
+    """Pass 2 of a LARS step (slk_lars_multi), ONE launch after reduce_tnorm_multi(groups): per tensor (the
+    weight and the bias of each segment) ratio = trust_coef * |w| / (|g| + wd * |w| + eps) (1 where a norm is
+    0), then sgdm_from_slabs' momentum arithmetic on ratio * (g + wd * w). trust_out[2k], [2k + 1] =
+    [w_norm, g_norm, ratio] of the weight and the bias of the group's k-th segment."""
+    cols, nslab, ns, nws, gid, parts, outs, like = _trust_args(groups, "lars_multi", 4)
+    _lib.call("slk_lars_multi", *_host_arrays(cols[:3] + [nslab, ns, nws, gid], n_int=4), len(gid),
+              *_host_arrays([parts, outs], n_int=0), len(groups), *_lr_args(lr_table, step), float(momentum),
+              float(dampening), float(weight_decay), int(bool(nesterov)), float(trust_coef), float(eps),
+              int(bool(exclude_bias)), _stream(like))
+
+
+def lamb_moments_multi(groups, step, beta1, beta2, eps, weight_decay=0.0, exclude_bias=True, loss=None):
+    """Pass 1 of a LAMB step (slk_lamb_moments_multi), ONE launch: grad = the fixed-order slab sum, Adam's m and
+    v moved and stored, and four partials per block, [u2_W, p2_W, u2_b, p2_b], of the update direction
+    u = m-hat / (sqrt(v-hat) + eps) + wd * p. groups = [(partials, trust_out, [(param, grad, m, v, slabs, nw),
+    ...])] as for lamb_multi."""
+    cols, nslab, ns, nws, gid, parts, _, like = _trust_args(groups, "lamb_moments_multi", 5)
+    _lib.call("slk_lamb_moments_multi",
+              *_host_arrays([cols[1], cols[0], cols[2], cols[3], cols[-1], nslab, ns, nws, gid], n_int=4), len(gid),
+              *_host_arrays([parts], n_int=0), len(groups), _dev(step, "step", (1,), torch.int32), float(beta1),
+              float(beta2), float(eps), float(weight_decay), int(bool(exclude_bias)), *_loss_args(loss), _stream(like))
+
+
+def lamb_multi(groups, lr_table, step, beta1, beta2, eps, weight_decay=0.0, exclude_bias=True):
+    """Pass 2 of a LAMB step (slk_lamb_multi), ONE launch after lamb_moments_multi(groups): per tensor
+    ratio = |w| / |u| (1 where a norm is 0) and p -= lr * ratio * u, u recomputed from the stored moments."""
+    cols, nslab, ns, nws, gid, parts, outs, like = _trust_args(groups, "lamb_multi", 5)
+    _lib.call("slk_lamb_multi", *_host_arrays([cols[0], cols[2], cols[3], nslab, ns, nws, gid], n_int=4), len(gid),
+              *_host_arrays([parts, outs], n_int=0), len(groups), *_lr_args(lr_table, step), float(beta1),
+              float(beta2), float(eps), float(weight_decay), int(bool(exclude_bias)), _stream(like))
+
+
 def tick(counter):
     """++counter on the device (a stage's optimizer step counter; advances inside a captured graph)."""
     _lib.call("slk_tick", _dev(counter, "counter", (1,), torch.int32), _stream(counter))

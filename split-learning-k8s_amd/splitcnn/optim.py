@@ -21,8 +21,17 @@ threshold stay on the device; trainer.grad_norms() reads the last step's. One de
 `stage.grads` keeps the UNCLIPPED reduced gradient (torch scales p.grad in place); the gradient the optimizer
 consumed is coef * grads. The clip tensors are no optimizer state (optimizer_state() keeps its keys).
 
-Limits: one rate and one recipe per stage (no per-parameter groups), L2 norm only (no clip_grad_value_), and
-the multi-GPU classes of dist.py take only stages built without a config.
+`LARS` (an SGD, for the K2 stages) and `LAMB` (an Adam, for the K5 stages) scale every tensor's step by a trust
+ratio of two of its own norms; a tensor is one weight or one bias, and `exclude_bias` (the default) keeps the
+biases at ratio 1 without weight decay. They run as two launches like a clipped step (slk_reduce_tnorm_multi ->
+slk_lars_multi, slk_lamb_moments_multi -> slk_lamb_multi), inside the captured graph and at the schedule's rate;
+trainer.trust_ratios() reads the last step's norms and ratios. The optimizer state keeps its keys (momentum
+buffer, or m and v, plus the counter). Not combined with clip=, and not taken by dist.py, the U-shaped or the
+federated paths: those raise ValueError.
+
+Limits: one rate and one recipe per stage (the only per-parameter distinction is weight / bias under the
+layer-wise recipes), L2 norm only (no clip_grad_value_), and the multi-GPU classes of dist.py take only stages
+built without a config.
 """
 from __future__ import annotations
 
@@ -84,6 +93,62 @@ class Adam:
     def __repr__(self):
         return (f"Adam(lr={self.lr}, betas={self.betas}, eps={self.eps}, weight_decay={self.weight_decay}, "
                 f"decoupled={self.decoupled})")
+
+
+class LARS(SGD):
+    """Layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017; timm's Lars with trust_clip=False) on the
+    SGD family: per tensor ratio = trust_coef * |w| / (|g| + weight_decay * |w| + eps), 1 where |w| or |g| is 0,
+    and torch.optim.SGD's momentum arithmetic on ratio * (g + weight_decay * w). With exclude_bias a bias runs
+    at ratio 1 and weight decay 0: plain momentum SGD at lr."""
+
+    def __init__(self, lr: float, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
+                 weight_decay: float = 0.0, trust_coef: float = 1e-3, eps: float = 1e-8, exclude_bias: bool = True):
+        super().__init__(lr, momentum, dampening, nesterov, weight_decay)
+        if not trust_coef > 0.0:
+            raise ValueError(f"Invalid trust_coef value: {trust_coef}")
+        if not eps >= 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        self.trust_coef, self.eps, self.exclude_bias = float(trust_coef), float(eps), bool(exclude_bias)
+
+    def kernel_args(self) -> dict:
+        return dict(super().kernel_args(), trust_coef=self.trust_coef, eps=self.eps, exclude_bias=self.exclude_bias)
+
+    def __repr__(self):
+        return (f"LARS(lr={self.lr}, momentum={self.momentum}, dampening={self.dampening}, nesterov={self.nesterov}, "
+                f"weight_decay={self.weight_decay}, trust_coef={self.trust_coef}, eps={self.eps}, "
+                f"exclude_bias={self.exclude_bias})")
+
+
+class LAMB(Adam):
+    """LAMB (You et al. 2019, algorithm 2; apex FusedLAMB and timm's Lamb without their gradient pre-clipping) on
+    the Adam family: u = m-hat / (sqrt(v-hat) + eps) + weight_decay * w, per tensor ratio = |w| / |u| (1 where
+    either is 0) and w -= lr * ratio * u. With exclude_bias a bias runs at ratio 1 and weight decay 0: plain
+    Adam at lr."""
+
+    def __init__(self, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.01, exclude_bias: bool = True):
+        super().__init__(lr, betas, eps, weight_decay, decoupled=True)
+        self.exclude_bias = bool(exclude_bias)
+
+    def kernel_args(self) -> dict:
+        return {"beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps, "weight_decay": self.weight_decay,
+                "exclude_bias": self.exclude_bias}
+
+    def __repr__(self):
+        return (f"LAMB(lr={self.lr}, betas={self.betas}, eps={self.eps}, weight_decay={self.weight_decay}, "
+                f"exclude_bias={self.exclude_bias})")
+
+
+def is_layerwise(optim) -> bool:
+    """Whether a config is one of the layer-wise recipes (the two trust-ratio launches instead of the fused one)."""
+    return isinstance(optim, (LARS, LAMB))
+
+
+def refuse_layerwise(optim, who: str):
+    """A path that cannot run the layer-wise launches must not run plain SGD / Adam in their place."""
+    if is_layerwise(optim):
+        raise ValueError(f"{who}: {type(optim).__name__} (layer-wise trust ratios) is not supported here; it runs "
+                         "on the one-GPU stages and trainers without clip=")
 
 
 class ClipNorm:

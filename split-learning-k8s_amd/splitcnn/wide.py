@@ -37,7 +37,7 @@ from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
-from .optim import Adam, ClipNorm, LRSchedule, check_clip
+from .optim import LAMB, Adam, ClipNorm, LRSchedule, check_clip, is_layerwise
 
 P_DROP = 0.25
 KEEP_THRESHOLD = int(round(P_DROP * 4294967296.0))          # keep iff hash >= p * 2^32
@@ -348,7 +348,9 @@ class _AdamRecipe:
     (AdamW or Adam's) and the rate read from the schedule's device table at the stage's step_ctr. With an
     optim.ClipNorm (`clip`, which like a schedule selects slk_adamw_*) every step is two launches,
     slk_reduce_sqnorm_multi then slk_adamw_clip_multi: the stage's gradient is clipped by its own global L2
-    norm before weight decay; `grads` keeps the unclipped gradient, `clip_out` the last step's [norm, coef]."""
+    norm before weight decay; `grads` keeps the unclipped gradient, `clip_out` the last step's [norm, coef].
+    With an optim.LAMB every step is slk_lamb_moments_multi then slk_lamb_multi over the stage's
+    [weight | bias] pairs; `trust_out` keeps every tensor's [w_norm, u_norm, ratio] of the last step."""
 
     def _init_optim(self, optim, schedule, clip=None):
         if optim is not None and not isinstance(optim, Adam):
@@ -356,8 +358,11 @@ class _AdamRecipe:
         check_clip(clip)
         if optim is None and (schedule is not None or clip is not None):
             optim = Adam(self.lr, self.betas, self.eps)
+        if is_layerwise(optim) and clip is not None:
+            raise ValueError(f"{type(optim).__name__} is not combined with clip= (the trust ratio already bounds "
+                             "every tensor's step by its own norms)")
         self.optim, self.schedule = optim, None
-        self.clip = self.clip_out = None
+        self.clip = self.clip_out = self.trust_out = None
         if optim is None:
             return
         self.lr, self.betas, self.eps = optim.lr, optim.betas, optim.eps
@@ -365,6 +370,31 @@ class _AdamRecipe:
         if clip is not None:
             self.clip = clip.to(self.device)
             self.clip_out = torch.zeros(2, dtype=_F32, device=self.device)   # [norm, coef] of the last step
+        if isinstance(optim, LAMB):   # [w_norm, u_norm, ratio] of every tensor's last step, in TENSORS' order
+            self.trust_out = torch.zeros(2 * len(self.PAIRS), 3, dtype=_F32, device=self.device)
+
+    def _lamb(self, segments, write_grads, kw):
+        """The two LAMB launches over this stage's [weight | bias] pairs (PAIRS: (lo, n, weight elements)); a
+        (lo, n, slabs) slice over the whole stage (the gradient block in place) becomes one slice per pair."""
+        pairs = {(lo, n): nw for lo, n, nw in self.PAIRS}
+        flat = []
+        for lo, n, sl in segments:
+            if (lo, n) in pairs:
+                flat.append((lo, n, sl, pairs[(lo, n)]))
+            elif (lo, n) == (0, self.params.numel()):
+                flat += [(a, k, sl[:, a:a + k], nw) for a, k, nw in self.PAIRS]
+            else:
+                raise ValueError("LAMB: a segment must be one [weight | bias] pair")
+        segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
+                 self.v[lo:lo + n], sl, nw) for lo, n, sl, nw in flat]
+        need = ops.trust_partials_needed(segs)
+        self.trust_nblk = [ops.reduce_sqnorm_nblk(g[4].shape[1], g[4].shape[0]) for g in segs]   # partials per pair
+        groups = [(self._buf.get("trust_partials", (need,), _F32, self.device), self.trust_out, segs)]
+        lr_table, step = kw.pop("lr_table"), kw["step"]
+        with TIMER("lamb_moments_multi"):
+            ops.lamb_moments_multi(groups, **kw)
+        with TIMER("lamb_multi"):
+            ops.lamb_multi(groups, lr_table, **kw)
 
     def _adamw(self, segments, write_grads=True, fuse=True):
         """slk_adamw_* on (lo, n, slabs) slices of this stage (slabs [nslab, n]): ONE launch (fuse) or one
@@ -372,6 +402,8 @@ class _AdamRecipe:
         segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
                  self.v[lo:lo + n], sl) for lo, n, sl in segments]
         kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
+        if is_layerwise(self.optim):
+            return self._lamb(segments, write_grads, kw)
         if self.clip is not None:
             need = self.clip_npart = ops.clip_partials_needed(segs)   # partials of this stage's last clipped step
             groups = [(self._buf.get("clip_partials", (need,), _F32, self.device), self.clip_out, segs)]
@@ -393,6 +425,8 @@ class WideClientStage(_AdamRecipe):
     Adam (client_part.py:114,132-133 for the widened model)."""
 
     OFF = {"W1": 0, "b1": 1728, "W2": 1792, "b2": 75520, "W3": 75648, "b3": 370560}
+    PAIRS = ((0, 1792, 1728), (1792, 73856, 73728), (75648, 295168, 294912))
+    TENSORS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "conv3.weight", "conv3.bias")
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None,
@@ -517,6 +551,9 @@ class WideClientStage(_AdamRecipe):
 class WideServerStage(_AdamRecipe):
     """Server half: step_request(cut, labels, step) -> (dcut, loss_i): dropout + fc + CE forward and
     backward, Adam, loss logged to the device ring (server_part.py:38-58 for the widened model)."""
+
+    PAIRS = ((0, SERVER_NPARAM, 163840),)
+    TENSORS = ("fc.weight", "fc.bias")
 
     def __init__(self, model: Optional[WideModelPartB] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None, optim: Optional[Adam] = None,
@@ -672,7 +709,9 @@ class WideTrainer(GraphedTrainer):
     seeds the dropout mask), so the captured graph follows the schedule. Without them `lr` is a by-value
     kernel argument that a captured graph keeps (use a schedule and LRSchedule.set_lr to change it). `clip`
     (optim.ClipNorm, shared by both stages) clips each stage's gradient by that stage's own global norm before
-    its Adam update; grad_norms() reads the last step's norms. `loss` (loss.SoftCrossEntropy) makes the head take
+    its Adam update; grad_norms() reads the last step's norms. An optim.LAMB config scales every tensor's step by
+    its trust ratio (two launches per stage step like clipping, not combined with `clip`); trust_ratios() reads the
+    last step's norms and ratios. `loss` (loss.SoftCrossEntropy) makes the head take
     mixed labels (loss.CutMix in the loader) with label smoothing, a by-value constant a captured graph keeps (no
     setter); evaluation stays the plain cross-entropy on plain labels."""
 
