@@ -708,6 +708,33 @@ int slk_lamb_multi(float* const* params, float* const* m, float* const* v, const
                    const int* nw, const int* group, int nseg, const float* const* partials,
                    float* const* trust_out, int ngroup, const float* lr_table, int lr_len, const int* step,
                    float beta1, float beta2, float eps, float weight_decay, int exclude_bias, void* stream);
+/* Exponential moving average of the parameters, after the step's optimizer launches and before the tick of
+ * `step`: nseg (1 .. SLK_EMA_MAXSEG) segments (e[s], p[s], n[s]) move in ONE launch, e in place, p only read. The
+ * pointer and size arrays are host memory (read at the call, so the launch is safe inside a stream capture);
+ * `decay` (f32[1]) and `step` (i32[1], the optimizer steps completed BEFORE this one) are device memory read by
+ * the kernel, so a captured graph follows both; `start` (>= 0) and `warmup` (0 / 1) travel by value and a captured
+ * graph keeps them. With k = *step and t = k - start:
+ *   t <  0:  e[i] = p[i]                 a copy of the bits (NaN payloads and -0.0 included)
+ *   t >= 0:  n  = t + 1                  (an integer in [1, 2^31])
+ *            nf = (float)n               round to nearest even; exact up to 2^24, above that nf is the nearest
+ *                                        float32 (spacing 2, 4, ... 128), still non-decreasing in n
+ *            w  = fl(fl(1 + nf) / fl(10 + nf))    correctly rounded division; w < 1 until n is about 1.5e8, then 1
+ *            d  = warmup ? (w < *decay ? w : *decay) : *decay     (TensorFlow's / torch_ema's num_updates form;
+ *                                        once w >= *decay — at the latest when w rounds to 1 — d is *decay for good)
+ *            omd = fl(1 - d)
+ *            e[i] = fma(omd, fl(p[i] - e[i]), e[i])   the difference rounded on its own, the product and the sum
+ *                                        fused: one rounding (torch's AveragedModel lerp e + (1 - d)(p - e))
+ * NaN and +-inf in p[i] propagate into e[i] by this arithmetic alone and reach no other element. Every element
+ * is read and written by exactly one thread, without atomics; its result depends on e[i], p[i], *decay, *step,
+ * start and warmup only — not on the grid, the segment's place in the launch or the pointers' alignment. e[s] and
+ * p[s] need 4-byte alignment; where both have the same 16-byte phase the body moves as 16-byte vectors behind a
+ * scalar head, otherwise the segment moves by scalars. n[s] = 0 is legal (its pointers may then be NULL).
+ * Refused with hipErrorInvalidValue, nothing launched: a NULL argument or segment pointer (n[s] > 0), nseg outside
+ * [1, SLK_EMA_MAXSEG], n[s] < 0, start < 0, a pointer not 4-byte aligned, e[s] == p[s] or any overlap of the two
+ * blocks of a segment. */
+#define SLK_EMA_MAXSEG 8
+int slk_ema_multi(float* const* e, const float* const* p, const int* n, int nseg, const float* decay,
+                  const int* step, int start, int warmup, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -109,6 +109,8 @@ _SIGS = {
     "slk_lamb_moments_multi": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P, _I, _F,
                                _P, _I, _P, _P],
     "slk_lamb_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P],
+    # exponential moving average of the parameters (optim.EMA)
+    "slk_ema_multi": [_P, _P, _P, _I, _P, _P, _I, _I, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

@@ -106,6 +106,9 @@ def _default_optimizer_only(who: str, *stages) -> None:
         if getattr(st, "loss", None) is not None:
             raise ValueError(f"dist.{who}: {type(st).__name__} carries a soft-target loss (splitcnn.loss); the "
                              "multi-GPU classes run the hard-label heads only — build the stage without loss=")
+        if getattr(st, "ema", None) is not None:
+            raise ValueError(f"dist.{who}: {type(st).__name__} carries an averaged copy of its parameters (optim.EMA); "
+                             "the multi-GPU classes do not launch its update — build the stage without ema=")
         if any(getattr(st, a, None) is not None for a in ("optim", "schedule", "clip")):
             raise ValueError(f"dist.{who}: {type(st).__name__} carries an optimizer config / learning-rate schedule "
                              "/ gradient clipping (splitcnn.optim); the multi-GPU classes take only the default "

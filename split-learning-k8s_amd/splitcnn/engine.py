@@ -31,7 +31,7 @@ from . import ops
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .model_def import ModelPartA, ModelPartB
-from .optim import LARS, SGD, ClipNorm, LRSchedule, check_clip, is_layerwise
+from .optim import EMA, LARS, SGD, ClipNorm, LRSchedule, check_clip, check_ema, is_layerwise
 
 LR = 0.01  # optim.SGD(lr=0.01) on both sides (client_part.py:17, server_part.py:15)
 
@@ -98,13 +98,17 @@ class _SgdRecipe:
     global L2 norm before weight decay; `grads` keeps the unclipped gradient and `clip_out` the last step's
     device [norm, coef]. With an optim.LARS every step is slk_reduce_tnorm_multi then slk_lars_multi over the
     stage's [weight | bias] pairs (PAIRS: (lo, hi, weight elements) of the flat block); `trust_out` keeps
-    every tensor's [w_norm, g_norm, ratio] of the last step in TENSORS' order."""
+    every tensor's [w_norm, g_norm, ratio] of the last step in TENSORS' order. With an optim.EMA (`ema_cfg`, which
+    selects slk_sgdm_* as well: the average needs the counter) the stage owns `ema`, a flat block like params that
+    starts as their copy, and every step is optimizer launch(es), slk_ema_multi, tick; a trainer that shares the
+    counter (auto_tick False) launches the update of both stages itself, in front of its tick."""
 
-    def _init_optim(self, lr, optim, schedule, clip=None):
+    def _init_optim(self, lr, optim, schedule, clip=None, ema=None):
         if optim is not None and not isinstance(optim, SGD):
             raise TypeError(f"optim: expected splitcnn.optim.SGD or None, got {type(optim).__name__}")
         check_clip(clip)
-        if optim is None and (schedule is not None or clip is not None):
+        check_ema(ema)
+        if optim is None and (schedule is not None or clip is not None or ema is not None):
             optim = SGD(lr)
         if is_layerwise(optim) and clip is not None:
             raise ValueError(f"{type(optim).__name__} is not combined with clip= (the trust ratio already bounds "
@@ -112,9 +116,13 @@ class _SgdRecipe:
         self.optim, self.schedule = optim, None
         self.clip = self.clip_out = self.trust_out = None
         self.buf = self.step_ctr = None
+        self.ema = self.ema_cfg = None
         self.auto_tick = True
         if optim is None:
             return
+        if ema is not None:
+            self.ema_cfg = ema.to(self.device)
+            self.ema = self.params.clone()
         self.lr = optim.lr
         self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
         self.buf = torch.zeros_like(self.params)
@@ -179,13 +187,38 @@ class _SgdRecipe:
 
     def _tick(self):
         if self.auto_tick:
+            ema_update([self])
             ops.tick(self.step_ctr)
+
+    def _weights(self, shapes, ema=False):
+        """Views of the parameter block, or of the averaged block (ema), in the tensors' own shapes."""
+        if ema and self.ema is None:
+            raise RuntimeError(f"{type(self).__name__}: weights='ema' needs a stage built with ema= (optim.EMA)")
+        flat, out, off = self.ema if ema else self.params, [], 0
+        for shp in shapes:
+            k = 1
+            for d in shp:
+                k *= d
+            out.append(flat[off:off + k].view(shp))
+            off += k
+        return out
 
     def optim_segment(self, slabs):
         """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch; with
         `clip` (shared with that stage) a group of its own in that stage's two clip launches."""
         seg = (self.params, self.grads, self.buf, slabs)
         return seg if self.clip is None and not is_layerwise(self.optim) else seg + (self,)
+
+
+def ema_update(stages):
+    """slk_ema_multi over the averaged blocks of `stages` (those built with ema=; they share the config and the
+    counter): ONE launch, after their optimizer launches and before the counter's tick."""
+    stages = [st for st in stages if st.ema is not None]
+    if not stages:
+        return
+    cfg = stages[0].ema_cfg
+    with TIMER("ema_multi"):
+        ops.ema_multi([(st.ema, st.params) for st in stages], cfg.value, stages[0].step_ctr, cfg.start, cfg.warmup)
 
 
 class _Buffers:
@@ -267,13 +300,13 @@ class ClientStage(_SgdRecipe):
 
     def __init__(self, model: Optional[ModelPartA] = None, lr: float = LR, device="cuda",
                  optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None):
+                 clip: Optional[ClipNorm] = None, ema: Optional[EMA] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else ModelPartA()).to(self.device)
         self.lr = lr
         self.params, self.grads = _flatten_params(
             [self.model.conv1.weight, self.model.conv1.bias], self.device)
-        self._init_optim(lr, optim, schedule, clip)
+        self._init_optim(lr, optim, schedule, clip, ema)
         self._buf = _Buffers()
         self._x = None
         self._act = None
@@ -327,22 +360,24 @@ class ClientStage(_SgdRecipe):
             ops.conv1_fwd_x3(x, self.W1.detach(), self.b1.detach(), act_amax, act16)
         self._x, self._act, self._act_amax, self._act16 = x, None, act_amax, act16
 
-    def forward_eval(self, x: torch.Tensor):
+    def forward_eval(self, x: torch.Tensor, ema: bool = False):
         """The client forward of an evaluation pass: returns (act, act_amax, act16) in this stage's own
         `eval_` buffers — the x3 operand (act None) when emit_act16, else the f32 act (+ act_amax when
         emit_amax). Keeps nothing for a backward and leaves _x / _act / _act16 / _relu_bits alone, so a
-        training forward ... backward_step sequence with an evaluation in between still works."""
+        training forward ... backward_step sequence with an evaluation in between still works. `ema`: the
+        kernels read the averaged block (views of it) instead of the parameters."""
         B = x.shape[0]
+        W1, b1 = self._weights(((32, 1, 3, 3), (32,)), True) if ema else (self.W1.detach(), self.b1.detach())
         if self.emit_act16:
             amax = self._buf.get("eval_act_amax", (B,), torch.float32, self.device)
             a16 = self._buf.get("eval_act16", (ops.conv2_act16_bytes(B),), torch.uint8, self.device)
             with TIMER("eval_conv1_fwd"):
-                ops.conv1_fwd_x3(x, self.W1.detach(), self.b1.detach(), amax, a16)
+                ops.conv1_fwd_x3(x, W1, b1, amax, a16)
             return None, amax, a16
         act = self._buf.get("eval_act", (B, 32, 26, 26), torch.float32, self.device)
         amax = self._buf.get("eval_act_amax", (B,), torch.float32, self.device) if self.emit_amax else None
         with TIMER("eval_conv1_fwd"):
-            ops.conv1_fwd(x, self.W1.detach(), self.b1.detach(), out=act, act_amax=amax)
+            ops.conv1_fwd(x, W1, b1, out=act, act_amax=amax)
         return act, amax, None
 
     def _slabs(self, cut_grad, x, act, tag="slabs"):
@@ -397,7 +432,8 @@ class ServerStage(_SgdRecipe):
     def __init__(self, model: Optional[ModelPartB] = None, lr: float = LR, device="cuda",
                  loss_log: Optional[LossLog] = None, conv: str = CONV_DEFAULT,
                  optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None):
+                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None,
+                 ema: Optional[EMA] = None):
         self.device = torch.device(device)
         # loss=SoftCrossEntropy(eps): every head path below calls its soft entry (mixed labels + label smoothing,
         # splitcnn.loss); eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
@@ -410,7 +446,7 @@ class ServerStage(_SgdRecipe):
         m = self.model
         self.params, self.grads = _flatten_params(
             [m.conv2.weight, m.conv2.bias, m.fc1.weight, m.fc1.bias], self.device)
-        self._init_optim(lr, optim, schedule, clip)
+        self._init_optim(lr, optim, schedule, clip, ema)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -639,7 +675,7 @@ class ServerStage(_SgdRecipe):
 
     def evaluate(self, act: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, *,
                  act16: Optional[torch.Tensor] = None, act_amax: Optional[torch.Tensor] = None,
-                 metrics=None, logits: Optional[torch.Tensor] = None):
+                 metrics=None, logits: Optional[torch.Tensor] = None, ema: bool = False):
         """Forward only (model.eval(); outputs = model(act); criterion(outputs, labels); outputs.argmax(1)):
         returns (pred i64 [B], loss_i f32 [B]); labels=None predicts only (loss_i is None). With act16 +
         act_amax on the 'x3' preset the code-less image forward runs (slk_conv2_fwd_pool_x3p); with an f32
@@ -649,10 +685,14 @@ class ServerStage(_SgdRecipe):
         receives the logits instead of this stage's buffer (self.eval_logits either way).
         Every buffer is this call's own (`eval_` names: about 0.15 GB of pooled at B = 4096 here, 0.35 GB
         of images in ClientStage.forward_eval) and the label flag is eval_err_flag: parameters, gradients,
-        the training buffers, err_flag and the loss log are not written."""
+        the training buffers, err_flag and the loss log are not written. `ema`: the kernels read the averaged block
+        (views of it, optim.EMA) instead of the parameters; it is not written either."""
         m = self.model
-        W2, b2 = m.conv2.weight.detach(), m.conv2.bias.detach()
-        W3, b3 = m.fc1.weight.detach(), m.fc1.bias.detach()
+        if ema:
+            W2, b2, W3, b3 = self._weights(((64, 32, 3, 3), (64,), (10, 9216), (10,)), True)
+        else:
+            W2, b2 = m.conv2.weight.detach(), m.conv2.bias.detach()
+            W3, b3 = m.fc1.weight.detach(), m.fc1.bias.detach()
         fi = self.impl_fwd
         if act16 is not None:
             if fi != "x3" or act_amax is None:
@@ -703,7 +743,11 @@ class SplitTrainer(GraphedTrainer):
     per step like clipping, not combined with `clip`); trust_ratios() reads the last step's norms and ratios.
     `loss` (loss.SoftCrossEntropy) makes the server's head take mixed labels with label
     smoothing; the smoothing is a by-value constant of the launch, kept by a captured graph, with no setter.
-    Evaluation stays the plain cross-entropy on plain labels."""
+    Evaluation stays the plain cross-entropy on plain labels. `ema` (optim.EMA, shared by both stages; selects
+    the configured kernels like a schedule) keeps an exponential moving average of both parameter blocks: ONE
+    slk_ema_multi launch over both in front of the shared counter's tick, inside the captured graph;
+    evaluate / eval_batch / predict(weights="ema") run on it and ema_state_dict() reads it. Its `warmup` and
+    `start` are by-value constants a captured graph keeps (no setter); EMA.set_decay reaches a captured graph."""
 
     input_shape = (1, 28, 28)
 
@@ -711,12 +755,15 @@ class SplitTrainer(GraphedTrainer):
                  lr: float = LR, device="cuda", graph: bool = True, loss_log: Optional[LossLog] = None,
                  conv: str = CONV_DEFAULT, act16: bool = True, fuse_client_backward: bool = True,
                  graph_inputs: int = 4, optim: Optional[SGD] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None):
+                 clip: Optional[ClipNorm] = None, loss: Optional[SoftCrossEntropy] = None,
+                 ema: Optional[EMA] = None):
         check_clip(clip)
+        check_ema(ema)
         super().__init__(device, graph, graph_inputs)
-        self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule, clip=clip)
+        self.client = ClientStage(client, lr, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
         self.server = ServerStage(server, lr, self.device, loss_log, conv=conv, optim=self.client.optim,
-                                  schedule=self.client.schedule, clip=self.client.clip, loss=loss)
+                                  schedule=self.client.schedule, clip=self.client.clip, loss=loss,
+                                  ema=self.client.ema_cfg)
         if self.server.optim is not None:
             self.client.step_ctr = self.server.step_ctr
             self.client.auto_tick = self.server.auto_tick = False   # _eager ticks the shared counter
@@ -752,25 +799,30 @@ class SplitTrainer(GraphedTrainer):
             cut_grad, _ = self.server.step_request(act, y, act_amax=self.client._act_amax, act16=a16)
             self.client.backward_step(cut_grad)
         if self.server.optim is not None and not self.server.auto_tick:
+            ema_update([self.client, self.server])   # both blocks in ONE launch, in front of the shared tick
             ops.tick(self.server.step_ctr)
 
     def _optim_state(self):
-        """The device tensors of the optimizer state, by name (momentum buffers and step counters)."""
+        """The device tensors of the optimizer state, by name (momentum buffers and step counters; with ema= the
+        averaged blocks)."""
+        keys = (("momentum_buffer", "buf"), ("step", "step_ctr"))
         return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
-                if st.optim is not None for k, a in (("momentum_buffer", "buf"), ("step", "step_ctr"))}
+                if st.optim is not None for k, a in keys + ((("ema", "ema"),) if st.ema is not None else ())}
 
     def _state(self):
-        """Both parameter blocks, the loss log's counter and the optimizer state: what a step writes."""
+        """Both parameter blocks, the loss log's counter and the optimizer state (the averaged blocks with it):
+        what a step writes."""
         return [self.client.params, self.server.params, self.server.loss_log.counter, *self._optim_state().values()]
 
     # ---- evaluation / prediction: forward only, own `eval_` buffers (about 0.5 GB extra at B = 4096), no
     # training state touched
-    def _eval_eager(self, x, y, metrics=None):
-        act, amax, a16 = self.client.forward_eval(x)
-        return self.server.evaluate(act, y, act16=a16, act_amax=amax, metrics=metrics)
+    def _eval_eager(self, x, y, metrics=None, weights="live"):
+        ema = self._check_weights(weights)
+        act, amax, a16 = self.client.forward_eval(x, ema=ema)
+        return self.server.evaluate(act, y, act16=a16, act_amax=amax, metrics=metrics, ema=ema)
 
-    def predict(self, x: torch.Tensor, return_logits: bool = False):
-        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""
-        act, amax, a16 = self.client.forward_eval(x)
-        pred, _ = self.server.evaluate(act, None, act16=a16, act_amax=amax)
+    def predict(self, x: torch.Tensor, return_logits: bool = False, weights: str = "live"):
+        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
+        weights="ema": on the averaged weights (optim.EMA)."""
+        pred, _ = self._eval_eager(x, None, weights=weights)
         return (pred.clone(), self.server.eval_logits.clone()) if return_logits else pred.clone()

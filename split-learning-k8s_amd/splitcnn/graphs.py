@@ -185,6 +185,32 @@ class GraphedTrainer:
             k += len(st.TENSORS)
         return out
 
+    # ---- the averaged weights (optim.EMA)
+    def _check_weights(self, weights) -> bool:
+        """Whether an evaluation runs on the averaged weights: "live" or "ema" (which needs ema=)."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"weights: expected 'live' or 'ema', got {weights!r}")
+        if weights == "ema" and any(getattr(st, "ema", None) is None for st in (self.client, self.server)):
+            raise RuntimeError("weights='ema': the trainer was built without ema= (optim.EMA)")
+        return weights == "ema"
+
+    def ema_state_dict(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        """{"client": {...}, "server": {...}}: the averaged blocks as CPU tensors under the modules' own
+        state_dict() names and shapes (load them into fresh modules to deploy the average). One host sync.
+        Needs `ema=`."""
+        stages = (("client", self.client), ("server", self.server))
+        if any(getattr(st, "ema", None) is None for _, st in stages):
+            raise RuntimeError("ema_state_dict: the trainer was built without ema= (optim.EMA)")
+        out = {}
+        for name, st in stages:
+            sd, flat, off = st.model.state_dict(), st.ema.detach().cpu(), 0
+            out[name] = {}
+            for t in st.TENSORS:   # the flat block's order
+                k = sd[t].numel()
+                out[name][t] = flat[off:off + k].view(sd[t].shape).clone()
+                off += k
+        return out
+
     # ---- optimizer state
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
         """CPU copies of the optimizer state, by name (empty where the optimizer has none). With the
@@ -203,39 +229,47 @@ class GraphedTrainer:
         self._state_written()
 
     # ---- evaluation: forward only, own `eval_` buffers, no training state touched
-    def _eval_graph_for(self, B: int, metrics):
+    def _eval_graph_for(self, B: int, metrics, weights="live"):
         """The evaluation pass for batch size B as a HIP graph on static inputs: one linear chain on one
         stream (client forward, server forward, head, accumulate), kept in `_eval_graphs` — not `_graphs`,
         whose keys the step's caller-buffer budget counts. The accumulator of `metrics` is baked in: another
         metrics object (or none) recaptures on the same static inputs. Warm-up and capture leave the
-        accumulator and the evaluation label flag as they were."""
-        g = self._eval_graphs.get(B)
+        accumulator and the evaluation label flag as they were. The pass on the averaged weights
+        (weights="ema") is a graph of its own under the key (B, "ema"), with its own static inputs: `_eval_graphs[B]`
+        stays the live one."""
+        key = B if weights == "live" else (B, weights)
+        g = self._eval_graphs.get(key)
         if g is not None and g["metrics"] is metrics:
             return g
         x, y = self._new_inputs(B) if g is None else (g["x"], g["y"])
         state = [self.server.eval_err_flag] + ([metrics.acc] if metrics is not None else [])
-        graph, out = capture(lambda: self._eval_eager(x, y, metrics), self.device, state)
+        run = ((lambda: self._eval_eager(x, y, metrics)) if weights == "live" else
+               (lambda: self._eval_eager(x, y, metrics, weights=weights)))
+        graph, out = capture(run, self.device, state)
         # the buffers this graph writes: a replay runs no Python, so eval_batch re-points the public
         # attributes (server.eval_logits, and a trainer's eval_cut) at them after every replay
         g = {"graph": graph, "x": x, "y": y, "metrics": metrics, "out": out, "logits": self.server.eval_logits,
              "cut": self.eval_cut}
-        self._eval_graphs[B] = g
+        self._eval_graphs[key] = g
         return g
 
-    def eval_batch(self, x: torch.Tensor, y: torch.Tensor, metrics=None):
+    def eval_batch(self, x: torch.Tensor, y: torch.Tensor, metrics=None, weights: str = "live"):
         """One held-out batch, asynchronous: (pred, loss_i), stage buffers that the next batch of the same
         size overwrites (the logits are in server.eval_logits); `metrics` (metrics.EvalMetrics) updated on
         the device. With graph=True the pass replays a graph captured once per batch size on static inputs
         that x and y are copied into. The graph holds the accumulator of `metrics`: calling with another
         metrics object (or none, or alternating with evaluate(), which uses the trainer's own) captures
         that size again — a warm-up and a capture each switch — so keep to one EvalMetrics per trainer in a
-        loop. Parameters, optimizer state, the loss log, err_flag and global_step are not touched."""
+        loop. Parameters, optimizer state, the loss log, err_flag and global_step are not touched.
+        weights="ema" runs the same pass on the averaged weights (optim.EMA; its own graph per batch size); the
+        averaged blocks are only read."""
+        ema = self._check_weights(weights)
         if tuple(x.shape[1:]) != self.input_shape or tuple(y.shape) != (x.shape[0],):
             raise ValueError(f"eval_batch: expected x [B,{','.join(map(str, self.input_shape))}] and y [B], got "
                              f"{tuple(x.shape)} and {tuple(y.shape)}")
         if not self.graph:
-            return self._eval_eager(x, y, metrics)
-        g = self._eval_graph_for(x.shape[0], metrics)
+            return self._eval_eager(x, y, metrics, weights=weights) if ema else self._eval_eager(x, y, metrics)
+        g = self._eval_graph_for(x.shape[0], metrics, weights)
         g["x"].copy_(x, non_blocking=True)
         g["y"].copy_(y, non_blocking=True)
         g["graph"].replay()
@@ -244,16 +278,17 @@ class GraphedTrainer:
             self.eval_cut = g["cut"]
         return g["out"]
 
-    def evaluate(self, batches, metrics=None):
+    def evaluate(self, batches, metrics=None, weights: str = "live"):
         """metrics.EvalResult over an iterable of device (x, y) batches — for example
         DeviceLoader(MnistIDX(root, train=False), 4096, shuffle=False) — with one host sync, at the end.
         With metrics=None the trainer's own EvalMetrics is reset and used; a caller's `metrics` is added to
-        as it is (reset it first for a fresh evaluation)."""
+        as it is (reset it first for a fresh evaluation). weights="ema": on the averaged weights (optim.EMA)."""
         from .metrics import EvalMetrics
+        self._check_weights(weights)
         if metrics is None:
             if self._eval_metrics is None:
                 self._eval_metrics = EvalMetrics(self.device)
             metrics = self._eval_metrics.reset()
         for x, y in batches:
-            self.eval_batch(x, y, metrics)
+            self.eval_batch(x, y, metrics, weights)
         return metrics.result()

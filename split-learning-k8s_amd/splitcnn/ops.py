@@ -860,6 +860,25 @@ def lamb_multi(groups, lr_table, step, beta1, beta2, eps, weight_decay=0.0, excl
               float(beta2), float(eps), float(weight_decay), int(bool(exclude_bias)), _stream(like))
 
 
+def ema_multi(segments, decay, step, start=0, warmup=True):
+    """ONE launch (slk_ema_multi): e <- e + (1 - d)(p - e) for each (e, p) of `segments` (1 to 8 flat f32 blocks of
+    equal length, any 4-byte alignment, e and p apart), or e <- p while *step < start; d is *decay, under `warmup`
+    min(*decay, (1 + n) / (10 + n)) with n = *step - start + 1. decay (f32[1], optim.EMA.value) and step (i32[1], the
+    stage's counter BEFORE its tick) are read on the device; start and warmup travel by value."""
+    k = len(segments)
+    if not 1 <= k <= 8:
+        raise ValueError("ema_multi: 1 to 8 segments")
+    es, ps, ns = [], [], []
+    for e, p in segments:
+        if e.dim() != 1:
+            raise ValueError("ema_multi: a segment is a pair of flat blocks")
+        es.append(_dev(e, "ema", None))
+        ps.append(_dev(p, "param", tuple(e.shape)))
+        ns.append(int(e.numel()))
+    _lib.call("slk_ema_multi", *_host_arrays([es, ps, ns], n_int=1, k=k), k, _dev(decay, "decay", (1,)),
+              _dev(step, "step", (1,), torch.int32), int(start), int(bool(warmup)), _stream(decay))
+
+
 def tick(counter):
     """++counter on the device (a stage's optimizer step counter; advances inside a captured graph)."""
     _lib.call("slk_tick", _dev(counter, "counter", (1,), torch.int32), _stream(counter))

@@ -29,6 +29,13 @@ trainer.trust_ratios() reads the last step's norms and ratios. The optimizer sta
 buffer, or m and v, plus the counter). Not combined with clip=, and not taken by dist.py, the U-shaped or the
 federated paths: those raise ValueError.
 
+`EMA` keeps an exponential moving average of a stage's parameters, updated by one launch (slk_ema_multi) after the
+optimizer launch(es) of every step and before the counter's tick, inside the captured graph; the trainers evaluate
+on it (evaluate / eval_batch / predict with weights="ema") and ema_state_dict() reads it. Its decay is device
+memory (`set_decay`), `warmup` and `start` are by-value constants a captured graph keeps. The averaged blocks join
+optimizer_state() as client.ema / server.ema only when ema= was given. Not taken by dist.py, the U-shaped or the
+federated paths: those raise ValueError.
+
 Limits: one rate and one recipe per stage (the only per-parameter distinction is weight / bias under the
 layer-wise recipes), L2 norm only (no clip_grad_value_), and the multi-GPU classes of dist.py take only stages
 built without a config.
@@ -190,6 +197,55 @@ def check_clip(clip):
     if clip is not None and not isinstance(clip, ClipNorm):
         raise TypeError(f"clip: expected splitcnn.optim.ClipNorm or None, got {type(clip).__name__}")
     return clip
+
+
+class EMA:
+    """An exponential moving average of a stage's parameters, kept after every optimizer step, as a config:
+    e <- e + (1 - d)(p - e) in float32 (torch.optim.swa_utils.AveragedModel's lerp), in one launch (slk_ema_multi)
+    between the stage's optimizer launches and the tick of its step counter k. With t = k - start: t < 0 copies
+    the parameters (the average starts at step `start`); otherwise n = t + 1 and d = min(decay, (1 + n) / (10 + n))
+    under `warmup` (TensorFlow's / torch_ema's num_updates form), else d = decay. The decay is a device f32[1] the
+    kernel reads, so a captured HIP graph follows `set_decay` without being recaptured. `warmup` and `start` are
+    constructor constants passed to the kernel by value: a captured graph keeps them, and there is no setter."""
+
+    def __init__(self, decay: float = 0.999, warmup: bool = True, start: int = 0, device="cuda"):
+        self.decay = self._checked(decay)
+        if not isinstance(warmup, (bool, np.bool_)):
+            raise ValueError(f"Invalid warmup: {warmup!r} (a bool)")
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= start < 2 ** 31:
+            raise ValueError(f"Invalid start: {start!r} (an optimizer step count >= 0)")
+        self.warmup, self.start = bool(warmup), int(start)
+        self.value = torch.full((1,), self.decay, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _checked(decay) -> float:
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.integer, np.floating)):
+            raise ValueError(f"Invalid decay: {decay!r}")
+        if not 0.0 <= decay < 1.0 or not float(np.float32(decay)) < 1.0:   # NaN fails this too; so does 1 - 1e-9 in f32
+            raise ValueError(f"Invalid decay: {decay} (need 0 <= decay < 1 in float32)")
+        return float(decay)
+
+    def to(self, device) -> "EMA":
+        """Move the decay (a no-op on its own device); captured graphs hold its address, so move an EMA before
+        the first step only."""
+        if self.value.device != torch.device(device):
+            self.value = self.value.to(device)
+        return self
+
+    def set_decay(self, decay: float) -> None:
+        """Overwrite the decay in place: an asynchronous device write on the current stream, so the next step —
+        eager or a replay of an already captured graph — averages at `decay`."""
+        self.decay = self._checked(decay)
+        self.value.fill_(self.decay)
+
+    def __repr__(self):
+        return f"EMA(decay={self.decay}, warmup={self.warmup}, start={self.start})"
+
+
+def check_ema(ema):
+    if ema is not None and not isinstance(ema, EMA):
+        raise TypeError(f"ema: expected splitcnn.optim.EMA or None, got {type(ema).__name__}")
+    return ema
 
 
 class LRSchedule:

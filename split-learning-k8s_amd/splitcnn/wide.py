@@ -37,7 +37,7 @@ from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
-from .optim import LAMB, Adam, ClipNorm, LRSchedule, check_clip, is_layerwise
+from .optim import EMA, LAMB, Adam, ClipNorm, LRSchedule, check_clip, check_ema, is_layerwise
 
 P_DROP = 0.25
 KEEP_THRESHOLD = int(round(P_DROP * 4294967296.0))          # keep iff hash >= p * 2^32
@@ -350,12 +350,19 @@ class _AdamRecipe:
     slk_reduce_sqnorm_multi then slk_adamw_clip_multi: the stage's gradient is clipped by its own global L2
     norm before weight decay; `grads` keeps the unclipped gradient, `clip_out` the last step's [norm, coef].
     With an optim.LAMB every step is slk_lamb_moments_multi then slk_lamb_multi over the stage's
-    [weight | bias] pairs; `trust_out` keeps every tensor's [w_norm, u_norm, ratio] of the last step."""
+    [weight | bias] pairs; `trust_out` keeps every tensor's [w_norm, u_norm, ratio] of the last step.
+    With an optim.EMA (`ema_cfg`; the default Adam path has its counter and keeps its launches) the stage owns
+    `ema`, a flat block like params that starts as their copy, and slk_ema_multi runs on every stepping path after
+    the optimizer launch(es) and in front of the counter's tick (_tick)."""
 
-    def _init_optim(self, optim, schedule, clip=None):
+    def _init_optim(self, optim, schedule, clip=None, ema=None):
         if optim is not None and not isinstance(optim, Adam):
             raise TypeError(f"optim: expected splitcnn.optim.Adam or None, got {type(optim).__name__}")
         check_clip(clip)
+        self.ema = self.ema_cfg = None
+        if check_ema(ema) is not None:
+            self.ema_cfg = ema.to(self.device)
+            self.ema = self.params.clone()
         if optim is None and (schedule is not None or clip is not None):
             optim = Adam(self.lr, self.betas, self.eps)
         if is_layerwise(optim) and clip is not None:
@@ -372,6 +379,14 @@ class _AdamRecipe:
             self.clip_out = torch.zeros(2, dtype=_F32, device=self.device)   # [norm, coef] of the last step
         if isinstance(optim, LAMB):   # [w_norm, u_norm, ratio] of every tensor's last step, in TENSORS' order
             self.trust_out = torch.zeros(2 * len(self.PAIRS), 3, dtype=_F32, device=self.device)
+
+    def _tick(self, stream):
+        """The averaged block's update (ema=), then ++step_ctr: the end of every stepping path."""
+        if self.ema is not None:
+            with TIMER("ema_multi"):
+                ops.ema_multi([(self.ema, self.params)], self.ema_cfg.value, self.step_ctr, self.ema_cfg.start,
+                              self.ema_cfg.warmup)
+        _k("tick", self.step_ctr.data_ptr(), stream)
 
     def _lamb(self, segments, write_grads, kw):
         """The two LAMB launches over this stage's [weight | bias] pairs (PAIRS: (lo, n, weight elements)); a
@@ -430,7 +445,7 @@ class WideClientStage(_AdamRecipe):
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None):
+                 clip: Optional[ClipNorm] = None, ema: Optional[EMA] = None):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartA()).to(self.device)
         m = self.model
@@ -441,9 +456,11 @@ class WideClientStage(_AdamRecipe):
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps = lr, betas, eps
-        self._init_optim(optim, schedule, clip)
+        self._init_optim(optim, schedule, clip, ema)
         self.fuse_adam = True  # step_from_slabs: the three Adam segments in one launch
         self.sh = new_shadows(self.device)   # bf16 conv weight shadows (slk_wide_shadows layouts)
+        # a second set for the averaged weights, rebuilt from them inside every evaluation pass that reads it
+        self.sh_ema = new_shadows(self.device) if self.ema is not None else None
         self._buf = _Buffers()
         self._saved = {}
         self.refresh_shadows()
@@ -459,9 +476,19 @@ class WideClientStage(_AdamRecipe):
         """Rebuild the bf16 conv weight shadows from the f32 masters (after load_state_dict or Adam)."""
         build_shadows(self._p("W1", 1728), self._p("W2", 73728), self._p("W3", 294912), self.sh, _stream(self.params))
 
-    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, tag="") -> torch.Tensor:
-        """cut = client forward of x; `tag` keeps separate saved tensors per micro-batch."""
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, tag="", ema: bool = False) -> torch.Tensor:
+        """cut = client forward of x; `tag` keeps separate saved tensors per micro-batch. `ema` (evaluation only):
+        the averaged weights — their bf16 shadows are rebuilt from the averaged block first (slk_wide_shadows, part
+        of the pass and of its graph, so they are always current) and the biases are the block's own."""
         B = x.shape[0]
+        if ema:
+            if self.ema is None:
+                raise RuntimeError("WideClientStage: weights='ema' needs a stage built with ema= (optim.EMA)")
+            e, o = self.ema, self.OFF
+            build_shadows(e[o["W1"]:o["b1"]], e[o["W2"]:o["b2"]], e[o["W3"]:o["b3"]], self.sh_ema, _stream(e))
+            sh, (b1, b2, b3) = self.sh_ema, (e[o["b1"]:o["W2"]], e[o["b2"]:o["W3"]], e[o["b3"]:])
+        else:
+            sh, (b1, b2, b3) = self.sh, (self._p("b1", 64), self._p("b2", 128), self._p("b3", 256))
         _dev(x, "x", (B, 3, 32, 32))
         a1 = self._b(f"a1{tag}", (B, 8, 32, 32, 8), _BF)
         p2 = self._b(f"p2{tag}", (B, 16, 16, 16, 8), _BF)
@@ -470,8 +497,7 @@ class WideClientStage(_AdamRecipe):
         _dev(cut, "cut", (B,) + CUT_SHAPE, _BF)
         code3 = self._b(f"code3{tag}", (B,) + CUT_SHAPE, _U8)
         a1bits = self._b(f"a1bits{tag}", (B, 1024), torch.int64)
-        client_forward_kernels(x, self.sh, self._p("b1", 64), self._p("b2", 128), self._p("b3", 256),
-                               a1, p2, code2, cut, code3, a1bits)
+        client_forward_kernels(x, sh, b1, b2, b3, a1, p2, code2, cut, code3, a1bits)
         self._x, self._a1, self._p2, self._code2, self._code3 = x, a1, p2, code2, code3
         self._saved[tag] = (x, a1, p2, code2, code3, a1bits)
         return cut
@@ -513,7 +539,7 @@ class WideClientStage(_AdamRecipe):
             self._adam(1792, 73856, s2)
             self._adam(75648, 295168, s3)
         self.refresh_shadows()
-        _k("tick", self.step_ctr.data_ptr(), _stream(self.params))
+        self._tick(_stream(self.params))
 
     def backward_step(self, dcut: torch.Tensor):
         self.step_from_slabs(*self.backward_slabs(dcut))
@@ -545,7 +571,7 @@ class WideClientStage(_AdamRecipe):
                CLIENT_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
                self.step_ctr.data_ptr(), _stream(g))
         self.refresh_shadows()
-        _k("tick", self.step_ctr.data_ptr(), _stream(g))
+        self._tick(_stream(g))
 
 
 class WideServerStage(_AdamRecipe):
@@ -558,7 +584,7 @@ class WideServerStage(_AdamRecipe):
     def __init__(self, model: Optional[WideModelPartB] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, seed: int = 0, loss_log: Optional[LossLog] = None, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
-                 loss: Optional[SoftCrossEntropy] = None):
+                 loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None):
         self.device = torch.device(device)
         # loss=SoftCrossEntropy(eps): the head is slk_wide_head_soft (mixed labels + label smoothing, splitcnn.loss);
         # eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
@@ -570,8 +596,10 @@ class WideServerStage(_AdamRecipe):
         self.v = torch.zeros_like(self.params)
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
-        self._init_optim(optim, schedule, clip)
+        self._init_optim(optim, schedule, clip, ema)
         self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
+        # the averaged fc weight in the cut's order, rebuilt inside every evaluation pass that reads it
+        self.wf8_ema = torch.empty_like(self.wf8) if self.ema is not None else None
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
         self.eval_logits = None   # the logits of the last evaluate() (a stage buffer)
@@ -585,16 +613,24 @@ class WideServerStage(_AdamRecipe):
     def refresh_shadows(self):
         _k("wide_fc_shadow", self.params.data_ptr(), self.wf8.data_ptr(), _stream(self.params))
 
-    def evaluate(self, cut, labels=None, metrics=None):
+    def evaluate(self, cut, labels=None, metrics=None, ema: bool = False):
         """Forward only, as WideModelPartB.eval() runs it: slk_wide_head_fwd with every feature kept
         (keep_threshold 0, keep_scale 1), then loss_i / pred from the logits (slk_eval_logits) and, with
         `metrics` (metrics.EvalMetrics), the device accumulator. Returns (pred, loss_i); labels=None predicts
         only (loss_i is None). Own `eval_` buffers and eval_err_flag; step_ctr is read (the dropout hash input,
-        unused at threshold 0) and never ticked; parameters, Adam state and the loss log are not touched."""
+        unused at threshold 0) and never ticked; parameters, Adam state and the loss log are not touched. `ema`:
+        the head reads the averaged block — wf8_ema is rebuilt from it first (slk_wide_fc_shadow, part of the pass
+        and of its graph) and the bias is the block's own; the block is not written."""
         B = cut.shape[0]
         _dev(cut, "cut", (B,) + CUT_SHAPE, _BF)
         logits = self._b("eval_logits", (B, 10), _F32)
-        _k("wide_head_fwd", cut.data_ptr(), self.wf8.data_ptr(), self.params[163840:].data_ptr(),
+        wf8, flat = self.wf8, self.params
+        if ema:
+            if self.ema is None:
+                raise RuntimeError("WideServerStage: weights='ema' needs a stage built with ema= (optim.EMA)")
+            wf8, flat = self.wf8_ema, self.ema
+            _k("wide_fc_shadow", flat.data_ptr(), wf8.data_ptr(), _stream(cut))
+        _k("wide_head_fwd", cut.data_ptr(), wf8.data_ptr(), flat[163840:].data_ptr(),
            self.step_ctr.data_ptr(), self.seed, 0, 1.0, logits.data_ptr(), 0, B, _stream(cut))
         with TIMER("eval_logits"):
             loss_i, pred = ops.eval_logits(logits, labels,
@@ -642,7 +678,7 @@ class WideServerStage(_AdamRecipe):
                self.v.data_ptr(), sf.data_ptr(), sf.shape[0], SERVER_NPARAM, float(self.lr),
                float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_ctr.data_ptr(), s)
         self.refresh_shadows()
-        _k("tick", self.step_ctr.data_ptr(), s)
+        self._tick(s)
 
     def log_loss(self, loss_i, step=None):
         _k("loss_log", loss_i.data_ptr(), loss_i.numel(), 1.0 / loss_i.numel(),
@@ -696,7 +732,7 @@ class WideServerStage(_AdamRecipe):
            self.loss_log.counter.data_ptr(), s)
         if step is not None:
             self.loss_log.note_step(step)
-        _k("tick", self.step_ctr.data_ptr(), s)
+        self._tick(s)
 
 
 class WideTrainer(GraphedTrainer):
@@ -713,19 +749,25 @@ class WideTrainer(GraphedTrainer):
     its trust ratio (two launches per stage step like clipping, not combined with `clip`); trust_ratios() reads the
     last step's norms and ratios. `loss` (loss.SoftCrossEntropy) makes the head take
     mixed labels (loss.CutMix in the loader) with label smoothing, a by-value constant a captured graph keeps (no
-    setter); evaluation stays the plain cross-entropy on plain labels."""
+    setter); evaluation stays the plain cross-entropy on plain labels. `ema` (optim.EMA, shared by both stages)
+    keeps an exponential moving average of both parameter blocks: each stage launches slk_ema_multi before its own
+    tick, inside the captured graph; evaluate / eval_batch / predict(weights="ema") run on it (bf16 shadows rebuilt
+    from it inside the pass) and ema_state_dict() reads it. Its `warmup` and `start` are by-value constants a
+    captured graph keeps (no setter); EMA.set_decay reaches a captured graph."""
 
     input_shape = (3, 32, 32)
 
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
-                 loss: Optional[SoftCrossEntropy] = None):
+                 loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None):
         check_clip(clip)
+        check_ema(ema)
         super().__init__(device, graph)
-        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip)
+        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
-                                      schedule=self.client.schedule, clip=self.client.clip, loss=loss)
+                                      schedule=self.client.schedule, clip=self.client.clip, loss=loss,
+                                      ema=self.client.ema_cfg)
 
     def _eager(self, x, y):
         c = self.client
@@ -734,12 +776,14 @@ class WideTrainer(GraphedTrainer):
 
     def _state(self):
         c, s = self.client, self.server
-        return [c.params, c.m, c.v, c.step_ctr, s.params, s.m, s.v, s.step_ctr, s.loss_log.counter]
+        return ([c.params, c.m, c.v, c.step_ctr, s.params, s.m, s.v, s.step_ctr, s.loss_log.counter] +
+                [st.ema for st in (c, s) if st.ema is not None])
 
     def _optim_state(self):
-        """Adam's m / v and the step counters of both stages, by name."""
+        """Adam's m / v and the step counters of both stages, by name; with ema= the averaged blocks."""
+        keys = (("exp_avg", "m"), ("exp_avg_sq", "v"), ("step", "step_ctr"))
         return {f"{n}.{k}": getattr(st, a) for n, st in (("client", self.client), ("server", self.server))
-                for k, a in (("exp_avg", "m"), ("exp_avg_sq", "v"), ("step", "step_ctr"))}
+                for k, a in keys + ((("ema", "ema"),) if st.ema is not None else ())}
 
     def _state_written(self):
         """The bf16 / C8 weight shadows follow the f32 masters."""
@@ -748,12 +792,14 @@ class WideTrainer(GraphedTrainer):
 
     # ---- evaluation / prediction: no dropout, no tick: both step counters, the parameters, Adam's m / v
     # and the shadows are as before (the cut of the last evaluation is in eval_cut)
-    def _eval_eager(self, x, y, metrics=None):
+    def _eval_eager(self, x, y, metrics=None, weights="live"):
+        ema = self._check_weights(weights)
         # the client forward under its own tag: the saved tensors of a training forward (tag "") survive
-        self.eval_cut = self.client.forward(x, tag="eval")   # the last evaluation's cut (a stage buffer)
-        return self.server.evaluate(self.eval_cut, y, metrics=metrics)
+        self.eval_cut = self.client.forward(x, tag="eval", ema=ema)   # the last evaluation's cut (a stage buffer)
+        return self.server.evaluate(self.eval_cut, y, metrics=metrics, ema=ema)
 
-    def predict(self, x, return_logits: bool = False):
-        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits."""
-        pred, _ = self._eval_eager(x, None)
+    def predict(self, x, return_logits: bool = False, weights: str = "live"):
+        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
+        weights="ema": on the averaged weights (optim.EMA)."""
+        pred, _ = self._eval_eager(x, None, weights=weights)
         return (pred.clone(), self.server.eval_logits.clone()) if return_logits else pred.clone()
