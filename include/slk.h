@@ -735,6 +735,39 @@ int slk_lamb_multi(float* const* params, float* const* m, float* const* v, const
 #define SLK_EMA_MAXSEG 8
 int slk_ema_multi(float* const* e, const float* const* p, const int* n, int nseg, const float* decay,
                   const int* step, int start, int warmup, void* stream);
+/* FP8 cut records (csrc/slk_cut8.hip): an opt-in, lossy wire format of the K5 cut and of its gradient. A sample
+ * is the 16,384 contiguous bf16 elements of one cut [256,8,8] (C8 layout in memory; the codec is elementwise, so
+ * the layout does not matter) or of one cut-gradient row. fmt 0 = "e4m3" (OCP e4m3fn, F_MAX 448), fmt 1 = "e5m2"
+ * (OCP e5m2, F_MAX 57344); the convention is e4m3 forward, e5m2 backward.
+ * Record: one sample becomes 16,400 bytes (16 x 1025), records contiguous: u8 [n, 16400], so a slice of samples
+ * is a slice of bytes. The base pointer must be 16-byte aligned.
+ *   bytes 0..3   int32 e, little endian          bytes 8..15      zero
+ *   bytes 4..7   uint32 fmt                      bytes 16..16399  payload, byte i = the fp8 code of element i
+ * Encode: amax = max |x_i| over the sample. amax == 0: e = 0; otherwise e is the smallest integer with
+ * amax * 2^-e <= F_MAX, clamped below at -100. y_i = x_i * 2^-e (an exact float32 product of a bf16 value and a
+ * power of two) is converted to fp8 round-to-nearest-even; |y_i| <= F_MAX by construction, so nothing saturates
+ * and neither format's NaN or inf codes are produced; a result of zero keeps the sign of x_i. A sample with any
+ * non-finite element is poisoned: e = 0x7FFFFFFF and an all-zero payload.
+ * Decode: x^_i = fp8_to_f32(payload_i) * 2^e written as bf16 — exact: at most 4 significant bits, and e >= -100
+ * keeps it a normal bf16 — with one exception at the top of bf16's range: where the product of a finite code is
+ * 2^128 or more it is written as the largest finite bf16 of its sign (0x7F7F / 0xFF7F), never as inf. An encoder
+ * produces such a code only for a sample whose amax lies in bf16's top binade and rounds up past it (amax =
+ * 255 * 2^120 becomes 256 * 2^120 in e4m3); saturating there is nearer to x than the bound below asks and keeps
+ * the idempotence. A poisoned record decodes to 16,384 bf16 NaNs (0x7FC0). A record is malformed if its
+ * fmt word is not `fmt`, bytes 8..15 are not zero, or e is outside [-100, 127] and not the poison value: it
+ * decodes to NaNs as well and sets err_flag[0] = 1 (a plain store; nobody clears it). NaN and inf codes inside a
+ * received payload convert and propagate (a NaN code of either sign gives 0x7FC0).
+ * Error: |x - x^| <= max(|x| * 2^-(m+1), 2^e * 2^(emin-m-1)), (m, emin) = (3, -6) for e4m3 and (2, -14) for
+ * e5m2. decode(encode(.)) is idempotent in decoded bits (the records may differ: e drops by one where the
+ * rounded amax falls onto F_MAX / 2).
+ * slk_cut8_roundtrip is bitwise decode(encode(x)) in one launch with no record in memory; out may equal x.
+ * One block per sample; every output byte is written by exactly one thread, without atomics. n == 0 launches
+ * nothing and returns 0; n < 0, fmt outside {0, 1}, a NULL pointer or a pointer that is not 16-byte aligned
+ * (err_flag: 4-byte) is refused with hipErrorInvalidValue before any launch. */
+int slk_cut8_encode(const void* x_bf16, int n, int fmt, void* rec, void* stream);
+int slk_cut8_decode(const void* rec, int n, int fmt, void* out_bf16, int* err_flag, void* stream);
+int slk_cut8_roundtrip(const void* x_bf16, int n, int fmt, void* out_bf16, void* stream);
+int64_t slk_cut8_record_bytes(void); /* 16400 */
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -111,6 +111,11 @@ _SIGS = {
     "slk_lamb_multi": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _I, _P],
     # exponential moving average of the parameters (optim.EMA)
     "slk_ema_multi": [_P, _P, _P, _I, _P, _P, _I, _I, _P],
+    # FP8 records of the K5 cut and its gradient (codec.Fp8Cut)
+    "slk_cut8_encode": [_P, _I, _I, _P, _P],
+    "slk_cut8_decode": [_P, _I, _I, _P, _P, _P],
+    "slk_cut8_roundtrip": [_P, _I, _I, _P, _P],
+    "slk_cut8_record_bytes": [],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)
@@ -141,7 +146,7 @@ _SIGS = {
     "slk_tick": [_P, _P],
 }
 _RESTYPES = {"slk_error_string": ctypes.c_char_p, "slk_build_id": ctypes.c_char_p, "slk_conv2_act16_bytes": ctypes.c_int64,
-             "slk_relu_bits_bytes": ctypes.c_int64}
+             "slk_relu_bits_bytes": ctypes.c_int64, "slk_cut8_record_bytes": ctypes.c_int64}
 
 SYMBOLS = tuple(_SIGS)
 

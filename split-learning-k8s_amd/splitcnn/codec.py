@@ -6,13 +6,20 @@ bit mask of its nonzero elements plus those elements in order, and the gradient 
 same positions only: the client applies its own ReLU mask before using the gradient (ReLU's backward
 in activations.backward, src/client_part.py:132), so the positions left out never reach a result.
 Every weight, loss and gradient downstream is bit-identical to the dense exchange.
+
+The widened model's bf16 cut (K5, wide.py) has a codec of its own, Fp8Cut (csrc/slk_cut8.hip): opt-in and lossy, one
+power-of-two scale per sample and OCP FP8 codes, half the bytes in each direction.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
-from .ops import _stream
+from .ops import _dev, _stream
+
+CUT8_SAMPLE = 16384      # bf16 elements of one K5 cut [256,8,8] or of one cut-gradient row
+CUT8_RECORD = 16400      # bytes of one record: a 16-byte header and one fp8 code per element
+CUT8_FORMATS = {"e4m3": 0, "e5m2": 1}
 
 
 class CutCodec:
@@ -77,3 +84,98 @@ class CutCodec:
         v = v if vals is None else vals
         _lib.call("slk_cut_unpack", v.data_ptr(), out.numel(), mask.data_ptr(), offsets.data_ptr(), out.data_ptr(),
                   _stream(out))
+
+
+class Fp8Cut:
+    """Opt-in lossy FP8 exchange of the widened model's cut (csrc/slk_cut8.hip; the rule is in include/slk.h,
+    "FP8 cut records"): one power-of-two scale per sample, OCP fp8 codes, 16,400 bytes a sample against the bf16
+    cut's 32,768. `fwd` is the format of the cut ("e4m3" by convention), `bwd` that of the cut gradient ("e5m2");
+    either may be None, which leaves that direction dense bf16. The formats are constructor constants passed to the
+    kernels by value: a captured graph keeps them, and there is no setter.
+
+    A sample is 16,384 contiguous bf16 elements: x / out are [n, ...] with 16,384 elements per row, records are
+    uint8 [n, 16400]. Every method works on caller-visible buffers and launches on the tensor's current stream."""
+
+    def __init__(self, fwd="e4m3", bwd="e5m2"):
+        for name, v in (("fwd", fwd), ("bwd", bwd)):
+            if v is not None and v not in CUT8_FORMATS:
+                raise ValueError(f"Fp8Cut: {name}={v!r}; expected one of {sorted(CUT8_FORMATS)} or None")
+        if fwd is None and bwd is None:
+            raise ValueError("Fp8Cut: fwd and bwd are both None — that is the dense exchange (pass no codec)")
+        self.fwd, self.bwd = fwd, bwd
+        self._bufs = {}
+
+    def __repr__(self):
+        return f"Fp8Cut(fwd={self.fwd!r}, bwd={self.bwd!r})"
+
+    def format(self, direction: str):
+        """The format name of "fwd" / "bwd", or None where that direction stays dense."""
+        if direction not in ("fwd", "bwd"):
+            raise ValueError(f"Fp8Cut: direction {direction!r}; expected 'fwd' or 'bwd'")
+        return self.fwd if direction == "fwd" else self.bwd
+
+    def _fmt(self, direction: str) -> int:
+        name = self.format(direction)
+        if name is None:
+            raise ValueError(f"Fp8Cut: the {direction} direction is dense (built with {direction}=None)")
+        return CUT8_FORMATS[name]
+
+    @staticmethod
+    def _rows(t, name) -> int:
+        """Checked sample count of a bf16 tensor [n, ...] of 16,384 elements per row."""
+        _dev(t, name, dtype=torch.bfloat16)
+        if t.dim() < 1 or t.numel() != t.shape[0] * CUT8_SAMPLE:
+            raise ValueError(f"{name}: expected [n, ...] with {CUT8_SAMPLE} elements per sample, got {tuple(t.shape)}")
+        Fp8Cut._aligned(t, name)
+        return int(t.shape[0])
+
+    @staticmethod
+    def _records(rec, n, name="rec"):
+        _dev(rec, name, (n, CUT8_RECORD), torch.uint8)
+        Fp8Cut._aligned(rec, name)
+
+    @staticmethod
+    def _aligned(t, name):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: the base address must be 16-byte aligned")
+
+    def records(self, key, n: int, device):
+        """The uint8 [n, 16400] record buffer of `key`. Keyed by shape too and never replaced, so a HIP graph
+        captured around the kernels at one size keeps valid pointers after another size has run (CutCodec._buf)."""
+        k = (key, int(n), str(torch.device(device)))
+        t = self._bufs.get(k)
+        if t is None:
+            t = torch.empty((int(n), CUT8_RECORD), dtype=torch.uint8, device=device)
+            self._bufs[k] = t
+        return t
+
+    def encode(self, x, rec, direction: str = "fwd"):
+        """x (bf16 [n, ...]) -> rec (uint8 [n, 16400]) in `direction`'s format."""
+        fmt, n = self._fmt(direction), self._rows(x, "x")
+        self._records(rec, n)
+        _lib.call("slk_cut8_encode", x.data_ptr(), n, fmt, rec.data_ptr(), _stream(x))
+        return rec
+
+    def decode(self, rec, out, err_flag, direction: str = "fwd"):
+        """rec -> out (bf16 [n, ...]); a malformed record (not `direction`'s format, a nonzero reserved word, an
+        exponent out of range) decodes to NaNs and sets err_flag (int32 [1])."""
+        fmt, n = self._fmt(direction), self._rows(out, "out")
+        self._records(rec, n)
+        _dev(err_flag, "err_flag", (1,), torch.int32)
+        _lib.call("slk_cut8_decode", rec.data_ptr(), n, fmt, out.data_ptr(), err_flag.data_ptr(), _stream(out))
+        return out
+
+    def roundtrip(self, x, out, direction: str):
+        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x."""
+        fmt, n = self._fmt(direction), self._rows(x, "x")
+        if self._rows(out, "out") != n:
+            raise ValueError(f"out: expected {n} samples like x, got {out.shape[0]}")
+        _lib.call("slk_cut8_roundtrip", x.data_ptr(), n, fmt, out.data_ptr(), _stream(x))
+        return out
+
+
+def check_cut_codec(codec):
+    """A trainer's / hub's codec argument: an Fp8Cut or None."""
+    if codec is not None and not isinstance(codec, Fp8Cut):
+        raise TypeError(f"expected splitcnn.codec.Fp8Cut or None, got {type(codec).__name__}")
+    return codec

@@ -854,14 +854,32 @@ class WideHub:
     parts are still in flight. Clients then all-reduce their weight gradient (370,816 f32) and take
     identical Adam steps: exactly the single-process widened step at batch (N-1)*B.
     Stages: client.forward(x, tag) / backward_grads(dcut, tag, accumulate) / step_from_grads / grads /
-    cut_shape / cut_dtype; server.accumulate(cut, labels, scale, b0, k, nparts, dcut) / finish_step."""
+    cut_shape / cut_dtype; server.accumulate(cut, labels, scale, b0, k, nparts, dcut) / finish_step.
 
-    def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None):
+    codec (codec.Fp8Cut, opt-in and lossy; both sides must be built with the same formats): each part travels as
+    FP8 records (16,400 B/sample, include/slk.h "FP8 cut records") in every direction whose format is not None —
+    the sender encodes the part into one uint8 tensor, the receiver decodes it where the dense tensor would have
+    landed (the server into its `cuts` slice before accumulate; it encodes each `dcuts` slice before sending) — so
+    the step is exactly wide.WideTrainer(cut_codec=...)'s at batch (N-1)*B. A direction set to None travels dense
+    bf16. HIP kernels: the stage must be on a CUDA device. Every rank that decodes keeps `err_flag` (a malformed
+    record decodes to NaNs and sets it); check_exchange() reads it. `exchange_bytes` counts what this rank sent and
+    received in the last step, `dense_bytes` what the dense exchange would have moved."""
+
+    def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None, codec=None):
         _default_optimizer_only("WideHub", stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.server_rank = world - 1
         self.nclients = world - 1
         self.client_group = client_group
+        self.codec = self.err_flag = None
+        if codec is not None:
+            from .codec import check_cut_codec
+            self.codec = check_cut_codec(codec)
+            device = torch.device(getattr(stage, "device", "cpu"))
+            if device.type != "cuda":
+                raise ValueError("WideHub(codec=...): the FP8 cut codec runs as HIP kernels on CUDA tensors; the stage "
+                                 f"is on {device} — pass no codec (on BOTH sides) for CPU stages")
+            self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
         if groups is None:   # one group per direction, as for Hub (exchange_groups)
             groups = exchange_groups() if dist.is_initialized() else (None, None)
         self.groups = tuple(groups)
@@ -869,6 +887,7 @@ class WideHub:
         self.global_step = 0
         self._bufs = {}
         self.exchange_bytes = 0
+        self.dense_bytes = 0
 
     def _buf(self, name, shape, dtype, device):
         key = (name, tuple(shape), dtype, str(torch.device(device)))
@@ -878,59 +897,86 @@ class WideHub:
             self._bufs[key] = t
         return t
 
+    def _fp8(self, direction) -> bool:
+        return self.codec is not None and self.codec.format(direction) is not None
+
+    def _count_bytes(self, n: int, dense_per_sample: int):
+        """The last step's bytes on this rank's links for n samples: each direction's cut payload + the labels."""
+        from .codec import CUT8_RECORD
+        per = sum(CUT8_RECORD if self._fp8(d) else dense_per_sample for d in ("fwd", "bwd"))
+        self.exchange_bytes = n * per + n * 8
+        self.dense_bytes = 2 * n * dense_per_sample + n * 8
+
+    def check_exchange(self):
+        """Raise if any record this rank decoded so far was malformed (one host sync)."""
+        if self.err_flag is not None and int(self.err_flag.item()) != 0:
+            raise RuntimeError("dist.WideHub: a received FP8 cut record was malformed (wrong format word, nonzero "
+                               "reserved bytes or an exponent out of range); its sample was decoded to NaNs")
+
     def client_step(self, x, y):
-        c = self.stage
+        c, q = self.stage, self.codec
         B, m = x.shape[0], self.micro
         assert B % m == 0, "batch must be divisible by the micro-batch count"
         b = B // m
         dcut = self._buf("dcut", c.cut_shape(B), c.cut_dtype, x.device)
         fw, bw = self.groups
-        sends, recvs = [], []
+        f8, b8 = self._fp8("fwd"), self._fp8("bwd")
+        sends, recvs, grecs = [], [], []
         for k in range(m):
             sl = slice(k * b, (k + 1) * b)
             cut = c.forward(x[sl], tag=k)
+            if f8:
+                cut = q.encode(cut, q.records(("fwd", k), b, x.device), "fwd")
             sends.append(isend(cut, self.server_rank, fw))
             sends.append(isend(y[sl], self.server_rank, fw))
         for k in range(m):
-            recvs.append(irecv(dcut[k * b:(k + 1) * b], self.server_rank, bw))
+            grecs.append(q.records(("bwd", k), b, x.device) if b8 else dcut[k * b:(k + 1) * b])
+            recvs.append(irecv(grecs[k], self.server_rank, bw))
         for k in range(m):
             recvs[k].wait()
+            if b8:
+                q.decode(grecs[k], dcut[k * b:(k + 1) * b], self.err_flag, "bwd")
             c.backward_grads(dcut[k * b:(k + 1) * b], tag=k, accumulate=k > 0)
         for w in sends:
             w.wait()
         if self.nclients > 1:
             dist.all_reduce(c.grads, group=self.client_group)
         c.step_from_grads()
-        self.exchange_bytes = 2 * dcut.numel() * dcut.element_size() + y.numel() * 8
+        self._count_bytes(B, dcut[0].numel() * dcut.element_size() if B else 0)
         self.global_step += 1
 
     def server_step(self, B: int, device, cut_shape, cut_dtype):
         """B = per-client batch; cut_shape(n) / cut_dtype describe the client stage's cut tensor."""
-        s = self.stage
+        s, q = self.stage, self.codec
         m, nc = self.micro, self.nclients
         b, G = B // m, nc * B
         cuts = self._buf("cuts", cut_shape(G), cut_dtype, device)
         dcuts = self._buf("dcuts", cut_shape(G), cut_dtype, device)
         labels = self._buf("labels", (G,), torch.int64, device)
         fw, bw = self.groups
-        reqs = {}
+        f8, b8 = self._fp8("fwd"), self._fp8("bwd")
+        reqs, recs = {}, {}
         for c in range(nc):
             for k in range(m):
                 sl = slice(c * B + k * b, c * B + (k + 1) * b)
-                reqs[c, k] = (irecv(cuts[sl], c, fw), irecv(labels[sl], c, fw))
+                recs[c, k] = q.records(("fwd", c, k), b, device) if f8 else cuts[sl]
+                reqs[c, k] = (irecv(recs[c, k], c, fw), irecv(labels[sl], c, fw))
         sends, part = [], 0
         for k in range(m):
             for c in range(nc):
                 sl = slice(c * B + k * b, c * B + (k + 1) * b)
                 for r in reqs[c, k]:
                     r.wait()
+                if f8:
+                    q.decode(recs[c, k], cuts[sl], self.err_flag, "fwd")
                 s.accumulate(cuts[sl], labels[sl], 1.0 / G, c * B + k * b, part, m * nc, dcut=dcuts[sl])
-                sends.append(isend(dcuts[sl], c, bw))
+                out = q.encode(dcuts[sl], q.records(("bwd", c, k), b, device), "bwd") if b8 else dcuts[sl]
+                sends.append(isend(out, c, bw))
                 part += 1
         s.finish_step(m * nc, step=self.global_step)
         for w in sends:
             w.wait()
-        self.exchange_bytes = 2 * cuts.numel() * cuts.element_size() + labels.numel() * 8
+        self._count_bytes(G, cuts[0].numel() * cuts.element_size() if G else 0)
         self.global_step += 1
 
 

@@ -33,6 +33,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
+from .codec import Fp8Cut, check_cut_codec
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
@@ -753,26 +754,45 @@ class WideTrainer(GraphedTrainer):
     keeps an exponential moving average of both parameter blocks: each stage launches slk_ema_multi before its own
     tick, inside the captured graph; evaluate / eval_batch / predict(weights="ema") run on it (bf16 shadows rebuilt
     from it inside the pass) and ema_state_dict() reads it. Its `warmup` and `start` are by-value constants a
-    captured graph keeps (no setter); EMA.set_decay reaches a captured graph."""
+    captured graph keeps (no setter); EMA.set_decay reaches a captured graph. `cut_codec` (codec.Fp8Cut) puts the
+    arithmetic of the FP8 exchange (dist.WideHub(codec=...)) inside the step: the head reads
+    roundtrip(cut, fwd) from a server-stage buffer and the client back-propagates roundtrip(dcut, bwd) — straight
+    through, exactly what the wire does — two slk_cut8_roundtrip launches inside the captured graph (one per
+    direction that is not None). evaluate / eval_batch / predict quantise the cut the same way, on the live and on
+    the averaged weights: that is what a deployed server receives. The formats are by-value constants a captured
+    graph keeps (no setter); cut_codec=None launches nothing new."""
 
     input_shape = (3, 32, 32)
 
     def __init__(self, client: Optional[WideModelPartA] = None, server: Optional[WideModelPartB] = None,
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
-                 loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None):
+                 loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
+                 cut_codec: Optional[Fp8Cut] = None):
         check_clip(clip)
         check_ema(ema)
+        self.cut_codec = check_cut_codec(cut_codec)
         super().__init__(device, graph)
         self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
                                       schedule=self.client.schedule, clip=self.client.clip, loss=loss,
                                       ema=self.client.ema_cfg)
 
+    def _wire(self, t, direction, name):
+        """What the other side of an FP8 exchange receives for t: roundtrip(t) in `direction`'s format, in the
+        server stage's buffer `name` (fwd) or in place (bwd: the server's own dcut buffer); t itself without a
+        codec or where the direction is dense."""
+        q = self.cut_codec
+        if q is None or q.format(direction) is None:
+            return t
+        out = self.server._b(name, tuple(t.shape), _BF) if name is not None else t
+        with TIMER("cut8_roundtrip"):
+            return q.roundtrip(t, out, direction)
+
     def _eager(self, x, y):
         c = self.client
-        dcut, _ = self.server.step_request(c.forward(x), y)
-        c.backward_step(dcut)
+        dcut, _ = self.server.step_request(self._wire(c.forward(x), "fwd", "cut_q"), y)
+        c.backward_step(self._wire(dcut, "bwd", None))
 
     def _state(self):
         c, s = self.client, self.server
@@ -796,7 +816,7 @@ class WideTrainer(GraphedTrainer):
         ema = self._check_weights(weights)
         # the client forward under its own tag: the saved tensors of a training forward (tag "") survive
         self.eval_cut = self.client.forward(x, tag="eval", ema=ema)   # the last evaluation's cut (a stage buffer)
-        return self.server.evaluate(self.eval_cut, y, metrics=metrics, ema=ema)
+        return self.server.evaluate(self._wire(self.eval_cut, "fwd", "eval_cut_q"), y, metrics=metrics, ema=ema)
 
     def predict(self, x, return_logits: bool = False, weights: str = "live"):
         """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
