@@ -175,6 +175,16 @@ int slk_fc_xent_soft(const float* pooled, const float* W3, const float* b3, cons
 int slk_fc_wgrad(const float* dlogits, const float* pooled, float* slabs, int B, void* stream);
 int slk_fc_wgrad_nslab(int B);
 
+/* slk_fc_dgrad_amax + slk_fc_wgrad in ONE launch whose blocks take one of the two jobs from their index (each
+ * kind keeps its own partition, so neither waits for the other): the default K2 step's fc1 backward. Every output bit for bit what the two entries write for the same inputs:
+ *   dpooled[b][k] = the ten-term fmaf chain from 0 over the classes in ascending order, fmaf(dlogits[b][j], W3[j][k], .)
+ *   dp_amax[b]    = max_k |dpooled[b][k]|                       (a maximum: no order)
+ *   slabs[s]      = [dW3 | db3] of slice s of the batch, slk_fc_wgrad_nslab(B) slices in slk_fc_wgrad's order: each
+ *                   dW3[j][k] the fmaf chain from 0 over the slice's samples in ascending order, db3[j] their plain
+ *                   sum in the same order. */
+int slk_fc_backward(const float* dlogits, const float* W3, const float* pooled, float* dpooled, float* dp_amax,
+                    float* slabs, int B, void* stream);
+
 /* Cut-layer gradient: cut_grad = conv2 input gradient of maxpool/relu-masked dpooled
  * (uses `code` from slk_conv2_fwd_pool). This is `client_activations.grad` of
  * src/server_part.py:45,51,57. Winograd F(2x2,3x3) on the f32 MFMA; the routed conv2 output

@@ -772,11 +772,21 @@ __global__ __launch_bounds__(FCH_T, 1) void fc_head16_kernel(
 #endif
 constexpr int FCW_MAXSPLIT = SLK_FCW_MAXSPLIT;
 constexpr int FCW_SLAB = W3_N + NCLS;  // 92170
-__global__ __launch_bounds__(256) void fc_wgrad_kernel(const float* __restrict__ dlogits,
-                                                       const float* __restrict__ pooled,
-                                                       float* __restrict__ slabs, int B, int per) {
-    const int k4 = blockIdx.x * 256 + threadIdx.x;  // float4 column index (< 2304)
-    const int sp = blockIdx.y;
+template <bool NT>
+__device__ __forceinline__ float4 fcw_ld(const float4* p) {
+    if constexpr (NT) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *p;
+    }
+}
+// One block's work, (column block cb, batch slice sp): shared by fc_wgrad_kernel and fc_backward_kernel's wgrad role.
+template <bool NT = false>  // NT: pooled through non-temporal loads (fc_backward_kernel's wgrad role)
+__device__ __forceinline__ void fcw_block(const float* __restrict__ dlogits, const float* __restrict__ pooled,
+                                          float* __restrict__ slabs, int B, int per, int cb, int sp) {
+    const int k4 = cb * 256 + threadIdx.x;  // float4 column index (< 2304)
     const int bs = sp * per, be = min(B, bs + per);
     float4 acc[NCLS];
 #pragma unroll
@@ -786,7 +796,7 @@ __global__ __launch_bounds__(256) void fc_wgrad_kernel(const float* __restrict__
     for (; b + 8 <= be; b += 8) {
         float4 p[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) p[u] = P4[(size_t)(b + u) * FC_K4 + k4];
+        for (int u = 0; u < 8; ++u) p[u] = fcw_ld<NT>(P4 + (size_t)(b + u) * FC_K4 + k4);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -797,7 +807,7 @@ __global__ __launch_bounds__(256) void fc_wgrad_kernel(const float* __restrict__
             }
     }
     for (; b < be; ++b) {
-        const float4 p = P4[(size_t)b * FC_K4 + k4];
+        const float4 p = fcw_ld<NT>(P4 + (size_t)b * FC_K4 + k4);
 #pragma unroll
         for (int jj = 0; jj < NCLS; ++jj) {
             const float d = dlogits[b * NCLS + jj];
@@ -808,11 +818,17 @@ __global__ __launch_bounds__(256) void fc_wgrad_kernel(const float* __restrict__
     float* slab = slabs + (size_t)sp * FCW_SLAB;
 #pragma unroll
     for (int jj = 0; jj < NCLS; ++jj) reinterpret_cast<float4*>(slab + jj * P_SAMPLE)[k4] = acc[jj];
-    if (blockIdx.x == 0 && threadIdx.x < NCLS) {
+    if (cb == 0 && threadIdx.x < NCLS) {
         float s = 0.f;
         for (int bb = bs; bb < be; ++bb) s += dlogits[bb * NCLS + threadIdx.x];
         slab[W3_N + threadIdx.x] = s;
     }
+}
+
+__global__ __launch_bounds__(256) void fc_wgrad_kernel(const float* __restrict__ dlogits,
+                                                       const float* __restrict__ pooled,
+                                                       float* __restrict__ slabs, int B, int per) {
+    fcw_block(dlogits, pooled, slabs, B, per, blockIdx.x, blockIdx.y);
 }
 
 static inline int fcw_per(int B) {
@@ -825,6 +841,102 @@ extern "C" int slk_fc_wgrad_nslab(int B) {
     if (B <= 0) return 0;
     const int per = fcw_per(B);
     return (B + per - 1) / per;
+}
+
+// fc1's backward in one launch, two roles. The input gradient (dpooled = dlogits @ W3, + dp_amax) and the weight
+// gradient slabs both need only dlogits (+ W3 / + pooled) and not each other: one is all stores, the other nearly
+// all loads, so each block of this kernel takes ONE of the two jobs from its index. Nothing is shared but the
+// dispatch: each role keeps its own partition, threads and arithmetic, and writes bit for bit what its parent
+// kernel writes.
+//   wgrad role: fcw_block for (column block w % 9, batch slice w / 9), the parent's block order.
+//   dpooled role: what fc_head16_kernel<4> does, for FCB_S = 8 samples per 256-thread block: thread = float4
+//     column, 2304 / 256 = 9 trips for every wave (the parent's 512 threads ran 4.5); the next trip's ten W3
+//     float4 are loaded while this trip's FMAs run, ahead of its 8 row stores (class by class into the registers
+//     the trip has just finished with), the first set before the dlogits -> LDS prologue and its barrier. dl
+//     stays in LDS (broadcast reads), as in the parent.
+// The wgrad blocks take the first indices, the dpooled blocks follow as soon as a CU has room; the wgrad role
+// loads pooled non-temporally (pooled has no reader after this launch, dpooled has two, the conv2 dgrad and wgrad).
+// Measured at B = 4096 with these loads: with pooled in the Infinity Cache, as in the step,
+// this order 55.4 us, the two kinds alternating in proportion to their counts 57.8, dpooled blocks first 59.4,
+// the two launches 67.8 (quartiles of the first two overlap); with every operand from HBM 66.8 / 72.6 / 72.4 / 78.4.
+constexpr int FCB_T = 256, FCB_S = 8, FCB_W = FCB_T / 64, FCB_TRIPS = FC_K4 / FCB_T;
+static_assert(FC_K4 % FCB_T == 0 && FCB_S * NCLS <= FCB_T, "fc backward tiling");
+
+__global__ __launch_bounds__(FCB_T) void fc_backward_kernel(
+    const float* __restrict__ dlogits, const float* __restrict__ W3, const float* __restrict__ pooled,
+    float* __restrict__ dpooled, float* __restrict__ dp_amax, float* __restrict__ slabs, int B, int per,
+    unsigned nw) {
+    if (blockIdx.x < nw) {  // blocks [0, nw): the wgrad role; [nw, nw + ceil(B / 8)): the dpooled role
+        const unsigned w = blockIdx.x;
+        fcw_block<true>(dlogits, pooled, slabs, B, per, (int)(w % (FC_K4 / 256)), (int)(w / (FC_K4 / 256)));
+        return;
+    }
+    const unsigned d0 = blockIdx.x - nw;  // sample group
+    __shared__ __attribute__((aligned(16))) float dl[NCLS][FCB_S];  // class-major: a class's 8 values in two 16-B reads
+    __shared__ float mx[FCB_W][FCB_S];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int s0 = (int)d0 * FCB_S;
+    const int ns = min(FCB_S, B - s0);
+    const float4* W34 = reinterpret_cast<const float4*>(W3);
+    float4* D4 = reinterpret_cast<float4*>(dpooled + (size_t)s0 * P_SAMPLE);
+    float4 w[NCLS];
+#pragma unroll
+    for (int jj = 0; jj < NCLS; ++jj) w[jj] = W34[jj * FC_K4 + tid];
+    if (tid < FCB_S * NCLS) {
+        const int s = tid / NCLS, jj = tid - s * NCLS;
+        dl[jj][s] = s < ns ? dlogits[(size_t)(s0 + s) * NCLS + jj] : 0.f;
+    }
+    __syncthreads();
+    float dmx[FCB_S];
+#pragma unroll
+    for (int s = 0; s < FCB_S; ++s) dmx[s] = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < FCB_TRIPS; ++t) {
+        const float4* Wn = W34 + (t + 1 < FCB_TRIPS ? t + 1 : t) * FCB_T;  // (last trip: a re-read of its own set, unused)
+        float4* Dt = D4 + t * FCB_T;
+        // classes outermost: class jj's W3 value is dead after its 8 FMAs per component, so the next trip's takes
+        // its registers at once (no second set of 40). Each output is still the ten-term chain, classes in order.
+        float4 o[FCB_S];
+#pragma unroll
+        for (int s = 0; s < FCB_S; ++s) o[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int jj = 0; jj < NCLS; ++jj) {
+            // dl stays in LDS, read per class (broadcast): hoisted out, the 80 values took 172 VGPRs
+            asm volatile("" ::: "memory");
+            const float4 wj = w[jj];
+            w[jj] = Wn[jj * FC_K4 + tid];
+#pragma unroll
+            for (int s = 0; s < FCB_S; ++s) {
+                const float d = dl[jj][s];  // (0 for a row past the batch)
+                o[s].x = fmaf(d, wj.x, o[s].x);
+                o[s].y = fmaf(d, wj.y, o[s].y);
+                o[s].z = fmaf(d, wj.z, o[s].z);
+                o[s].w = fmaf(d, wj.w, o[s].w);
+            }
+        }
+        // the sums are complete HERE: without this the compiler sinks each sample's chain into its store's
+        // branch, sample-major again, with all of dl, w and the next trip's w live (184 VGPRs)
+#pragma unroll
+        for (int s = 0; s < FCB_S; ++s) asm volatile("" : "+v"(o[s].x), "+v"(o[s].y), "+v"(o[s].z), "+v"(o[s].w));
+#pragma unroll
+        for (int s = 0; s < FCB_S; ++s) {
+            if (s < ns) Dt[s * FC_K4 + tid] = o[s];
+            dmx[s] = fmaxf(dmx[s], fmaxf(fmaxf(fabsf(o[s].x), fabsf(o[s].y)), fmaxf(fabsf(o[s].z), fabsf(o[s].w))));
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < FCB_S; ++s) {
+        const float v = wave_max(dmx[s]);
+        if (lane == 0) mx[wave][s] = v;
+    }
+    __syncthreads();
+    if (tid < ns) {
+        float v = mx[0][tid];
+#pragma unroll
+        for (int ww = 1; ww < FCB_W; ++ww) v = fmaxf(v, mx[ww][tid]);
+        dp_amax[s0 + tid] = v;
+    }
 }
 
 // ============================================================================ C ABI
@@ -992,5 +1104,18 @@ extern "C" int slk_fc_wgrad(const float* dlogits, const float* pooled, float* sl
     const int per = fcw_per(B);
     dim3 grid(FC_K4 / 256, (B + per - 1) / per);
     fc_wgrad_kernel<<<grid, 256, 0, slk_stream(stream)>>>(dlogits, pooled, slabs, B, per);
+    return slk_launch_status();
+}
+
+// slk_fc_dgrad_amax + slk_fc_wgrad in one role-split launch (fc_backward_kernel): the same bits in every output
+extern "C" int slk_fc_backward(const float* dlogits, const float* W3, const float* pooled, float* dpooled,
+                               float* dp_amax, float* slabs, int B, void* stream) {
+    SLK_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(dlogits && W3 && pooled && dpooled && dp_amax && slabs);
+    const int per = fcw_per(B);
+    const unsigned nd = (unsigned)((B + FCB_S - 1) / FCB_S), nw = (unsigned)((FC_K4 / 256) * ((B + per - 1) / per));
+    fc_backward_kernel<<<nd + nw, FCB_T, 0, slk_stream(stream)>>>(dlogits, W3, pooled, dpooled, dp_amax, slabs, B, per,
+                                                                  nw);
     return slk_launch_status();
 }

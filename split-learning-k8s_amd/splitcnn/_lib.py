@@ -60,6 +60,7 @@ _SIGS = {
                             _P],
     "slk_fc_wgrad": [_P, _P, _P, _I, _P],
     "slk_fc_wgrad_nslab": [_I],
+    "slk_fc_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
     "slk_conv2_dgrad": [_P, _P, _P, _P, _I, _P],
     "slk_conv2_dgrad_direct": [_P, _P, _P, _P, _I, _P],
     "slk_conv2_wgrad": [_P, _P, _P, _P, _I, _P],

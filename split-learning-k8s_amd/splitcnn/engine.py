@@ -463,6 +463,9 @@ class ServerStage(_SgdRecipe):
         self.fc_split = True
         # ... with its logits and cross-entropy in one launch (slk_fc_logits_xent, round 6; bitwise the two)
         self.fc_one_launch = True
+        # ... and its fc1 wgrad and dpooled (+ dp_amax) as the two roles of one launch (slk_fc_backward; bitwise
+        # the two launches, which False restores; the non-split orders above always use the two)
+        self.fc_backward_one_launch = True
         self._buf = _Buffers()
 
     def bind_grads(self, view: torch.Tensor):
@@ -535,11 +538,16 @@ class ServerStage(_SgdRecipe):
                         loss_i, dlogits = ops.xent_soft_fwd_bwd(
                             logits, labels, grad_scale, soft, loss_i=self._b("loss_i", (B,)),
                             dlogits=self._b("dlogits", (B, 10)), err_flag=self.err_flag)
-            with TIMER("fc_wgrad"):
-                s3 = ops.fc_wgrad_slabs(dlogits, pooled, slabs=self._b("s3", (ops.fc_wgrad_nslab(B), ops.FC_SLAB)))
+            s3 = self._b("s3", (ops.fc_wgrad_nslab(B), ops.FC_SLAB))
             dpooled = self._b("dpooled", (B, 64, 12, 12))
-            with TIMER("fc_dgrad"):
-                ops.fc_dgrad(dlogits, W3, out=dpooled.view(B, 9216), dp_amax=dp_amax)
+            if self.fc_backward_one_launch:
+                with TIMER("fc_backward"):
+                    ops.fc_backward(dlogits, W3, pooled, dpooled=dpooled.view(B, 9216), dp_amax=dp_amax, slabs=s3)
+            else:
+                with TIMER("fc_wgrad"):
+                    ops.fc_wgrad_slabs(dlogits, pooled, slabs=s3)
+                with TIMER("fc_dgrad"):
+                    ops.fc_dgrad(dlogits, W3, out=dpooled.view(B, 9216), dp_amax=dp_amax)
         else:
             with TIMER("fc_xent"):
                 if soft is None:

@@ -411,6 +411,20 @@ def fc_wgrad_slabs(dlogits, pooled, slabs=None):
     return slabs
 
 
+def fc_backward(dlogits, W3, pooled, dpooled=None, dp_amax=None, slabs=None):
+    """fc_dgrad (with dp_amax) and fc_wgrad_slabs in one role-split launch (slk_fc_backward): the same bits in
+    dpooled [B, 9216], dp_amax [B] and slabs. Returns (dpooled, dp_amax, slabs)."""
+    B = batch_of(dlogits, (10,), "dlogits")
+    if _pooled_batch(pooled) != B:
+        raise ValueError("pooled / dlogits batch mismatch")
+    dpooled = _out(dpooled, (B, 9216), dlogits, name="dpooled")
+    dp_amax = _out(dp_amax, (B,), dlogits, name="dp_amax")
+    slabs = _out(slabs, (fc_wgrad_nslab(B), FC_SLAB), dlogits, name="slabs")
+    _lib.call("slk_fc_backward", _dev(dlogits, "dlogits"), _dev(W3, "fc1.weight", (10, 9216)), _dev(pooled, "pooled"),
+              _dev(dpooled, "dpooled"), _dev(dp_amax, "dp_amax", (B,)), _dev(slabs, "slabs"), B, _stream(dlogits))
+    return dpooled, dp_amax, slabs
+
+
 def _dpooled_batch(dpooled):
     return _pooled_batch(dpooled)
 

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--order", action="store_true", help="the launch-order knobs instead of the presets")
+    ap.add_argument("--only", default=None, help="with --order: a comma-separated subset of the variants (x3 always)")
     args = ap.parse_args()
     B = 4096
     dev = torch.device("cuda:0")
@@ -31,10 +32,11 @@ def main():
     # the default splits the head (fc_split); the fused-head orders set it off
     server_attrs = {"x3_fused_head": {"fc_split": False}, "x3_two_launch_head": {"fc_one_launch": False},
                     "x3_fcw_early": {"fc_split": False, "fc_wgrad_early": True},
-                    "x3_wgrad_first": {"wgrad_first": True}}
+                    "x3_wgrad_first": {"wgrad_first": True},
+                    "x3_fc_back_two_launches": {"fc_backward_one_launch": False}}
     ap_head = os.environ.get("AB_HEAD") == "1"  # the round-6 one-launch head vs the two launches only
     if args.order:
-        configs = {"x3": {}, **{k: {} for k in server_attrs}}
+        configs = {"x3": {}, **{k: {} for k in server_attrs if args.only is None or k in args.only.split(",")}}
     if ap_head:
         configs = {"x3": {}, "x3_two_launch_head": {}}
     for name, kw in configs.items():
