@@ -20,205 +20,55 @@ HIP graph.
 """
 from __future__ import annotations
 
-import contextlib
-from collections import defaultdict
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import ops
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .model_def import ModelPartA, ModelPartB
-from .optim import EMA, LARS, SGD, ClipNorm, LRSchedule, check_clip, check_ema, is_layerwise
+from .optim import EMA, SGD, ClipNorm, LRSchedule, check_clip, check_ema
+from .recipe import TIMER, Seg, StageRecipe, _flatten_params, ema_update   # TIMER: bench.py and the tools take it from here
 
 LR = 0.01  # optim.SGD(lr=0.01) on both sides (client_part.py:17, server_part.py:15)
 
 
-class KernelTimer:
-    """HIP-event timing of named launches on the launching (current) stream. Disabled by default;
-    bench.py enables it for its per-kernel pass. Never enable inside graph capture."""
+class _SgdRecipe(StageRecipe):
+    """The SGD family of a K2 stage (recipe.StageRecipe holds what it shares with K5). The default is the
+    reference's optim.SGD(lr) on slk_sgd_*, without state or a counter, so whatever needs the counter (a schedule,
+    clip=, ema=) selects slk_sgdm_* with the momentum buffers `buf`. The clipped step is slk_sgdm_clip_multi, the
+    layer-wise recipe optim.LARS (slk_reduce_tnorm_multi then slk_lars_multi). The callers time the stage's whole
+    update (TIMER sgd_client / sgd_server), so nothing here does."""
 
-    def __init__(self):
-        self.enabled = False
-        self._ev: Dict[str, list] = defaultdict(list)
-
-    @contextlib.contextmanager
-    def __call__(self, name: str):
-        if not self.enabled:
-            yield
-            return
-        s = torch.cuda.Event(enable_timing=True)
-        e = torch.cuda.Event(enable_timing=True)
-        s.record()
-        yield
-        e.record()
-        self._ev[name].append((s, e))
-
-    def reset(self):
-        self._ev.clear()
-
-    def summary(self) -> Dict[str, Dict[str, float]]:
-        torch.cuda.synchronize()
-        out = {}
-        for k, v in self._ev.items():
-            ms = [s.elapsed_time(e) for s, e in v]
-            out[k] = {"avg_ms": sum(ms) / len(ms), "min_ms": min(ms), "n": len(ms)}
-        return out
-
-
-TIMER = KernelTimer()
-
-
-def _flatten_params(params: List[nn.Parameter], device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Move `params` into one flat fp32 block; each Parameter becomes a view of it."""
-    n = sum(p.numel() for p in params)
-    flat = torch.empty(n, dtype=torch.float32, device=device)
-    gflat = torch.zeros(n, dtype=torch.float32, device=device)
-    off = 0
-    for p in params:
-        k = p.numel()
-        flat[off:off + k].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
-        p.data = flat[off:off + k].view(p.shape)
-        p.grad = gflat[off:off + k].view(p.shape)
-        off += k
-    return flat, gflat
-
-
-class _SgdRecipe:
-    """Optimizer state of a K2 stage. Without a config (optim=None, schedule=None) the stage runs the
-    reference's optim.SGD(lr) on slk_sgd_*, `lr` a by-value kernel argument (frozen into a captured graph).
-    With an optim.SGD config and / or an optim.LRSchedule it runs slk_sgdm_*: the momentum buffers `buf` (one
-    flat block like params / grads), the device counter `step_ctr` of completed optimizer steps and the
-    schedule's device table, all read by the kernels, so graph replays follow them. The stage advances
-    step_ctr after its optimizer launches unless a trainer that shares one counter between both stages does
-    (auto_tick False). With an optim.ClipNorm (`clip`, which like a schedule selects slk_sgdm_*) every step is
-    two launches, slk_reduce_sqnorm_multi then slk_sgdm_clip_multi: the stage's gradient is clipped by its own
-    global L2 norm before weight decay; `grads` keeps the unclipped gradient and `clip_out` the last step's
-    device [norm, coef]. With an optim.LARS every step is slk_reduce_tnorm_multi then slk_lars_multi over the
-    stage's [weight | bias] pairs (PAIRS: (lo, hi, weight elements) of the flat block); `trust_out` keeps
-    every tensor's [w_norm, g_norm, ratio] of the last step in TENSORS' order. With an optim.EMA (`ema_cfg`, which
-    selects slk_sgdm_* as well: the average needs the counter) the stage owns `ema`, a flat block like params that
-    starts as their copy, and every step is optimizer launch(es), slk_ema_multi, tick; a trainer that shares the
-    counter (auto_tick False) launches the update of both stages itself, in front of its tick."""
-
-    def _init_optim(self, lr, optim, schedule, clip=None, ema=None):
-        if optim is not None and not isinstance(optim, SGD):
-            raise TypeError(f"optim: expected splitcnn.optim.SGD or None, got {type(optim).__name__}")
-        check_clip(clip)
-        check_ema(ema)
-        if optim is None and (schedule is not None or clip is not None or ema is not None):
-            optim = SGD(lr)
-        if is_layerwise(optim) and clip is not None:
-            raise ValueError(f"{type(optim).__name__} is not combined with clip= (the trust ratio already bounds "
-                             "every tensor's step by its own norms)")
-        self.optim, self.schedule = optim, None
-        self.clip = self.clip_out = self.trust_out = None
-        self.buf = self.step_ctr = None
-        self.ema = self.ema_cfg = None
-        self.auto_tick = True
-        if optim is None:
-            return
-        if ema is not None:
-            self.ema_cfg = ema.to(self.device)
-            self.ema = self.params.clone()
-        self.lr = optim.lr
-        self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
-        self.buf = torch.zeros_like(self.params)
-        self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if clip is not None:
-            self.clip = clip.to(self.device)
-            self.clip_out = torch.zeros(2, dtype=torch.float32, device=self.device)   # [norm, coef] of the last step
-        if isinstance(optim, LARS):   # [w_norm, g_norm, ratio] of every tensor's last step, in TENSORS' order
-            self.trust_out = torch.zeros(2 * len(self.PAIRS), 3, dtype=torch.float32, device=self.device)
-
-    def _trust_group(self, segs):
-        """This stage's [W | b] pairs as one group of the LARS launches: its own partials and trust_out. A
-        (param, grad, buf, slabs) tuple over the whole stage (step(): the gradient block in place; a fused
-        trainer's client segment) becomes one slice per pair."""
-        out = []
-        for g in segs:
-            if g[0].numel() == self.PAIRS[-1][1] and len(self.PAIRS) > 1:
-                out += [tuple(t[lo:hi] if t is not None else None for t in g[:3]) + (g[3][:, lo:hi], nw)
-                        for lo, hi, nw in self.PAIRS]
-            else:
-                lo = g[0].storage_offset() - self.params.storage_offset()
-                nw = {(a, b): w for a, b, w in self.PAIRS}.get((lo, lo + g[0].numel()))
-                if nw is None:
-                    raise ValueError(f"{type(self.optim).__name__}: a segment must be one [weight | bias] pair")
-                out.append(g + (nw,))
-        need = ops.trust_partials_needed(out)
-        self.trust_nblk = [ops.reduce_sqnorm_nblk(g[3].shape[1], g[3].shape[0]) for g in out]   # partials per pair
-        return (self._buf.get("trust_partials", (need,), torch.float32, self.device), self.trust_out, out)
-
-    def _clip_group(self, segs):
-        """This stage's segments as one group of the clip launches: its own partials and [norm, coef]."""
-        need = self.clip_npart = ops.clip_partials_needed(segs)   # partials of this stage's last clipped step
-        return (self._buf.get("clip_partials", (need,), torch.float32, self.device), self.clip_out, segs)
+    CONFIG, STATE = SGD, ("buf",)
 
     def _sgdm(self, segments, loss=None, multi=False):
-        """slk_sgdm_* on (lo, hi, slabs) slices of this stage (slabs [nslab, hi - lo]) and ready
-        (param, grad, buf, slabs) tuples: separate launches, or ONE with the loss log (multi). With `clip`
-        always the two clip launches (the loss log rides in the first); another clipped stage's
-        optim_segment joins them as a group of its own."""
-        grouped = self.clip is not None or is_layerwise(self.optim)   # another stage joins as its own group
-        if any(len(g) == (4 if grouped else 5) and g[0] is not self.params for g in segments):
-            raise ValueError("a segment of another stage must share this stage's clip= (both clipped by one "
-                             "optim.ClipNorm, or neither) and its layer-wise recipe")
-        segs = [(self.params[g[0]:g[1]], self.grads[g[0]:g[1]], self.buf[g[0]:g[1]], g[2]) if len(g) == 3 else g
-                for g in segments]
-        kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
-        if is_layerwise(self.optim):
-            groups = [self._trust_group([g for g in segs if len(g) == 4])]
-            groups += [g[4]._trust_group([g[:4]]) for g in segs if len(g) == 5]
-            ops.reduce_tnorm_multi(groups, loss=loss)
-            ops.lars_multi(groups, **kw)
-        elif self.clip is not None:
-            groups = [self._clip_group([g for g in segs if len(g) == 4])]
-            groups += [g[4]._clip_group([g[:4]]) for g in segs if len(g) == 5]
-            ops.reduce_sqnorm_multi(groups, loss=loss)
-            ops.sgdm_clip_multi(groups, self.clip.value, **kw)
-        elif multi:
+        """One optimizer step on recipe.Seg segments ((lo, hi, slabs) slices of this stage are taken too): separate
+        launches, or ONE with the loss log (multi); another stage's optim_segment joins them."""
+        self._step([g if type(g) is Seg else self.seg(*g) for g in segments], loss, multi)
+
+    def _by_value(self, segs, loss, multi):
+        if multi:
+            ops.sgd_multi_from_slabs(segs, self.lr, loss=loss)
+        else:
+            for g in segs:
+                ops.sgd_from_slabs(*g, self.lr)
+
+    def _plain(self, segs, loss, multi, kw):
+        if multi:
             ops.sgdm_multi_from_slabs(segs, loss=loss, **kw)
         else:
             for g in segs:
                 ops.sgdm_from_slabs(*g, **kw)
 
-    def _tick(self):
-        if self.auto_tick:
-            ema_update([self])
-            ops.tick(self.step_ctr)
+    def _clipped(self, groups, loss, kw):
+        ops.reduce_sqnorm_multi(groups, loss=loss)
+        ops.sgdm_clip_multi(groups, self.clip.value, **kw)
 
-    def _weights(self, shapes, ema=False):
-        """Views of the parameter block, or of the averaged block (ema), in the tensors' own shapes."""
-        if ema and self.ema is None:
-            raise RuntimeError(f"{type(self).__name__}: weights='ema' needs a stage built with ema= (optim.EMA)")
-        flat, out, off = self.ema if ema else self.params, [], 0
-        for shp in shapes:
-            k = 1
-            for d in shp:
-                k *= d
-            out.append(flat[off:off + k].view(shp))
-            off += k
-        return out
-
-    def optim_segment(self, slabs):
-        """This stage's whole update as a segment of another stage's slk_sgdm_multi_from_slabs launch; with
-        `clip` (shared with that stage) a group of its own in that stage's two clip launches."""
-        seg = (self.params, self.grads, self.buf, slabs)
-        return seg if self.clip is None and not is_layerwise(self.optim) else seg + (self,)
-
-
-def ema_update(stages):
-    """slk_ema_multi over the averaged blocks of `stages` (those built with ema=; they share the config and the
-    counter): ONE launch, after their optimizer launches and before the counter's tick."""
-    stages = [st for st in stages if st.ema is not None]
-    if not stages:
-        return
-    cfg = stages[0].ema_cfg
-    with TIMER("ema_multi"):
-        ops.ema_multi([(st.ema, st.params) for st in stages], cfg.value, stages[0].step_ctr, cfg.start, cfg.warmup)
+    def _layerwise(self, groups, loss, kw):
+        ops.reduce_tnorm_multi(groups, loss=loss)
+        ops.lars_multi(groups, **kw)
 
 
 class _Buffers:
@@ -306,7 +156,7 @@ class ClientStage(_SgdRecipe):
         self.lr = lr
         self.params, self.grads = _flatten_params(
             [self.model.conv1.weight, self.model.conv1.bias], self.device)
-        self._init_optim(lr, optim, schedule, clip, ema)
+        self._init_optim(optim, schedule, clip, ema)
         self._buf = _Buffers()
         self._x = None
         self._act = None
@@ -401,11 +251,8 @@ class ClientStage(_SgdRecipe):
         """optimizer.step() from gradient slabs produced elsewhere (the server's fused x3 dgrad,
         ServerStage.forward_backward(client_fuse=...)): one fused reduce + SGD launch."""
         with TIMER("sgd_client"):
-            if self.optim is None:
-                ops.sgd_from_slabs(self.params, self.grads, slabs, self.lr)
-            else:
-                self._sgdm([(0, ops.CLIENT_NPARAM, slabs)])
-                self._tick()
+            self._sgdm([self.seg(0, ops.CLIENT_NPARAM, slabs)])
+            self._tick()
 
     def backward(self, cut_grad: torch.Tensor, x: Optional[torch.Tensor] = None,
                  act: Optional[torch.Tensor] = None, accumulate: bool = False) -> None:
@@ -419,7 +266,7 @@ class ClientStage(_SgdRecipe):
             if self.optim is None:
                 ops.sgd(self.params, self.grads, self.lr)
             else:
-                self._sgdm([(self.params, None, self.buf, self.grads.view(1, -1))])
+                self._sgdm([self.grads_segment()])
                 self._tick()
 
 
@@ -446,7 +293,7 @@ class ServerStage(_SgdRecipe):
         m = self.model
         self.params, self.grads = _flatten_params(
             [m.conv2.weight, m.conv2.bias, m.fc1.weight, m.fc1.bias], self.device)
-        self._init_optim(lr, optim, schedule, clip, ema)
+        self._init_optim(optim, schedule, clip, ema)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
@@ -597,15 +444,15 @@ class ServerStage(_SgdRecipe):
                 s3 = ops.fc_wgrad_slabs(dlogits, pooled, slabs=self._b("s3", (ops.fc_wgrad_nslab(B), ops.FC_SLAB)))
         return cut_grad, loss_i, s2, s3
 
+    def _slab_segments(self, s2, s3):
+        """The stage's two slab kinds, [conv2 | fc1], as segments of its optimizer step."""
+        return [self.seg(0, ops.CONV2_SLAB, s2), self.seg(ops.CONV2_SLAB, ops.SERVER_NPARAM, s3)]
+
     def apply_grad_slabs(self, s2, s3):
         """optimizer.step() (server_part.py:52): two fused reduce+SGD launches, one per slab kind."""
         with TIMER("sgd_server"):
-            if self.optim is None:
-                ops.sgd_from_slabs(self.params[:ops.CONV2_SLAB], self.grads[:ops.CONV2_SLAB], s2, self.lr)
-                ops.sgd_from_slabs(self.params[ops.CONV2_SLAB:], self.grads[ops.CONV2_SLAB:], s3, self.lr)
-            else:
-                self._sgdm([(0, ops.CONV2_SLAB, s2), (ops.CONV2_SLAB, ops.SERVER_NPARAM, s3)])
-                self._tick()
+            self._sgdm(self._slab_segments(s2, s3))
+            self._tick()
 
     def reduce_grads(self, s2, s3, accumulate: bool = False):
         """Reduce slabs into the flat gradient block without stepping (micro-batches, all-reduce)."""
@@ -625,7 +472,7 @@ class ServerStage(_SgdRecipe):
             if self.optim is None:
                 ops.sgd(self.params, self.grads, self.lr)
             else:
-                self._sgdm([(self.params, None, self.buf, self.grads.view(1, -1))])
+                self._sgdm([self.grads_segment()])
                 self._tick()
 
     def log_loss(self, values, scale: Optional[float] = None, step: Optional[int] = None):
@@ -640,10 +487,9 @@ class ServerStage(_SgdRecipe):
                      cut_grad: Optional[torch.Tensor] = None, act_amax: Optional[torch.Tensor] = None,
                      act16: Optional[torch.Tensor] = None, client_fuse=None, extra_segments=()):
         """One /forward_pass request (server_part.py:38-58): returns (cut_grad, loss_i). The mean
-        loss for `step` lands in the device loss log. `extra_segments`: further (param, grad, slabs)
-        reduce+SGD segments at this stage's lr run in the same optimizer launch (the fused trainer's
-        client update, whose slabs the dgrad wrote); with an optimizer config they are (param, grad, buf,
-        slabs) (ClientStage.optim_segment) and step by this stage's recipe, schedule and counter."""
+        loss for `step` lands in the device loss log. `extra_segments`: further segments (recipe.Seg: the fused
+        trainer's client update, ClientStage.optim_segment, whose slabs the dgrad wrote) run in the same
+        optimizer launch and step by this stage's recipe: its lr, or its config, schedule and counter."""
         B = labels.shape[0]
         cut_grad, loss_i, s2, s3 = self.forward_backward(act, labels, 1.0 / B, cut_grad=cut_grad,
                                                          act_amax=act_amax, act16=act16, client_fuse=client_fuse)
@@ -651,26 +497,19 @@ class ServerStage(_SgdRecipe):
             # optimizer.step() + log_metric in ONE launch (bit-identical to the three below); measured
             # -10 us per step at B = 4096 (tools/ab_step.py). The client's SGD stays a separate launch
             # after its wgrad: moving that wgrad ahead of the server's update measured +25-35 us.
-            k = ops.CONV2_SLAB
             loss = (loss_i, 1.0 / B, self.loss_log.ring, self.loss_log.counter)
             with TIMER("sgd_server"):
-                if self.optim is None:
-                    ops.sgd_multi_from_slabs([(self.params[:k], self.grads[:k], s2),
-                                              (self.params[k:], self.grads[k:], s3), *extra_segments],
-                                             self.lr, loss=loss)
-                else:
-                    self._sgdm([(0, k, s2), (k, ops.SERVER_NPARAM, s3), *extra_segments], loss=loss, multi=True)
-                    self._tick()
+                self._sgdm([*self._slab_segments(s2, s3), *extra_segments], loss=loss, multi=True)
+                self._tick()
             if step is not None:
                 self.loss_log.note_step(step)
-        elif self.optim is None:
+        elif self.optim is None:   # the by-value recipe steps the extra segments after the loss log
             self.apply_grad_slabs(s2, s3)
             self.log_loss(loss_i, step=step)
-            for prm, grd, sl in extra_segments:
-                ops.sgd_from_slabs(prm, grd, sl, self.lr)
+            self._sgdm(extra_segments)
         else:
             with TIMER("sgd_server"):
-                self._sgdm([(0, ops.CONV2_SLAB, s2), (ops.CONV2_SLAB, ops.SERVER_NPARAM, s3), *extra_segments])
+                self._sgdm([*self._slab_segments(s2, s3), *extra_segments])
                 self._tick()
             self.log_loss(loss_i, step=step)
         return cut_grad, loss_i
@@ -794,13 +633,12 @@ class SplitTrainer(GraphedTrainer):
             # dgrad has run; bit-identical to step_from_slabs) when both stages step at one lr
             s = self.server
             if s.optim is None and c.optim is None:
-                one, seg = c.lr == s.lr, (c.params, c.grads, slabs)
+                one = c.lr == s.lr
             else:   # one recipe, one schedule and one counter (a config given to this trainer)
                 one = (c.optim is s.optim and c.schedule is s.schedule and c.step_ctr is s.step_ctr
                        and c.clip is s.clip)
-                seg = c.optim_segment(slabs) if one else None
             s.step_request(act, y, act_amax=c._act_amax, act16=a16, client_fuse=(x, c._relu_bits, slabs),
-                           extra_segments=[seg] if one else ())
+                           extra_segments=[c.optim_segment(slabs)] if one else ())
             if not one:
                 c.step_from_slabs(slabs)
         else:

@@ -8,6 +8,7 @@ Nothing here synchronises, so a sequence of these calls can be captured in a HIP
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -673,6 +674,18 @@ def sgdm_multi_from_slabs(segments, lr_table, step, momentum=0.0, dampening=0.0,
               float(dampening), float(weight_decay), int(bool(nesterov)), *_loss_args(loss), _stream(stream_of))
 
 
+def _adam_columns(segments):
+    """Checked columns (param, grad, m, v, slabs, nslab, n) of (param, grad, m, v, slabs) segments; grad may be None."""
+    cols = [[], [], [], [], [], [], []]
+    for param, grad, m, v, sl in segments:
+        nsl, n = sl.shape
+        row = (_dev(param, "param", (n,)), _dev(grad, "grad", (n,)) if grad is not None else None,
+               _dev(m, "m", (n,)), _dev(v, "v", (n,)), _dev(sl, "slabs"), int(nsl), int(n))
+        for c, val in zip(cols, row):
+            c.append(val)
+    return cols
+
+
 def adamw_from_slabs(param, grad, m, v, slabs, lr_table, step, beta1, beta2, eps, weight_decay=0.0, decoupled=True):
     """torch.optim.AdamW's (decoupled) or torch.optim.Adam(weight_decay)'s step from sum(slabs), t = step + 1,
     the rate read from the device table (slk_adamw_from_slabs); grad may be None."""
@@ -689,20 +702,36 @@ def adamw_multi_from_slabs(segments, lr_table, step, beta1, beta2, eps, weight_d
     k = len(segments)
     if not 1 <= k <= 4:
         raise ValueError("adamw_multi_from_slabs: 1 to 4 segments")
-    cols = [[], [], [], [], [], [], []]
-    for param, grad, m, v, sl in segments:
-        nsl, n = sl.shape
-        row = (_dev(param, "param", (n,)), _dev(grad, "grad", (n,)) if grad is not None else None,
-               _dev(m, "m", (n,)), _dev(v, "v", (n,)), _dev(sl, "slabs"), int(nsl), int(n))
-        for c, val in zip(cols, row):
-            c.append(val)
-    _lib.call("slk_adamw_multi_from_slabs", *_host_arrays(cols), k, *_lr_args(lr_table, step), float(beta1),
-              float(beta2), float(eps), float(weight_decay), int(bool(decoupled)), _stream(segments[0][0]))
+    _lib.call("slk_adamw_multi_from_slabs", *_host_arrays(_adam_columns(segments)), k, *_lr_args(lr_table, step),
+              float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(decoupled)),
+              _stream(segments[0][0]))
+
+
+def adam_from_slabs(param, grad, m, v, slabs, lr, beta1, beta2, eps, step):
+    """torch.optim.Adam's step from sum(slabs), t = step + 1, `lr` by value (slk_adam_from_slabs: the default K5
+    recipe); grad may be None. The caller advances `step` (tick) after the stage's launches."""
+    nslab, n = slabs.shape
+    gptr = _dev(grad, "grad", (n,)) if grad is not None else None
+    _lib.call("slk_adam_from_slabs", _dev(param, "param", (n,)), gptr, _dev(m, "m", (n,)), _dev(v, "v", (n,)),
+              _dev(slabs, "slabs"), nslab, n, float(lr), float(beta1), float(beta2), float(eps),
+              _dev(step, "step", (1,), torch.int32), _stream(param))
+
+
+def adam_multi_from_slabs(segments, lr, beta1, beta2, eps, step):
+    """ONE launch: adam_from_slabs(param, grad, m, v, slabs, ...) for each of `segments` (<= 4), bit-identical to
+    the separate launches (slk_adam_multi_from_slabs)."""
+    k = len(segments)
+    if not 1 <= k <= 4:
+        raise ValueError("adam_multi_from_slabs: 1 to 4 segments")
+    _lib.call("slk_adam_multi_from_slabs", *_host_arrays(_adam_columns(segments)), k, float(lr), float(beta1),
+              float(beta2), float(eps), _dev(step, "step", (1,), torch.int32), _stream(segments[0][0]))
 
 
 # ---- global-norm gradient clipping: reduce + square-norm partials, then the clipped step (two launches)
+@functools.lru_cache(maxsize=None)
 def reduce_sqnorm_nblk(n, nslab):
-    """Blocks (= square-norm partials) that reduce_sqnorm_multi spends on one [nslab, n] slab set."""
+    """Blocks (= square-norm partials) that reduce_sqnorm_multi spends on one [nslab, n] slab set (a pure function
+    of the two sizes: remembered, since every clipped or layer-wise step asks it three times per segment)."""
     return _lib.query("slk_reduce_sqnorm_nblk", int(n), int(nslab))
 
 
@@ -711,40 +740,54 @@ def clip_partials_needed(segments):
     return sum(reduce_sqnorm_nblk(seg[-1].shape[1], seg[-1].shape[0]) for seg in segments)
 
 
-def _clip_args(groups, who, width):
-    """The host arrays both clip passes share. groups = [(partials, norm_out, segments)], one per stage;
-    a segment is `width` tensors (param, grad, state ..., slabs). grad None: the [1, n] slabs ARE the
-    gradient block (reduced earlier), read in place. Returns (columns of the tensors' pointers, nslab, n,
-    group ids, partials pointers, norm_out pointers, a tensor to take the stream from)."""
+def _group_args(groups, who, width, trust=False):
+    """The host arrays the two passes of a clipped or (trust) layer-wise step share. groups = [(partials, out,
+    segments)], one per stage, out its norm_out [norm, coef] or trust_out; a segment is `width` tensors (param,
+    grad, state ..., slabs) and under `trust` nw, the number of weight elements of the [W | b] pair (the rest is
+    the bias). grad None: the [1, n] slabs ARE the gradient block (reduced earlier), read in place. Returns
+    (columns of the tensors' pointers, nslab, n, nw (empty without trust), group ids, partials pointers, out
+    pointers, a tensor to take the stream from)."""
     cols = [[] for _ in range(width)]
-    nslab, ns, gid, parts, outs = [], [], [], [], []
-    for g, (partials, norm_out, segments) in enumerate(groups):
+    nslab, ns, nws, gid, parts, outs = [], [], [], [], [], []
+    for g, (partials, out, segments) in enumerate(groups):
         if not segments:
             raise ValueError(f"{who}: group {g} has no segment")
         for seg in segments:
-            if len(seg) != width:
-                raise ValueError(f"{who}: a segment is {width} tensors")
-            sl = seg[-1]
+            if len(seg) != width + trust:
+                raise ValueError(f"{who}: a segment is {width} tensors" + (" and nw" if trust else ""))
+            sl = seg[width - 1]
             nsl, n = sl.shape
+            if trust:
+                nws.append(int(seg[-1]))
+                if not 0 <= nws[-1] <= n:
+                    raise ValueError(f"{who}: nw = {nws[-1]} outside [0, n = {n}]")
             grad = seg[1]
             if grad is None:
                 if nsl != 1:
                     raise ValueError(f"{who}: a segment without grad steps in place from ONE slab")
                 grad = sl.view(-1)
             names = ("param", "grad") + ("state",) * (width - 3)
-            for c, t, name in zip(cols, (seg[0], grad) + tuple(seg[2:-1]), names):
+            for c, t, name in zip(cols, (seg[0], grad) + tuple(seg[2:width - 1]), names):
                 c.append(_dev(t, name, (n,)) if t is not None else None)
             cols[-1].append(_dev(sl, "slabs"))
             nslab.append(int(nsl))
             ns.append(int(n))
             gid.append(g)
-        if _dev(partials, "partials") and partials.numel() < clip_partials_needed(segments):
-            raise ValueError(f"{who}: group {g} needs {clip_partials_needed(segments)} partials, got {partials.numel()}")
+        need = (trust_partials_needed if trust else clip_partials_needed)(segments)
+        if trust:
+            if _dev(partials, "partials") % 16 or partials.numel() < need:
+                raise ValueError(f"{who}: group {g} needs {need} partials (16-byte aligned), got {partials.numel()}")
+            if _dev(out, "trust_out") and out.numel() < 6 * len(segments):
+                raise ValueError(f"{who}: group {g} needs a trust_out of [{2 * len(segments)}, 3]")
+        else:
+            if _dev(partials, "partials") and partials.numel() < need:
+                raise ValueError(f"{who}: group {g} needs {need} partials, got {partials.numel()}")
+            _dev(out, "norm_out", (2,))
         parts.append(partials.data_ptr())
-        outs.append(_dev(norm_out, "norm_out", (2,)))
+        outs.append(out.data_ptr())
     if not 1 <= len(gid) <= 4:
         raise ValueError(f"{who}: 1 to 4 segments")
-    return cols, nslab, ns, gid, parts, outs, groups[0][2][0][0]
+    return cols, nslab, ns, nws, gid, parts, outs, groups[0][2][0][0]
 
 
 def reduce_sqnorm_multi(groups, loss=None):
@@ -753,7 +796,7 @@ def reduce_sqnorm_multi(groups, loss=None):
     block into its group's `partials`; plus loss_log(*loss). groups = [(partials, norm_out, segments)] as
     for sgdm_clip_multi / adamw_clip_multi (norm_out is not written here)."""
     width = len(groups[0][2][0])
-    cols, nslab, ns, gid, parts, _, like = _clip_args(groups, "reduce_sqnorm_multi", width)
+    cols, nslab, ns, _, gid, parts, _, like = _group_args(groups, "reduce_sqnorm_multi", width)
     _lib.call("slk_reduce_sqnorm_multi", *_host_arrays([cols[1], cols[-1], nslab, ns, gid], n_int=3), len(gid),
               *_host_arrays([parts], n_int=0), len(groups), *_loss_args(loss), _stream(like))
 
@@ -763,7 +806,7 @@ def sgdm_clip_multi(groups, max_norm, lr_table, step, momentum=0.0, dampening=0.
     group (one stage) norm = sqrt(sum of its partials), coef = min(1, max_norm / (norm + 1e-6)) -> norm_out,
     then sgdm_from_slabs' update from coef * grad. groups = [(partials, norm_out, [(param, grad, buf, slabs),
     ...])]; grad stays the unclipped gradient; max_norm is a device f32[1] (optim.ClipNorm.value)."""
-    cols, nslab, ns, gid, parts, outs, like = _clip_args(groups, "sgdm_clip_multi", 4)
+    cols, nslab, ns, _, gid, parts, outs, like = _group_args(groups, "sgdm_clip_multi", 4)
     _lib.call("slk_sgdm_clip_multi", *_host_arrays(cols[:3] + [nslab, ns, gid], n_int=3), len(gid),
               *_host_arrays([parts, outs], n_int=0), len(groups), _dev(max_norm, "max_norm", (1,)),
               *_lr_args(lr_table, step), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
@@ -773,7 +816,7 @@ def sgdm_clip_multi(groups, max_norm, lr_table, step, momentum=0.0, dampening=0.
 def adamw_clip_multi(groups, max_norm, lr_table, step, beta1, beta2, eps, weight_decay=0.0, decoupled=True):
     """Pass 2 for torch.optim.AdamW / Adam (slk_adamw_clip_multi): as sgdm_clip_multi with segments
     (param, grad, m, v, slabs) and adamw_from_slabs' update from coef * grad."""
-    cols, nslab, ns, gid, parts, outs, like = _clip_args(groups, "adamw_clip_multi", 5)
+    cols, nslab, ns, _, gid, parts, outs, like = _group_args(groups, "adamw_clip_multi", 5)
     _lib.call("slk_adamw_clip_multi", *_host_arrays(cols[:4] + [nslab, ns, gid], n_int=3), len(gid),
               *_host_arrays([parts, outs], n_int=0), len(groups), _dev(max_norm, "max_norm", (1,)),
               *_lr_args(lr_table, step), float(beta1), float(beta2), float(eps), float(weight_decay),
@@ -787,55 +830,12 @@ def trust_partials_needed(segments):
     return 4 * sum(reduce_sqnorm_nblk(seg[-2].shape[1], seg[-2].shape[0]) for seg in segments)
 
 
-def _trust_args(groups, who, width):
-    """The host arrays both layer-wise passes share. groups = [(partials, trust_out, segments)], one per stage; a
-    segment is `width` tensors (param, grad, state ..., slabs) and nw, the number of weight elements of the
-    [W | b] pair (the rest is the bias). grad None: the [1, n] slabs ARE the gradient block, read in place.
-    Returns (columns of the tensors' pointers, nslab, n, nw, group ids, partials pointers, trust_out pointers, a
-    tensor to take the stream from)."""
-    cols = [[] for _ in range(width)]
-    nslab, ns, nws, gid, parts, outs = [], [], [], [], [], []
-    for g, (partials, trust_out, segments) in enumerate(groups):
-        if not segments:
-            raise ValueError(f"{who}: group {g} has no segment")
-        for seg in segments:
-            if len(seg) != width + 1:
-                raise ValueError(f"{who}: a segment is {width} tensors and nw")
-            sl, nw = seg[-2], int(seg[-1])
-            nsl, n = sl.shape
-            if not 0 <= nw <= n:
-                raise ValueError(f"{who}: nw = {nw} outside [0, n = {n}]")
-            grad = seg[1]
-            if grad is None:
-                if nsl != 1:
-                    raise ValueError(f"{who}: a segment without grad steps in place from ONE slab")
-                grad = sl.view(-1)
-            names = ("param", "grad") + ("state",) * (width - 3)
-            for c, t, name in zip(cols, (seg[0], grad) + tuple(seg[2:-2]), names):
-                c.append(_dev(t, name, (n,)) if t is not None else None)
-            cols[-1].append(_dev(sl, "slabs"))
-            nslab.append(int(nsl))
-            ns.append(int(n))
-            nws.append(nw)
-            gid.append(g)
-        need = trust_partials_needed(segments)
-        if _dev(partials, "partials") % 16 or partials.numel() < need:
-            raise ValueError(f"{who}: group {g} needs {need} partials (16-byte aligned), got {partials.numel()}")
-        if _dev(trust_out, "trust_out") and trust_out.numel() < 6 * len(segments):
-            raise ValueError(f"{who}: group {g} needs a trust_out of [{2 * len(segments)}, 3]")
-        parts.append(partials.data_ptr())
-        outs.append(trust_out.data_ptr())
-    if not 1 <= len(gid) <= 4:
-        raise ValueError(f"{who}: 1 to 4 segments")
-    return cols, nslab, ns, nws, gid, parts, outs, groups[0][2][0][0]
-
-
 def reduce_tnorm_multi(groups, loss=None):
     """Pass 1 of a LARS step (slk_reduce_tnorm_multi), ONE launch: every segment's grad = the fixed-order sum of
     its slabs and four partials per block, [g2_W, p2_W, g2_b, p2_b], into its group's `partials`; plus
     loss_log(*loss). groups = [(partials, trust_out, [(param, grad, buf, slabs, nw), ...])] as for lars_multi
     (trust_out is not written here)."""
-    cols, nslab, ns, nws, gid, parts, _, like = _trust_args(groups, "reduce_tnorm_multi", 4)
+    cols, nslab, ns, nws, gid, parts, _, like = _group_args(groups, "reduce_tnorm_multi", 4, trust=True)
     _lib.call("slk_reduce_tnorm_multi", *_host_arrays([cols[1], cols[0], cols[-1], nslab, ns, nws, gid], n_int=4),
               len(gid), *_host_arrays([parts], n_int=0), len(groups), *_loss_args(loss), _stream(like))
 
@@ -846,7 +846,7 @@ def lars_multi(groups, lr_table, step, momentum=0.0, dampening=0.0, weight_decay
     weight and the bias of each segment) ratio = trust_coef * |w| / (|g| + wd * |w| + eps) (1 where a norm is
     0), then sgdm_from_slabs' momentum arithmetic on ratio * (g + wd * w). trust_out[2k], [2k + 1] =
     [w_norm, g_norm, ratio] of the weight and the bias of the group's k-th segment."""
-    cols, nslab, ns, nws, gid, parts, outs, like = _trust_args(groups, "lars_multi", 4)
+    cols, nslab, ns, nws, gid, parts, outs, like = _group_args(groups, "lars_multi", 4, trust=True)
     _lib.call("slk_lars_multi", *_host_arrays(cols[:3] + [nslab, ns, nws, gid], n_int=4), len(gid),
               *_host_arrays([parts, outs], n_int=0), len(groups), *_lr_args(lr_table, step), float(momentum),
               float(dampening), float(weight_decay), int(bool(nesterov)), float(trust_coef), float(eps),
@@ -858,7 +858,7 @@ def lamb_moments_multi(groups, step, beta1, beta2, eps, weight_decay=0.0, exclud
     v moved and stored, and four partials per block, [u2_W, p2_W, u2_b, p2_b], of the update direction
     u = m-hat / (sqrt(v-hat) + eps) + wd * p. groups = [(partials, trust_out, [(param, grad, m, v, slabs, nw),
     ...])] as for lamb_multi."""
-    cols, nslab, ns, nws, gid, parts, _, like = _trust_args(groups, "lamb_moments_multi", 5)
+    cols, nslab, ns, nws, gid, parts, _, like = _group_args(groups, "lamb_moments_multi", 5, trust=True)
     _lib.call("slk_lamb_moments_multi",
               *_host_arrays([cols[1], cols[0], cols[2], cols[3], cols[-1], nslab, ns, nws, gid], n_int=4), len(gid),
               *_host_arrays([parts], n_int=0), len(groups), _dev(step, "step", (1,), torch.int32), float(beta1),
@@ -868,7 +868,7 @@ def lamb_moments_multi(groups, step, beta1, beta2, eps, weight_decay=0.0, exclud
 def lamb_multi(groups, lr_table, step, beta1, beta2, eps, weight_decay=0.0, exclude_bias=True):
     """Pass 2 of a LAMB step (slk_lamb_multi), ONE launch after lamb_moments_multi(groups): per tensor
     ratio = |w| / |u| (1 where a norm is 0) and p -= lr * ratio * u, u recomputed from the stored moments."""
-    cols, nslab, ns, nws, gid, parts, outs, like = _trust_args(groups, "lamb_multi", 5)
+    cols, nslab, ns, nws, gid, parts, outs, like = _group_args(groups, "lamb_multi", 5, trust=True)
     _lib.call("slk_lamb_multi", *_host_arrays([cols[0], cols[2], cols[3], nslab, ns, nws, gid], n_int=4), len(gid),
               *_host_arrays([parts, outs], n_int=0), len(groups), *_lr_args(lr_table, step), float(beta1),
               float(beta2), float(eps), float(weight_decay), int(bool(exclude_bias)), _stream(like))

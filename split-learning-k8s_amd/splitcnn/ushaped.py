@@ -23,8 +23,9 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import CONV_DEFAULT, CONV_PRESETS, LR, TIMER, LossLog, _Buffers, _flatten_params
+from .engine import CONV_DEFAULT, CONV_PRESETS, LR, TIMER, LossLog, _Buffers
 from .model_def import ModelPartA, ModelPartB
+from .recipe import _flatten_params
 
 
 class UServerStage:

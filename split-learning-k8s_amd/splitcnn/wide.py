@@ -23,7 +23,6 @@ there is no CPU path. Activations live in HBM in the C8 layout [B][C/8][H][W][8]
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Optional
 
@@ -38,7 +37,8 @@ from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
-from .optim import EMA, LAMB, Adam, ClipNorm, LRSchedule, check_clip, check_ema, is_layerwise
+from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema
+from .recipe import Seg, StageRecipe, _flatten_params
 
 P_DROP = 0.25
 KEEP_THRESHOLD = int(round(P_DROP * 4294967296.0))          # keep iff hash >= p * 2^32
@@ -100,7 +100,7 @@ class WideModelPartB(nn.Module):
         thresh, scale = (KEEP_THRESHOLD, KEEP_SCALE) if self.training else (0, 1.0)
         logits = _WideHeadFn.apply(x, self.fc.weight, self.fc.bias, snap, self.dropout_seed, thresh, scale)
         if self.training:
-            _lib.call("slk_tick", self._drop_step.data_ptr(), _stream(x))
+            ops.tick(self._drop_step)
         return logits
 
 
@@ -164,20 +164,6 @@ def nchw_to_c8(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(B, C // 8, 8, H, W).permute(0, 1, 3, 4, 2).contiguous()
 
 
-def _flat(params, device):
-    n = sum(p.numel() for p in params)
-    flat = torch.empty(n, dtype=_F32, device=device)
-    grad = torch.zeros(n, dtype=_F32, device=device)
-    off = 0
-    for p in params:
-        k = p.numel()
-        flat[off:off + k].copy_(p.detach().reshape(-1).to(device=device, dtype=_F32))
-        p.data = flat[off:off + k].view(p.shape)
-        p.grad = grad[off:off + k].view(p.shape)
-        off += k
-    return flat, grad
-
-
 def _q(name, *args):
     return _lib.query(name, *args)
 
@@ -186,7 +172,6 @@ def _k(name, *args):
     """Launch slk_<name> under the (optional) HIP-event kernel timer."""
     with TIMER(name):
         _lib.call("slk_" + name, *args)
-
 
 
 def _require_cuda(x, who):
@@ -265,9 +250,7 @@ def client_backward_scratch(B, get):
 
 
 def _reduce(slabs):
-    out = torch.empty(slabs.shape[1], dtype=_F32, device=slabs.device)
-    _lib.call("slk_reduce_slabs", slabs.data_ptr(), slabs.shape[0], slabs.shape[1], out.data_ptr(), 0, _stream(slabs))
-    return out
+    return ops.reduce_slabs(slabs)
 
 
 class _WideClientFn(torch.autograd.Function):
@@ -342,92 +325,34 @@ class _WideHeadFn(torch.autograd.Function):
         return (c8_to_nchw(dcut).to(ctx.in_dtype), g[:163840].view(10, 16384), g[163840:], None, None, None, None)
 
 # ------------------------------------------------------------------------------------ stages
-class _AdamRecipe:
-    """Optimizer recipe of a K5 stage. Without a config (optim=None, schedule=None) the stage runs
-    torch.optim.Adam(lr, betas, eps) on slk_adam_*, `lr` a by-value kernel argument (frozen into a captured
-    graph). With an optim.Adam config and / or an optim.LRSchedule it runs slk_adamw_*: weight decay
-    (AdamW or Adam's) and the rate read from the schedule's device table at the stage's step_ctr. With an
-    optim.ClipNorm (`clip`, which like a schedule selects slk_adamw_*) every step is two launches,
-    slk_reduce_sqnorm_multi then slk_adamw_clip_multi: the stage's gradient is clipped by its own global L2
-    norm before weight decay; `grads` keeps the unclipped gradient, `clip_out` the last step's [norm, coef].
-    With an optim.LAMB every step is slk_lamb_moments_multi then slk_lamb_multi over the stage's
-    [weight | bias] pairs; `trust_out` keeps every tensor's [w_norm, u_norm, ratio] of the last step.
-    With an optim.EMA (`ema_cfg`; the default Adam path has its counter and keeps its launches) the stage owns
-    `ema`, a flat block like params that starts as their copy, and slk_ema_multi runs on every stepping path after
-    the optimizer launch(es) and in front of the counter's tick (_tick)."""
+class _AdamRecipe(StageRecipe):
+    """The Adam family of a K5 stage (recipe.StageRecipe holds what it shares with K2). The default is
+    torch.optim.Adam(lr, betas, eps) on slk_adam_*, which already keeps m, v and a counter: ema= leaves it in place
+    and only a config, a schedule or clip= selects slk_adamw_* (weight decay, AdamW's or Adam's). The clipped step
+    is slk_adamw_clip_multi, the layer-wise recipe optim.LAMB (slk_lamb_moments_multi then slk_lamb_multi, `trust_out`
+    rows [w_norm, u_norm, ratio]). Every launch reports under its entry's name (TIMER)."""
 
-    def _init_optim(self, optim, schedule, clip=None, ema=None):
-        if optim is not None and not isinstance(optim, Adam):
-            raise TypeError(f"optim: expected splitcnn.optim.Adam or None, got {type(optim).__name__}")
-        check_clip(clip)
-        self.ema = self.ema_cfg = None
-        if check_ema(ema) is not None:
-            self.ema_cfg = ema.to(self.device)
-            self.ema = self.params.clone()
-        if optim is None and (schedule is not None or clip is not None):
-            optim = Adam(self.lr, self.betas, self.eps)
-        if is_layerwise(optim) and clip is not None:
-            raise ValueError(f"{type(optim).__name__} is not combined with clip= (the trust ratio already bounds "
-                             "every tensor's step by its own norms)")
-        self.optim, self.schedule = optim, None
-        self.clip = self.clip_out = self.trust_out = None
-        if optim is None:
-            return
-        self.lr, self.betas, self.eps = optim.lr, optim.betas, optim.eps
-        self.schedule = (schedule if schedule is not None else LRSchedule.constant(optim.lr, self.device)).to(self.device)
-        if clip is not None:
-            self.clip = clip.to(self.device)
-            self.clip_out = torch.zeros(2, dtype=_F32, device=self.device)   # [norm, coef] of the last step
-        if isinstance(optim, LAMB):   # [w_norm, u_norm, ratio] of every tensor's last step, in TENSORS' order
-            self.trust_out = torch.zeros(2 * len(self.PAIRS), 3, dtype=_F32, device=self.device)
-
-    def _tick(self, stream):
-        """The averaged block's update (ema=), then ++step_ctr: the end of every stepping path."""
-        if self.ema is not None:
-            with TIMER("ema_multi"):
-                ops.ema_multi([(self.ema, self.params)], self.ema_cfg.value, self.step_ctr, self.ema_cfg.start,
-                              self.ema_cfg.warmup)
-        _k("tick", self.step_ctr.data_ptr(), stream)
-
-    def _lamb(self, segments, write_grads, kw):
-        """The two LAMB launches over this stage's [weight | bias] pairs (PAIRS: (lo, n, weight elements)); a
-        (lo, n, slabs) slice over the whole stage (the gradient block in place) becomes one slice per pair."""
-        pairs = {(lo, n): nw for lo, n, nw in self.PAIRS}
-        flat = []
-        for lo, n, sl in segments:
-            if (lo, n) in pairs:
-                flat.append((lo, n, sl, pairs[(lo, n)]))
-            elif (lo, n) == (0, self.params.numel()):
-                flat += [(a, k, sl[:, a:a + k], nw) for a, k, nw in self.PAIRS]
-            else:
-                raise ValueError("LAMB: a segment must be one [weight | bias] pair")
-        segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
-                 self.v[lo:lo + n], sl, nw) for lo, n, sl, nw in flat]
-        need = ops.trust_partials_needed(segs)
-        self.trust_nblk = [ops.reduce_sqnorm_nblk(g[4].shape[1], g[4].shape[0]) for g in segs]   # partials per pair
-        groups = [(self._buf.get("trust_partials", (need,), _F32, self.device), self.trust_out, segs)]
-        lr_table, step = kw.pop("lr_table"), kw["step"]
-        with TIMER("lamb_moments_multi"):
-            ops.lamb_moments_multi(groups, **kw)
-        with TIMER("lamb_multi"):
-            ops.lamb_multi(groups, lr_table, **kw)
+    CONFIG, HYPER, STATE = Adam, ("lr", "betas", "eps"), ("m", "v")
+    BY_VALUE_COUNTER = TICK_TIMER = True
 
     def _adamw(self, segments, write_grads=True, fuse=True):
-        """slk_adamw_* on (lo, n, slabs) slices of this stage (slabs [nslab, n]): ONE launch (fuse) or one
-        per slice; with `clip` always the two clip launches over all slices (one group)."""
-        segs = [(self.params[lo:lo + n], self.grads[lo:lo + n] if write_grads else None, self.m[lo:lo + n],
-                 self.v[lo:lo + n], sl) for lo, n, sl in segments]
-        kw = dict(lr_table=self.schedule.table, step=self.step_ctr, **self.optim.kernel_args())
-        if is_layerwise(self.optim):
-            return self._lamb(segments, write_grads, kw)
-        if self.clip is not None:
-            need = self.clip_npart = ops.clip_partials_needed(segs)   # partials of this stage's last clipped step
-            groups = [(self._buf.get("clip_partials", (need,), _F32, self.device), self.clip_out, segs)]
-            with TIMER("reduce_sqnorm_multi"):
-                ops.reduce_sqnorm_multi(groups)
-            with TIMER("adamw_clip_multi"):
-                ops.adamw_clip_multi(groups, self.clip.value, **kw)
-        elif fuse and len(segs) > 1:
+        """One optimizer step on (lo, hi, slabs) slices of this stage (slabs [nslab, hi - lo]) or recipe.Seg
+        segments: ONE launch (fuse) or one per slice; write_grads False: every slabs is the gradient block."""
+        segs = [g if type(g) is Seg else self.seg(*g, write_grads=write_grads) for g in segments]
+        self._step(segs, multi=fuse and len(segs) > 1)
+
+    def _by_value(self, segs, loss, multi):
+        hyper = (self.lr, *self.betas, self.eps, self.step_ctr)
+        if multi:
+            with TIMER("adam_multi_from_slabs"):
+                ops.adam_multi_from_slabs(segs, *hyper)
+        else:
+            for g in segs:
+                with TIMER("adam_from_slabs"):
+                    ops.adam_from_slabs(*g, *hyper)
+
+    def _plain(self, segs, loss, multi, kw):
+        if multi:
             with TIMER("adamw_multi_from_slabs"):
                 ops.adamw_multi_from_slabs(segs, **kw)
         else:
@@ -435,13 +360,26 @@ class _AdamRecipe:
                 with TIMER("adamw_from_slabs"):
                     ops.adamw_from_slabs(*g, **kw)
 
+    def _clipped(self, groups, loss, kw):
+        with TIMER("reduce_sqnorm_multi"):
+            ops.reduce_sqnorm_multi(groups, loss=loss)
+        with TIMER("adamw_clip_multi"):
+            ops.adamw_clip_multi(groups, self.clip.value, **kw)
+
+    def _layerwise(self, groups, loss, kw):
+        lr_table = kw.pop("lr_table")
+        with TIMER("lamb_moments_multi"):
+            ops.lamb_moments_multi(groups, loss=loss, **kw)
+        with TIMER("lamb_multi"):
+            ops.lamb_multi(groups, lr_table, **kw)
+
 
 class WideClientStage(_AdamRecipe):
     """Client half: forward(x) -> cut (bf16 C8); backward_step(dcut) = activations.backward(grads) +
     Adam (client_part.py:114,132-133 for the widened model)."""
 
     OFF = {"W1": 0, "b1": 1728, "W2": 1792, "b2": 75520, "W3": 75648, "b3": 370560}
-    PAIRS = ((0, 1792, 1728), (1792, 73856, 73728), (75648, 295168, 294912))
+    PAIRS = ((0, 1792, 1728), (1792, 75648, 73728), (75648, CLIENT_NPARAM, 294912))
     TENSORS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "conv3.weight", "conv3.bias")
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
@@ -450,12 +388,9 @@ class WideClientStage(_AdamRecipe):
         self.device = torch.device(device)
         self.model = (model if model is not None else WideModelPartA()).to(self.device)
         m = self.model
-        self.params, self.grads = _flat([m.conv1.weight, m.conv1.bias, m.conv2.weight, m.conv2.bias,
-                                         m.conv3.weight, m.conv3.bias], self.device)
+        self.params, self.grads = _flatten_params([m.conv1.weight, m.conv1.bias, m.conv2.weight, m.conv2.bias,
+                                                   m.conv3.weight, m.conv3.bias], self.device)
         assert self.params.numel() == CLIENT_NPARAM
-        self.m = torch.zeros_like(self.params)
-        self.v = torch.zeros_like(self.params)
-        self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps = lr, betas, eps
         self._init_optim(optim, schedule, clip, ema)
         self.fuse_adam = True  # step_from_slabs: the three Adam segments in one launch
@@ -513,34 +448,16 @@ class WideClientStage(_AdamRecipe):
         self._dp2, self._da1m = scratch
         return s1, s2, s3
 
-    def _adam(self, lo, n, slabs):
-        s = _stream(slabs)
-        _k("adam_from_slabs", self.params[lo:].data_ptr(), self.grads[lo:].data_ptr(),
-                  self.m[lo:].data_ptr(), self.v[lo:].data_ptr(), slabs.data_ptr(), slabs.shape[0], n,
-                  float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                  self.step_ctr.data_ptr(), s)
+    def _slab_segments(self, s1, s2, s3):
+        """The three slab sets, [conv1 | conv2 | conv3], as (lo, hi, slabs) slices: the stage's PAIRS."""
+        return [(lo, hi, sl) for (lo, hi, _), sl in zip(self.PAIRS, (s1, s2, s3))]
 
     def step_from_slabs(self, s1, s2, s3):
         """Adam on all client parameters from the three slab sets (ONE launch, bit-identical to one
-        slk_adam_from_slabs per set), then shadows + step counter."""
-        if self.optim is not None:
-            self._adamw(((0, 1792, s1), (1792, 73856, s2), (75648, 295168, s3)), fuse=self.fuse_adam)
-        elif self.fuse_adam:
-            P, I = ctypes.c_void_p, ctypes.c_int
-            segs = ((0, 1792, s1), (1792, 73856, s2), (75648, 295168, s3))
-            arr = lambda ts: ctypes.cast((P * 3)(*ts), P)  # noqa: E731
-            _k("adam_multi_from_slabs", arr([self.params[lo:].data_ptr() for lo, _, _ in segs]),
-               arr([self.grads[lo:].data_ptr() for lo, _, _ in segs]),
-               arr([self.m[lo:].data_ptr() for lo, _, _ in segs]), arr([self.v[lo:].data_ptr() for lo, _, _ in segs]),
-               arr([sl.data_ptr() for _, _, sl in segs]), ctypes.cast((I * 3)(*[sl.shape[0] for _, _, sl in segs]), P),
-               ctypes.cast((I * 3)(*[n for _, n, _ in segs]), P), 3, float(self.lr), float(self.betas[0]),
-               float(self.betas[1]), float(self.eps), self.step_ctr.data_ptr(), _stream(self.params))
-        else:
-            self._adam(0, 1792, s1)
-            self._adam(1792, 73856, s2)
-            self._adam(75648, 295168, s3)
+        slk_adam_from_slabs per set; fuse_adam False: one per set), then shadows + step counter."""
+        self._adamw(self._slab_segments(s1, s2, s3), fuse=self.fuse_adam)
         self.refresh_shadows()
-        self._tick(_stream(self.params))
+        self._tick()
 
     def backward_step(self, dcut: torch.Tensor):
         self.step_from_slabs(*self.backward_slabs(dcut))
@@ -555,24 +472,15 @@ class WideClientStage(_AdamRecipe):
     def backward_grads(self, dcut: torch.Tensor, tag="", accumulate: bool = False):
         """activations.backward(grads) into the flat gradient block (fixed-order slab reduction);
         accumulate=True adds (micro-batches of one step)."""
-        s1, s2, s3 = self.backward_slabs(dcut, tag)
-        st = _stream(dcut)
-        for lo, n, sl in ((0, 1792, s1), (1792, 73856, s2), (75648, 295168, s3)):
+        for lo, hi, sl in self._slab_segments(*self.backward_slabs(dcut, tag)):
             with TIMER("reduce_slabs"):
-                _lib.call("slk_reduce_slabs", sl.data_ptr(), sl.shape[0], n, self.grads[lo:].data_ptr(),
-                          int(bool(accumulate)), st)
+                ops.reduce_slabs(sl, out=self.grads[lo:hi], accumulate=accumulate)
 
     def step_from_grads(self):
         """Adam from self.grads (e.g. after an all-reduce over the client ranks)."""
-        g = self.grads
-        if self.optim is not None:
-            self._adamw([(0, CLIENT_NPARAM, g.view(1, -1))], write_grads=False)
-        else:
-            _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
-               CLIENT_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-               self.step_ctr.data_ptr(), _stream(g))
+        self._adamw([self.grads_segment()])
         self.refresh_shadows()
-        self._tick(_stream(g))
+        self._tick()
 
 
 class WideServerStage(_AdamRecipe):
@@ -591,11 +499,8 @@ class WideServerStage(_AdamRecipe):
         # eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
         self.loss = check_loss(loss)
         self.model = (model if model is not None else WideModelPartB()).to(self.device)
-        self.params, self.grads = _flat([self.model.fc.weight, self.model.fc.bias], self.device)
+        self.params, self.grads = _flatten_params([self.model.fc.weight, self.model.fc.bias], self.device)
         assert self.params.numel() == SERVER_NPARAM
-        self.m = torch.zeros_like(self.params)
-        self.v = torch.zeros_like(self.params)
-        self.step_ctr = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
         self._init_optim(optim, schedule, clip, ema)
         self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
@@ -671,22 +576,18 @@ class WideServerStage(_AdamRecipe):
         return dcut, loss_i, sf
 
     def step_from_slabs(self, sf):
-        s = _stream(sf)
-        if self.optim is not None:
-            self._adamw([(0, SERVER_NPARAM, sf)])
-        else:
-            _k("adam_from_slabs", self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-               self.v.data_ptr(), sf.data_ptr(), sf.shape[0], SERVER_NPARAM, float(self.lr),
-               float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_ctr.data_ptr(), s)
+        self._adamw([(0, SERVER_NPARAM, sf)])
         self.refresh_shadows()
-        self._tick(s)
+        self._tick()
 
-    def log_loss(self, loss_i, step=None):
-        _k("loss_log", loss_i.data_ptr(), loss_i.numel(), 1.0 / loss_i.numel(),
-                  self.loss_log.ring.data_ptr(), self.loss_log.ring.numel(), self.loss_log.counter.data_ptr(),
-                  _stream(loss_i))
+    def _log(self, values, scale, step):
+        with TIMER("loss_log"):
+            ops.loss_log(values, scale, self.loss_log.ring, self.loss_log.counter)
         if step is not None:
             self.loss_log.note_step(step)
+
+    def log_loss(self, loss_i, step=None):
+        self._log(loss_i, 1.0 / loss_i.numel(), step)
 
     def step_request(self, cut, labels, step=None, dcut=None):
         """One /forward_pass for the widened model: returns (dcut, loss_i)."""
@@ -709,31 +610,17 @@ class WideServerStage(_AdamRecipe):
         scale grad_scale = 1/global batch); the fc gradient adds into self.grads (k = 0 starts it) and
         this part's loss sum lands in loss part k of nparts. Returns dcut."""
         dcut, loss_i, sf = self.forward_backward(cut, labels, grad_scale, dcut=dcut, b0=b0)
-        s = _stream(sf)
         with TIMER("reduce_slabs"):
-            _lib.call("slk_reduce_slabs", sf.data_ptr(), sf.shape[0], SERVER_NPARAM, self.grads.data_ptr(),
-                      int(k > 0), s)
-        parts = self._b("loss_parts", (nparts,), _F32)
-        _lib.call("slk_loss_sum", loss_i.data_ptr(), loss_i.numel(), float(grad_scale), parts[k:].data_ptr(), s)
+            ops.reduce_slabs(sf, out=self.grads, accumulate=k > 0)
+        ops.loss_sum(loss_i, grad_scale, out=self._b("loss_parts", (nparts,), _F32)[k:k + 1])
         return dcut
 
     def finish_step(self, nparts: int, step=None):
         """Adam from the accumulated gradient, loss logged (sum of the parts), step counter ticked."""
-        g = self.grads
-        s = _stream(g)
-        if self.optim is not None:
-            self._adamw([(0, SERVER_NPARAM, g.view(1, -1))], write_grads=False)
-        else:
-            _k("adam_from_slabs", self.params.data_ptr(), None, self.m.data_ptr(), self.v.data_ptr(), g.data_ptr(), 1,
-               SERVER_NPARAM, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-               self.step_ctr.data_ptr(), s)
+        self._adamw([self.grads_segment()])
         self.refresh_shadows()
-        parts = self._b("loss_parts", (nparts,), _F32)
-        _k("loss_log", parts.data_ptr(), nparts, 1.0, self.loss_log.ring.data_ptr(), self.loss_log.ring.numel(),
-           self.loss_log.counter.data_ptr(), s)
-        if step is not None:
-            self.loss_log.note_step(step)
-        self._tick(s)
+        self._log(self._b("loss_parts", (nparts,), _F32), 1.0, step)
+        self._tick()
 
 
 class WideTrainer(GraphedTrainer):

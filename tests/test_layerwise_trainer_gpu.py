@@ -76,8 +76,8 @@ def same(a, b):
 
 
 def pairs(st):
-    """(lo, hi, nw) of a stage's [weight | bias] pairs (the K5 stages list (lo, n, nw))."""
-    return [(lo, b if hasattr(st, "buf") else lo + b, nw) for lo, b, nw in st.PAIRS]
+    """(lo, hi, nw) of a stage's [weight | bias] pairs."""
+    return list(st.PAIRS)
 
 
 WHICH = ["k2", "k5"]
