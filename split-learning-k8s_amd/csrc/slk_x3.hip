@@ -53,6 +53,24 @@ __device__ __forceinline__ void x3_split8(const float* v, float sc, f16x8& h, f1
         l[k + 1] = (_Float16)(b - (float)hb);
     }
 }
+// The same split for the producers of act16 images whose input may hold -0.0 (the forward's f32 rows, a received
+// cut), written on explicit pairs. From the scalar form hipcc converts some elements as v_fma_mixlo_f16(v, sc, +0),
+// which makes h = +0 and then l = -0 of a -0.0: the same values as the split's (h = -0, l = +0) in every product,
+// other bits in the image (tests/test_x3_lo_exact_gpu.py decodes them). Everywhere else the halves stay in
+// registers or LDS, or the input is a ReLU output (>= +0), and the scalar form's code is kept.
+__device__ __forceinline__ void x3_split8_img(const float* v, float sc, f16x8& h, f16x8& l) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        const f32x2 a = f32x2{v[k], v[k + 1]} * sc;
+        const f16x2 ha = __builtin_convertvector(a, f16x2);
+        const f16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, f32x2), f16x2);
+        h[k] = ha[0];
+        h[k + 1] = ha[1];
+        l[k] = la[0];
+        l[k + 1] = la[1];
+    }
+}
 
 __device__ __forceinline__ f32x4 mfma_f16(const f16x8& a, const f16x8& b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -538,7 +556,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(raw + rd[it] + j * X3F_PIX * 4);
             f16x8 h, l;
-            x3_split8(v, sc, h, l);
+            x3_split8_img(v, sc, h, l);
             *reinterpret_cast<f16x8*>(buf + wo[it]) = h;
             *reinterpret_cast<f16x8*>(buf + X3F_PLANE + wo[it]) = l;
         }
@@ -2457,7 +2475,7 @@ __global__ __launch_bounds__(C1X_T) void cut_unpack_x3_kernel(const float* __res
             if ((m >> bit) & 1u) v[j] = vals[(size_t)sr[w] + __popc(m & ((1u << bit) - 1u))];
         }
         f16x8 hh, ll;
-        x3_split8(v, sc, hh, ll);
+        x3_split8_img(v, sc, hh, ll);
         char* o = img + p * 64 + (c8 ^ (xx & 2)) * 16;
         *reinterpret_cast<f16x8*>(o) = hh;
         *reinterpret_cast<f16x8*>(o + X3S_PLANE) = ll;

@@ -9,7 +9,10 @@ src/client_part.py:117-125); its contract is plain bit arithmetic, so the checke
   unpack      = x where the bit is set, +0.0 elsewhere;  pack(g) = g[mask]
 All bit-exact. Sizes cover ragged tails (n not a multiple of 32 / 64 / 2048), one element, more
 blocks than the scan's 1024 threads, -0.0 (nonzero bit pattern, kept), NaN/inf/denormals, all-zero
-and all-set inputs, and a full B = 1024 micro-batch of the K3 cut (22,151,168 elements)."""
+and all-set inputs, a full B = 1024 micro-batch of the K3 cut (22,151,168 elements), and 12,289 blocks
+(2048 * 12,289 + 5 elements): the scan's second path, for more block counts than it stages in LDS (12,288), which
+a Pipeline micro-batch of 1,164 or more samples reaches. Every case also checks the word ranks
+(ranks[w] = set elements before word w)."""
 import numpy as np
 import pytest
 import torch
@@ -51,7 +54,8 @@ def _input(n, kind, seed):
 
 
 CASES = [(1, "dense"), (31, "relu"), (33, "relu"), (64, "special"), (2047, "relu"), (2048, "zeros"), (2049, "special"),
-         (65_541, "relu"), (2048 * 1100 + 7, "special"), (3_000_017, "dense"), (1024 * 32 * 26 * 26, "relu")]
+         (65_541, "relu"), (2048 * 1100 + 7, "special"), (3_000_017, "dense"), (1024 * 32 * 26 * 26, "relu"),
+         (2048 * 12_289 + 5, "special")]
 
 
 @pytest.mark.parametrize("n,kind", CASES)
@@ -70,6 +74,8 @@ def test_codec_roundtrip_vs_numpy(gpu, n, kind):
     assert np.array_equal(cnt.cpu().numpy(), counts) and np.array_equal(off.cpu().numpy(), offsets)
     assert int(tot.item()) == total
     assert np.array_equal(vals[:total].cpu().numpy().view(np.uint32), x.view(np.uint32)[set_])
+    before = np.cumsum(set_, dtype=np.int64) - set_                 # rank of every element = set elements before it
+    assert np.array_equal(codec.ranks("tx", n, bufs).cpu().numpy().astype(np.int64), before[::32])
 
     # receiving side: offsets from the mask alone, then unpack
     rx = codec.buffers("rx", n, gpu)
