@@ -232,15 +232,18 @@ int slk_conv2_wgrad_x3_nslab(int B);
 /* The forward that also writes its split f16 input images (act16, slk_conv2_act16_bytes(B) bytes; each
  * sample at its own scale from act_amax) and the wgrad that moves them by LDS-DMA instead of loading and
  * splitting act: the wgrad's input staging becomes a copy. Same results as slk_conv2_wgrad_x3 (bitwise:
- * the same scales, the same f16 values). */
+ * the same scales, the same f16 values).
+ * slk_conv2_wgrad_x3s refuses (invalid value) a batch whose K share would span more samples than its LDS scale
+ * table holds: B >= 2,883,243, whose act16 images and pooled gradient alone exceed the device's memory. */
 int slk_conv2_fwd_pool_x3s(const float* act, const float* act_amax, const float* W2, const float* b2, float* pooled,
                            uint8_t* code, uint16_t* act16, int B, void* stream);
 int slk_conv2_wgrad_x3s(const uint16_t* act16, const float* act_amax, const float* dpooled, const float* dp_amax,
                         const uint8_t* code, float* slabs, int B, void* stream);
-/* Which kernel slk_conv2_wgrad_x3s runs (round 6): 2 = on the 2:4-sparse f16 MFMA (v_smfmac_f32_16x16x64_f16:
+/* Which kernel slk_conv2_wgrad_x3s runs: always 2 = on the 2:4-sparse f16 MFMA (v_smfmac_f32_16x16x64_f16:
  * the max-pool routing leaves at most 2 nonzeros of dY in every 4 consecutive output pixels of a row starting at
- * a multiple of 4, so half the dense x3 products are never issued), 1 = the dense x3 kernel, 0 = the round-4
- * kernel. Measurement only (bench.py prices the executed products against the matching peak). */
+ * a multiple of 4, so half the dense x3 products are never issued). 1 (the dense x3 kernel) and 0 (the round-4
+ * kernel) named forms that are no longer built. Measurement only (bench.py prices the executed products against
+ * the matching peak). */
 int slk_conv2_wgrad_x3_form(void);
 /* slk_conv2_fwd_pool_x3s with the per-sample max |act| computed inside the forward (written to act_amax,
  * the values slk_row_amax gives) instead of read: the drop-in module path has no separate pass over the cut.
@@ -612,7 +615,8 @@ int slk_wide_conv3_dgrad(const uint16_t* dcut, const uint8_t* code3, const uint1
 int slk_wide_conv2_wgrad(const uint16_t* dp2, const uint8_t* code2, const uint16_t* a1, float* slabs, int B,
                          void* stream);
 int slk_wide_conv2_wgrad_nslab(int B);
-/* 1 when the K5 weight gradients run on the 2:4-sparse bf16 MFMA (the max-pool-routed dC), 0 dense. */
+/* Always 1: the K5 weight gradients run on the 2:4-sparse bf16 MFMA (the max-pool-routed dC); 0 named the dense
+ * form, which is no longer built. */
 int slk_wide_wgrad_form(void);
 int slk_wide_conv2_dgrad(const uint16_t* dp2, const uint8_t* code2, const uint16_t* w2d, const uint64_t* a1bits,
                          uint16_t* da1m, int B, void* stream);

@@ -28,11 +28,6 @@ constexpr int W3_N = NCLS * P_SAMPLE;// 92160
 constexpr int CODE_NONE = 4;         // pooled value <= 0: ReLU blocks the gradient
 }  // namespace slk
 
-// Pin gather-then-MFMA phases in the conv2 main loops with sched_barrier (A/B switch).
-#ifndef SLK_PIN_PHASES
-#define SLK_PIN_PHASES 0
-#endif
-
 template <typename T>
 __device__ __forceinline__ void slk_keep(T& v) { asm volatile("" : "+v"(v)); }
 

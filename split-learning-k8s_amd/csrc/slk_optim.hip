@@ -16,10 +16,7 @@ constexpr int RS_WAVES = 16;
 // 4 waves per 64 columns each summing every 4th slab, the 4 partials added in order (round 6: one thread
 // per column walked 64 slabs in 8 dependent rounds on 91 blocks; 64-column blocks over 92,170 columns
 // were ~1,400 dispatch-bound blocks); many slabs -> 64 columns per block, 16 waves over the slab range.
-#ifndef SLK_RS_MID
-#define SLK_RS_MID 1  // 0: the round-5 forms (<= 64 slabs thread per column), kept for the A/B
-#endif
-constexpr int RS_COLS_MAX = SLK_RS_MID ? 16 : 64, RS_MID_MAX = 64;
+constexpr int RS_COLS_MAX = 16, RS_MID_MAX = 64;
 __host__ __device__ constexpr int rs_cols_per_block(int nslab) {
     return nslab <= RS_COLS_MAX ? 1024 : (nslab <= RS_MID_MAX ? 256 : 64);
 }

@@ -190,16 +190,10 @@ __device__ __forceinline__ void c2d_chunk(const float* __restrict__ dcp, const f
 #pragma unroll
             for (int i = 0; i < NT; ++i) bv[tap][i] = dcp[pbase[i] + imm];
         }
-#if SLK_PIN_PHASES
-        __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
             for (int i = 0; i < NT; ++i) acc[i] = mfma32x32x2(av[tap], bv[tap][i], acc[i]);
-#if SLK_PIN_PHASES
-        __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 }
 
@@ -447,9 +441,6 @@ __global__ __launch_bounds__(C2W_THREADS, 3) void conv2_wgrad_kernel(
 #pragma unroll
                     for (int tt = 0; tt < 3; ++tt) bv[i][t][tt] = ir[base[tt] + t * A_HW + 2 * px];
             }
-#if SLK_PIN_PHASES
-            __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const float a0 = (cd[i] == q0) ? dv[i] : 0.f;
@@ -460,9 +451,6 @@ __global__ __launch_bounds__(C2W_THREADS, 3) void conv2_wgrad_kernel(
                     acc[tt] = mfma32x32x2(a1, bv[i][1][tt], acc[tt]);
                 }
             }
-#if SLK_PIN_PHASES
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         if (nu < nunit) write_dc(nxt);
         __syncthreads();

@@ -33,32 +33,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// Build-time knobs (tools/ablate_wide.py builds variants): weight lookahead of the conv stream, and
-// XCD grouping of tiles (all row blocks / channel blocks of one image on one XCD at the same time,
-// so halo rows and shared input tiles are L2 hits).
-#ifndef SLK_WIDE_XCD
-#define SLK_WIDE_XCD 1
-#endif
-// Wave priority: raise it around each step's MFMA block (1: conv kernels, 2: also wgrad), so a wave
-// with MFMAs ready issues ahead of a co-resident wave's epilogue VALU / staging work.
-#ifndef SLK_WIDE_DMA_LATE
-#define SLK_WIDE_DMA_LATE 0
-#endif
-#ifndef SLK_WIDE_PRIO
-#define SLK_WIDE_PRIO 0
-#endif
-// Stagger: the second half of the grid (the second workgroup of each CU under round-robin dispatch)
-// sleeps SLK_WIDE_STAGGER x 127 x 64 cycles before its first tile, so the two co-resident workgroups
-// run half a tile apart and one's epilogue (VALU + stores) overlaps the other's MFMA main loop.
-#ifndef SLK_WIDE_STAGGER
-#define SLK_WIDE_STAGGER 0
-#endif
-__device__ __forceinline__ void wide_stagger() {
-#if SLK_WIDE_STAGGER
-    if (blockIdx.x >= gridDim.x / 2)
-        for (int i = 0; i < SLK_WIDE_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
-}
+// Build-time knobs that are only a number (tools/ablate_wide.py builds variants): SLK_WIDE_FW, SLK_WIDE_NWV,
+// SLK_WIDE_C3D_NWV (the dispatch below). Tiles are grouped by XCD: all row blocks / channel blocks of one image
+// on one XCD at the same time, so halo rows and shared input tiles are L2 hits.
 
 namespace wide {
 constexpr int IMG = 32;                 // input 3 x 32 x 32
@@ -85,12 +62,8 @@ __device__ __forceinline__ float dpp_xor1(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
 }
 
-// Epilogue forms (SLK_WIDE_EPI2 = 0: the first forms, for A/B): relu + 2x2 max-pool by v_max3 and
-// first-equal argmax, bias folded into the accumulator's initial value; the a1 > 0 mask of conv2's
-// dgrad on packed bf16 pairs.
-#ifndef SLK_WIDE_EPI2
-#define SLK_WIDE_EPI2 1
-#endif
+// Epilogue forms: relu + 2x2 max-pool by v_max3 and first-equal argmax, bias folded into the accumulator's
+// initial value; the a1 > 0 mask of conv2's dgrad on packed bf16 pairs.
 __device__ __forceinline__ float max3f(float a, float b, float c) {
     float r;   // asm: hipcc would canonicalize each operand of a plain fmaxf first
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -133,10 +106,7 @@ __device__ __forceinline__ void wait_vmcnt_sat() { wait_vmcnt<(N > 63 ? 63 : N)>
 // Epilogue-aware waits: the first steps of a tile wait for weight slices that were issued BEFORE the
 // previous tile's epilogue, so that epilogue's stores (and this tile's prefetched epilogue loads) are
 // younger and may stay in flight. Without the allowance those steps drain every store before the
-// next MFMA. 0 = plain counts (profiling only).
-#ifndef SLK_WIDE_EPI
-#define SLK_WIDE_EPI 1
-#endif
+// next MFMA.
 
 // ----------------------------------------------------------------------------- conv geometry
 template <int CI_, int CO_, int HW_, int MT_, int MODE_, int FW_, int NWV_, int EXP_ = 0>
@@ -201,25 +171,11 @@ __device__ __forceinline__ TileState tile_state(int t, int B) {
     // n to XCD (n % 8) in one round: neighbouring row blocks share halo rows and the channel blocks
     // share the input tile through that XCD's L2. (Speed only; any placement is correct.)
     TileState s;
-#if SLK_WIDE_XCD
     const int xcd = t & 7, j = t >> 3;
     s.rb = j % C::RB;
     s.cob = (j / C::RB) % C::NCB;
     s.n = (j / (C::RB * C::NCB)) * 8 + xcd;
     s.valid = s.n < B;
-#else
-    int pt;
-    if (C::NCB == 2) {
-        s.cob = (t >> 3) & 1;
-        pt = ((t >> 4) << 3) | (t & 7);
-    } else {
-        s.cob = 0;
-        pt = t;
-    }
-    s.valid = pt < B * C::RB;
-    s.n = pt / C::RB;
-    s.rb = pt - s.n * C::RB;
-#endif
     return s;
 }
 
@@ -425,7 +381,6 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
     int t = blockIdx.x;
     TileState cur = tile_state<C>(t, B);
     if (!cur.valid) return;
-    wide_stagger();
     int tn = t + grid;
     TileState nxt = tile_state<C>(tn, B);
     int pcur[C::NDW], pnxt[C::NDW];
@@ -495,7 +450,7 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int f = 0; f < C::FW; ++f) {
-                if (C::MODE == wide::MODE_FWD_POOL && SLK_WIDE_EPI2)
+                if (C::MODE == wide::MODE_FWD_POOL)
                     acc[i][f] = f32x4{bias[i][0], bias[i][1], bias[i][2], bias[i][3]};
                 else
                     acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -508,7 +463,7 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
                 const bool last = tail && g == C::G - 1 && tap == 8;
                 // step s+1's weight slice (and at tap 8 the next group's input tile) has landed
                 if (tail) wait_vmcnt<0>();
-                else if (SLK_WIDE_EPI && tap < 2 && g == 0) {
+                else if (tap < 2 && g == 0) {
                     // weight step +1 predates the previous epilogue and this tile's epilogue loads
                     if (tap == 0) {
                         if (post) wait_vmcnt_sat<C::NW + C::EPI_ST + C::EPI_LD>();
@@ -525,9 +480,8 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
                 if (C::EXP && tap == 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                // weight step +3 into the slot of step -1; at tap 0 the next group's input tile. Both
-                // after this step's MFMAs when SLK_WIDE_DMA_LATE (same order of VMEM operations, so
-                // the counted waits are unchanged; every target slot is free since the barrier).
+                // weight step +3 into the slot of step -1; at tap 0 the next group's input tile (every
+                // target slot is free since the barrier). A lambda: hipcc's code for the step differs without it
                 auto issue_dma = [&]() {
                     {
                         const int sl = g * 9 + tap + C::L;
@@ -547,7 +501,7 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
                         else if (!tail) issue_input<C>(in, nxt, pnxt, 0, nslot, wave, lane);
                     }
                 };
-                if (!SLK_WIDE_DMA_LATE) issue_dma();
+                issue_dma();
                 // EXP: the next group's pooled input, staged by LDS-DMA at tap 0, is expanded into the
                 // free slot at tap 3 (read from tap 8 on)
                 if constexpr (C::EXP) {
@@ -570,14 +524,11 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
 #pragma unroll
                     for (int f = 0; f < C::FW; ++f) bv_n[f] = *reinterpret_cast<const bf16x8*>(ib + b_off[f] + toff);
                 }
-                if (SLK_WIDE_PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int f = 0; f < C::FW; ++f)
                         acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[f], acc[i][f], 0, 0, 0);
-                if (SLK_WIDE_PRIO) __builtin_amdgcn_s_setprio(0);
-                if (SLK_WIDE_DMA_LATE) issue_dma();
                 wslot = wn1;
             }
             islot ^= 1;
@@ -596,26 +547,11 @@ __global__ __launch_bounds__(C::THREADS, C::NWV == 4 ? 2 : 1) void wide_conv_ker
                     float pv[4];
                     uint32_t cw = 0;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (SLK_WIDE_EPI2) {   // the bias is already in the accumulators
-                            const float v0 = acc[i][f][r], v2 = acc[i][fb][r];
-                            uint32_t code;
-                            pv[r] = pool4(v0, dpp_xor1(v0), v2, dpp_xor1(v2), code);
-                            cw |= code << (8 * r);
-                            continue;
-                        }
-                        const float v0 = acc[i][f][r] + bias[i][r];
-                        const float v2 = acc[i][fb][r] + bias[i][r];
-                        const float v1 = dpp_xor1(v0), v3 = dpp_xor1(v2);
-                        // torch CPU max-pool over relu(c): strict > scan, first max wins
-                        float best = v0 > 0.f ? v0 : 0.f;
-                        int idx = 0;
-                        const float r1 = v1 > 0.f ? v1 : 0.f, r2 = v2 > 0.f ? v2 : 0.f, r3 = v3 > 0.f ? v3 : 0.f;
-                        if (r1 > best) { best = r1; idx = 1; }
-                        if (r2 > best) { best = r2; idx = 2; }
-                        if (r3 > best) { best = r3; idx = 3; }
-                        pv[r] = best;
-                        cw |= (uint32_t)(best > 0.f ? idx : slk::CODE_NONE) << (8 * r);
+                    for (int r = 0; r < 4; ++r) {   // the bias is already in the accumulators
+                        const float v0 = acc[i][f][r], v2 = acc[i][fb][r];
+                        uint32_t code;
+                        pv[r] = pool4(v0, dpp_xor1(v0), v2, dpp_xor1(v2), code);
+                        cw |= code << (8 * r);
                     }
                     if ((lane & 1) == 0) {
                         const int q = wn * 16 * C::FW + f * 16 + (lane & 15);
@@ -728,7 +664,6 @@ __global__ __launch_bounds__(256, 2) void wide_conv32_kernel(const uint16_t* __r
     int t = blockIdx.x;
     TileState cur = tile_state<C>(t, B);
     if (!cur.valid) return;
-    wide_stagger();
     int tn = t + grid;
     TileState nxt = tile_state<C>(tn, B);
     int pcur[C::NDW], pnxt[C::NDW];
@@ -772,7 +707,7 @@ __global__ __launch_bounds__(256, 2) void wide_conv32_kernel(const uint16_t* __r
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 if (tail) wait_vmcnt<0>();
-                else if (SLK_WIDE_EPI && tap < C::L && g == 0) {
+                else if (tap < C::L && g == 0) {
                     if (tap == 0) {
                         if (post) wait_vmcnt_sat<(C::L - 1) * C::NW + C::EPI_ST + C::EPI_LD>();
                         else wait_vmcnt_sat<(C::L - 1) * C::NW + C::EPI_LD>();
@@ -846,20 +781,9 @@ __global__ __launch_bounds__(256, 2) void wide_conv32_kernel(const uint16_t* __r
                                 v2 = __shfl_xor(v0, 16, 64);
                             }
                             const float v1 = dpp_xor1(v0), v3 = dpp_xor1(v2);
-                            if (SLK_WIDE_EPI2) {
-                                uint32_t code;
-                                pv[e] = pool4(v0, v1, v2, v3, code);
-                                cw |= code << (8 * e);
-                                continue;
-                            }
-                            float best = v0 > 0.f ? v0 : 0.f;
-                            int idx = 0;
-                            const float r1 = v1 > 0.f ? v1 : 0.f, r2 = v2 > 0.f ? v2 : 0.f, r3 = v3 > 0.f ? v3 : 0.f;
-                            if (r1 > best) { best = r1; idx = 1; }
-                            if (r2 > best) { best = r2; idx = 2; }
-                            if (r3 > best) { best = r3; idx = 3; }
-                            pv[e] = best;
-                            cw |= (uint32_t)(best > 0.f ? idx : slk::CODE_NONE) << (8 * e);
+                            uint32_t code;
+                            pv[e] = pool4(v0, v1, v2, v3, code);
+                            cw |= code << (8 * e);
                         }
                         const bool owner = C::HW == 32 ? (r & 1) == 0 : (r & 17) == 0;
                         if (owner) {
@@ -899,22 +823,11 @@ __global__ __launch_bounds__(256, 2) void wide_conv32_kernel(const uint16_t* __r
 #ifndef SLK_WIDE_NWV
 #define SLK_WIDE_NWV 4
 #endif
-#ifndef SLK_WIDE_K32
-#define SLK_WIDE_K32 1
-#endif
 // Per-layer kernel choice from tools/ablate_wide.py on MI355X (B = 4096): conv2 forward runs faster on
 // the 32x32x16 form (0.655 vs 0.693 ms), conv3 forward on the 16x16x32 form (0.585 vs 0.672), conv3
-// dgrad ties (0.667 / 0.672). SLK_WIDE_K32 = 0 / 2 forces all-16x16 / all-32x32 for A/B runs.
-#if SLK_WIDE_K32 == 2
-using CfgConv2Fwd = Conv32Cfg<64, 128, 32, wide::MODE_FWD_POOL>;
-using CfgConv3Fwd = Conv32Cfg<128, 256, 16, wide::MODE_FWD_POOL>;
-#elif SLK_WIDE_K32 == 1
+// dgrad ties (0.667 / 0.672).
 using CfgConv2Fwd = Conv32Cfg<64, 128, 32, wide::MODE_FWD_POOL>;
 using CfgConv3Fwd = ConvCfg<128, 256, 16, 128, wide::MODE_FWD_POOL, SLK_WIDE_FW, SLK_WIDE_NWV>;
-#else
-using CfgConv2Fwd = ConvCfg<64, 128, 32, 128, wide::MODE_FWD_POOL, SLK_WIDE_FW, SLK_WIDE_NWV>;
-using CfgConv3Fwd = ConvCfg<128, 256, 16, 128, wide::MODE_FWD_POOL, SLK_WIDE_FW, SLK_WIDE_NWV>;
-#endif
 // Backward: no unpooled gradient is ever materialised. conv3's dgrad and wgrad read the pooled cut
 // gradient dcut + code3 and route it while staging (EXP); conv3's dgrad writes dp2 (the gradient of
 // p2, 16 x 16), which conv2's dgrad and wgrad route by code2 the same way.
@@ -932,14 +845,9 @@ static int launch_conv(const uint16_t* in, const uint16_t* wsh, const void* aux,
     SLK_CHECK_ARG(B >= 0 && in && wsh && out && (aux || C::MODE == wide::MODE_DGRAD_PLAIN));
     if (C::MODE == wide::MODE_FWD_POOL) SLK_CHECK_ARG(out2 != nullptr);
     if (B == 0) return 0;
-    const long ntiles = (long)B * C::RB * C::NCB;
     long grid = C::NWV == 4 ? 512 : 256;               // 2 (4-wave) or 1 (8-wave) workgroups per CU
-#if SLK_WIDE_XCD
     const long span = 8L * ((B + 7) / 8) * C::RB * C::NCB;  // tile indices covering every image
     if (span < grid) grid = span;                           // a multiple of 8
-#else
-    if (ntiles < grid) grid = C::NCB == 2 ? ((ntiles + 15) / 16) * 16 : ntiles;
-#endif
     if constexpr (C::K32)
         hipLaunchKernelGGL(wide_conv32_kernel<C>, dim3((unsigned)grid), dim3(256), 0, slk_stream(stream), in, wsh, aux,
                            out, out2, B);
@@ -974,82 +882,61 @@ extern "C" int slk_wide_conv2_dgrad(const uint16_t* dp2, const uint8_t* code2, c
 // of dW (all 9 taps) and a K-split share of the batch's (image, row-block) tiles; each wave holds
 // 64 co x (9 taps x 16 ci) = 4 x 9 accumulators of v_mfma_f32_16x16x32_bf16 (144 VGPRs). Both operands
 // need 8 consecutive PIXELS per lane while the C8 layout stores 8 consecutive CHANNELS per 16 bytes, so
-// the fragments come from LDS by ds_read_b64_tr_b16 (the hardware transpose read): dC tile
-// [16 chunks][TR*W pixels] and the input halo tile [8 chunks][(TR+2)*(W+2) pixels], chunk planes
-// padded to a stride of 64 mod 256 bytes so every 32-lane half of a transposed read hits 64 distinct
-// banks. The whole next tile streams in by LDS-DMA while the current one is on the MFMAs (2 buffers,
-// one wait + barrier per tile). db rides along as one MFMA per step against a ones fragment. Each
-// workgroup writes its partial dW/db into its own slab (torch layout [co][ci][3][3] | db), reduced in
-// fixed order by slk_reduce_slabs / slk_adam_from_slabs.
-// SP (round 6, the default): dC is the max-pool backward of a pooled gradient, so in every block of 4
-// consecutive pixels of one row (x % 4 == 0: two pool windows' columns) at most 2 values per co are nonzero —
-// the 2:4 structure of v_smfmac_f32_16x16x64_bf16 (layout measured on the f16 form: slk_x3.hip's x3p notes,
+// the input fragments come from LDS by ds_read_b64_tr_b16 (the hardware transpose read) of the input
+// halo tile [8 chunks][(TR+2)*(W+2) pixels], chunk planes padded to a stride of 64 mod 256 bytes so every
+// 32-lane half of a transposed read hits 64 distinct banks. The whole next tile streams in by LDS-DMA
+// while the current one is on the MFMAs (2 buffers, one wait + barrier per tile). db rides along as one
+// MFMA per step against a ones fragment. Each workgroup writes its partial dW/db into its own slab (torch
+// layout [co][ci][3][3] | db), reduced in fixed order by slk_reduce_slabs / slk_adam_from_slabs.
+// dC is the max-pool backward of a pooled gradient + routing code (as ConvCfg::EXP; the pooled values and
+// codes move by LDS-DMA into a raw staging area), so in every block of 4 consecutive pixels of one row
+// (x % 4 == 0: two pool windows' columns) at most 2 values per co are nonzero — the 2:4 structure of
+// v_smfmac_f32_16x16x64_bf16 (layout measured on the f16 form: slk_x3.hip's x3p notes,
 // tools/ubench/smfmac_probe.hip). The staging writes dC as compressed records (the exact register image of a
-// lane's A fragment: 8 bf16 + a u16 index word) instead of the dense tile, and each K64 step issues 4 x 9
-// sparse instructions instead of 2 x 4 x 9 dense ones on the same B fragments: the same products, summed in
-// another order (slabs within ~1e-8 of the dense form's).
+// lane's A fragment: 8 bf16 + a u16 index word), and each K64 step issues 4 x 9 sparse instructions where the
+// removed dense form (a dense dC tile read by transposed reads too) issued 2 x 4 x 9 dense ones on the same B
+// fragments: the same products, summed in another order (slabs within ~1e-8 of the dense form's).
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-// the K5 weight gradients on the 2:4-sparse bf16 MFMA (wide_wgrad_kernel<C, true>; 0: the dense form)
-#ifndef SLK_WIDE_WG_SPARSE
-#define SLK_WIDE_WG_SPARSE 1
-#endif
-#ifndef SLK_WIDE_WG_SPLIT
-#define SLK_WIDE_WG_SPLIT 1
-#endif
-#ifndef SLK_WIDE_WG_ABL
-#define SLK_WIDE_WG_ABL 0  // profiling only (wrong results): 1 no dC staging (sparse records), 2 no MFMA steps
-#endif
 
-template <int CI_, int CO_, int HW_, int TR_, int EXP_ = 0>
+template <int CI_, int CO_, int HW_, int TR_>
 struct WgCfg {
     static constexpr int CI = CI_, CO = CO_, HW = HW_, TR = TR_;
-    // EXP: dC is the max-pool backward of a pooled gradient + routing code (as ConvCfg::EXP), expanded
-    // into the dC tile in registers; the input halo tile still moves by LDS-DMA
-    static constexpr bool EXP = EXP_;
     static constexpr int XITEMS = 16 * (TR / 2) * (HW / 2);   // pooled dC chunks per tile (16 planes)
     static constexpr int COB = 128, CIB = 64;
     static constexpr int NCOB = CO / COB, NCIB = CI / CIB, NBLK = NCOB * NCIB;
     static constexpr int NPX = TR * HW;                  // pixels per tile (K per tile)
-    static constexpr int NPXP = NPX + 4;                 // dC plane stride (pixels): 64 mod 256 bytes
     static constexpr int PW = HW + 2;
     static constexpr int NP = (TR + 2) * PW;
     static constexpr int ND = (NP + 63) / 64;
     static constexpr int NPI = ND * 64 + 4;              // input plane stride (pixels)
-    static constexpr int DC_BYTES = (COB / 8) * NPXP * 16;
     static constexpr int IN_BYTES = (CIB / 8) * NPI * 16;
-    static constexpr int BUF = DC_BYTES + IN_BYTES;
-    static constexpr int RAW = EXP ? XITEMS * 24 : 0;    // EXP staging: values [512][16 B], code dwords 2 x [512][4 B]
-    static constexpr int LDS = 2 * BUF + RAW;
-    static constexpr int KS = NPX / 32;                  // MFMA k-steps per tile
+    static constexpr int RAW = XITEMS * 24;              // pooled dC staging: values [512][16 B], code dwords 2 x [512][4 B]
     static constexpr int RB = HW / TR;
     static constexpr int SLAB = CO * CI * 9 + CO;
     static constexpr int KSPLIT = 256 / NBLK;            // one workgroup per CU
-    // SP (the 2:4-sparse form, wide_wgrad_kernel<C, true>): the tile's dC as compressed records
-    // [K64 step][ga 4][co 128][8 bf16] + u16 index words [step][ga][co], then the input tile
+    // a tile buffer: the tile's dC as compressed records [K64 step][ga 4][co 128][8 bf16] + u16 index words
+    // [step][ga][co], then the input tile
     static constexpr int KS64 = NPX / 64;
     static constexpr int SREC = KS64 * 4 * COB * 16, SIDX = KS64 * 4 * COB * 2;
     static constexpr int SDC = (SREC + SIDX + 1023) / 1024 * 1024;
     static constexpr int SBUF = SDC + IN_BYTES;
-    static_assert(NPX % 32 == 0 && (HW == 32 || HW == 16), "tile");
-    static_assert(!EXP || (NPX == 128 && COB == 128 && (HW == 32 ? TR == 4 : TR == 8)), "SP staging geometry");
-    static_assert(DC_BYTES % 16 == 0 && ((NPX * 16) % 1024) == 0, "dC rows move in whole KiB");
-    static_assert(!EXP || XITEMS == 512, "EXP: one pooled chunk per thread");
+    static_assert(NPX == 128 && COB == 128 && (HW == 32 ? TR == 4 : TR == 8), "staging geometry");
+    static_assert(XITEMS == 512, "one pooled chunk per thread");
 };
 
-template <class C, bool SP = false>
+template <class C>
 __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __restrict__ dc,
                                                             const uint16_t* __restrict__ in,
                                                             float* __restrict__ slabs, int B,
-                                                            const uint8_t* __restrict__ dcode = nullptr) {
-    static_assert(!SP || C::EXP, "the sparse form stages dC from the pooled gradient");
-    constexpr int BUF = SP ? C::SBUF : C::BUF;           // one of the two tile buffers
-    constexpr int DCB = SP ? C::SDC : C::DC_BYTES;       // offset of the input tile in a buffer
+                                                            const uint8_t* __restrict__ dcode) {
+    constexpr int BUF = C::SBUF;                         // one of the two tile buffers
+    constexpr int DCB = C::SDC;                          // offset of the input tile in a buffer
     // SPLIT: the raw pooled dC double-buffered (DMA two tiles ahead), so half the waves (4-7) can stage the next
     // tile's records before their MFMAs and the other half after (the SIMD pair (w, w + 4) overlaps one's staging
     // with the other's MFMAs); otherwise every wave stages after its MFMAs
     // (conv2's kernel only: conv3's spilled 13 VGPRs with it, 0.369 -> 0.490 ms; conv2 0.373 -> 0.365,
     // profiles/r06_ab_wide_wgrad_split.txt)
-    constexpr bool SPLIT = SP && SLK_WIDE_WG_SPLIT && C::HW == 32;
+    constexpr bool SPLIT = C::HW == 32;
     __shared__ __attribute__((aligned(1024))) char smem[2 * BUF + (SPLIT ? 2 : 1) * C::RAW];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1063,10 +950,9 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
 
     // per-lane transposed-read bases (bytes within a buffer)
     const int q = lane >> 4, ig = lane & 15, a = ig >> 2, p = ig & 3;
-    const int a_base = (((wm * 64 + 4 * p) >> 3) * C::NPXP + 8 * q + a) * 16 + (p & 1) * 8;
-    const int pl = 8 * q + a, r0 = pl / C::HW, x0 = pl % C::HW;
-    // wave wn owns input channels cib*64 + 16*wn .. +15 (chunks 2wn, 2wn+1) for all 9 taps
-    const int b_base = DCB + (((2 * wn + (p >> 1)) * C::NPI) + (r0 + 1) * C::PW + x0 + 1) * 16 + (p & 1) * 8;
+    // wave (wm, wn) owns co wm*64 .. +63 and input channels cib*64 + 16*wn .. +15 (chunks 2wn, 2wn+1) for all 9
+    // taps: its first co, and the lane's 8-B half and chunk plane of the input tile
+    const int a_co = wm * 64, b_half = (p & 1) * 8, b_plane = (2 * wn + (p >> 1)) * C::NPI;
     const bool do_db = cib == 0;
     const short one = 0x3F80;  // bf16 1.0
     const bf16x8 ones = __builtin_bit_cast(bf16x8, (__attribute__((ext_vector_type(8))) short){one, one, one, one, one, one, one, one});
@@ -1081,21 +967,16 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
     // tile t -> (image, row block). XCD grouping: ks and ks + 8 share an XCD, so tiles t = ks + k*KSPLIT
     // with equal t % 8 run there together; all RB row blocks of image n go to XCD n % 8.
     auto tile_of = [&](int t, int& n, int& rb) {
-#if SLK_WIDE_XCD
         const int j = t >> 3;
         rb = j % C::RB;
         n = (j / C::RB) * 8 + (t & 7);
-#else
-        n = t / C::RB;
-        rb = t - n * C::RB;
-#endif
     };
     auto valid = [&](int t) {
         int n, rb;
         tile_of(t, n, rb);
         return n < B;
     };
-    // EXP: pooled dC chunk tid = (plane c, pooled row pr, pooled col px) of tile t, staged by this
+    // pooled dC chunk tid = (plane c, pooled row pr, pooled col px) of tile t, staged by this
     // thread's own wave (LDS-DMA into `raw`), so its expansion needs only that wave's vmcnt wait
     char* const raw = smem + 2 * BUF;  // SPLIT: raw buffer k & 1 holds the pooled dC of this workgroup's tile k
     auto exp_issue_dc = [&](int t, char* raw) {
@@ -1109,38 +990,9 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
         glds4(dcode + idx * 8, lds_u32(raw + C::XITEMS * 16 + i0 * 4));
         glds4(dcode + idx * 8 + 4, lds_u32(raw + C::XITEMS * 20 + i0 * 4));
     };
-    auto exp_expand_dc = [&](char* buf) {
-        constexpr int PH = C::HW / 2, PR = C::TR / 2;
-        const int c = tid / (PR * PH), rem = tid - c * (PR * PH), pr = rem / PH, px = rem - pr * PH;
-        const uint4 v = *reinterpret_cast<const uint4*>(raw + tid * 16);
-        const uint32_t c0 = *reinterpret_cast<const uint32_t*>(raw + C::XITEMS * 16 + tid * 4);
-        const uint32_t c1 = *reinterpret_cast<const uint32_t*>(raw + C::XITEMS * 20 + tid * 4);
-        const uint32_t cA = __builtin_amdgcn_perm(0u, c0, 0x01010000u), cB = __builtin_amdgcn_perm(0u, c0, 0x03030202u);
-        const uint32_t cC = __builtin_amdgcn_perm(0u, c1, 0x01010000u), cD = __builtin_amdgcn_perm(0u, c1, 0x03030202u);
-        char* base = buf + (c * C::NPXP + 2 * pr * C::HW + 2 * px) * 16;
-        // lanes with px & 4 walk the window's columns in the other order: the 8 lanes of a ds_write_b128
-        // group then fill all 8 16-B slots of 128 B (same order: 2-way on every store, 8.4 M cycles a launch)
-        const int f = (px >> 2) & 1;
-#pragma unroll
-        for (int pos0 = 0; pos0 < 4; ++pos0) {
-            const int pos = pos0 ^ f;
-            *reinterpret_cast<uint4*>(base + ((pos >> 1) * C::HW + (pos & 1)) * 16) = route_chunk(v, cA, cB, cC, cD, pos);
-        }
-    };
     auto issue_tile = [&](int t, char* buf) {
         int n, rb;
         tile_of(t, n, rb);
-        // dC rows: 16 chunk planes x (NPX*16/1024) KiB, 4 pieces per wave
-        constexpr int PPC = C::NPX * 16 / 1024;
-#pragma unroll
-        for (int k = 0; k < (C::EXP ? 0 : (16 * PPC) / 8); ++k) {
-            const int piece = wave * ((16 * PPC) / 8) + k;
-            const int c = piece / PPC, part = piece - (piece / PPC) * PPC;
-            const char* src = reinterpret_cast<const char*>(dc) +
-                              (((size_t)(n * (C::CO / 8) + cob * 16 + c) * C::HW + rb * C::TR) * C::HW) * 16 +
-                              part * 1024 + lane * 16;
-            glds16((const void*)src, lds_u32(buf + c * C::NPXP * 16 + part * 1024));
-        }
         // input halo tile: wave w moves chunk plane w (ND pieces), halo lanes read zeros
         const char* plane = reinterpret_cast<const char*>(in) +
                             ((size_t)(n * (C::CI / 8) + cib * 8 + wave) * (C::HW * C::HW)) * 16;
@@ -1155,30 +1007,28 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
         }
     };
 
-    // SP geometry. K64 step s of a tile = 16 blocks of 4 pixels of one row (x % 4 == 0): block L = 16 s + 4 gb + jb
+    // Geometry. K64 step s of a tile = 16 blocks of 4 pixels of one row (x % 4 == 0): block L = 16 s + 4 gb + jb
     // is row y, block xb (pixels 4 xb .. +3) with, for HW = 32, y = 2 s + (gb >> 1), xb = 2 (gb & 1) + (jb & 1) +
     // 4 (jb >> 1); for HW = 16, y = 4 s + 2 (gb >> 1) + (jb >> 1), xb = 2 (gb & 1) + (jb & 1). So blocks jb, jb + 1
     // (one record half) are adjacent (a window quad), and the two lane groups gb = 0, 1 of a 32-lane half of a
     // B read are 8 pixels (128 B) apart: their transposed reads hit disjoint banks.
     // B (input tile, ds_read_b64_tr_b16): lane (gb, ig = 4 a + p) reads pixel 4 xb + a of row y, chunk plane
-    // 2 wn + (p >> 1), 8-B half p & 1 (as the dense read): one read per block, 4 per fragment.
+    // 2 wn + (p >> 1), 8-B half p & 1: one read per block, 4 per fragment.
     // one per-lane base (block L = 4 gb) + a compile-time offset per (s, jb)
-    const int spb0 = DCB + (((2 * wn + (p >> 1)) * C::NPI) + ((C::HW == 32 ? (q >> 1) : 2 * (q >> 1)) + 1) * C::PW +
-                            8 * (q & 1) + a + 1) * 16 + (p & 1) * 8;
+    const int spb0 = DCB + (b_plane + ((C::HW == 32 ? (q >> 1) : 2 * (q >> 1)) + 1) * C::PW + 8 * (q & 1) + a + 1) * 16 + b_half;
     auto spb_off = [](int st, int jb) {
         return C::HW == 32 ? (2 * st * C::PW + 4 * (jb & 1) + 16 * (jb >> 1)) * 16
                            : ((4 * st + (jb >> 1)) * C::PW + 4 * (jb & 1)) * 16;
     };
     // A: lane (ga = q, m = ig) of M tile i reads record (s, ga, co = 64 wm + 16 i + m) and its index word
-    const int sp_arec = ((q * C::COB) + wm * 64 + ig) * 16, sp_aidx = C::SREC + ((q * C::COB) + wm * 64 + ig) * 2;
-    // SP staging: thread (wave w, lane l) = items (co = 8 c + (l & 7), c = 2 w + k, k = 0, 1; pooled row pr; window quad
+    const int sp_arec = (q * C::COB + a_co + ig) * 16, sp_aidx = C::SREC + (q * C::COB + a_co + ig) * 2;
+    // Staging: thread (wave w, lane l) = items (co = 8 c + (l & 7), c = 2 w + k, k = 0, 1; pooled row pr; window quad
     // P): the quad's 4 windows (pooled px = 4 P .. +3, the raw items this wave's own DMA staged) are the two blocks
     // 2 P, 2 P + 1 of output rows 2 pr + d, i.e. one record half (8 B) + one index byte per d. Lane bits 0-2 = co,
     // bit 3 = the half (P & 1): a 16-lane ds_write_b64 group covers 16 distinct 8-B slots of 128 B.
     const int sco = lane & 7, sP0 = (lane >> 3) & 1, srest = lane >> 4;
     const int spr = C::HW == 32 ? (srest & 1) : srest, sP = C::HW == 32 ? sP0 + 2 * (srest >> 1) : sP0;
     auto sp_expand = [&](char* buf, const char* raw) {
-        if (SLK_WIDE_WG_ABL & 1) return;  // profiling only
         constexpr int PH = C::HW / 2, PR = C::TR / 2;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -1215,19 +1065,16 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
     int t = ks, b = 0;
     if (valid(t)) {
         issue_tile(t, smem);
-        if constexpr (C::EXP) {
-            exp_issue_dc(t, raw);
-            wait_vmcnt<0>();
-            if constexpr (SP) sp_expand(smem, raw);
-            else exp_expand_dc(smem);
-            if (SPLIT && valid(t + C::KSPLIT)) exp_issue_dc(t + C::KSPLIT, raw + C::RAW);
-        }
+        exp_issue_dc(t, raw);
+        wait_vmcnt<0>();
+        sp_expand(smem, raw);
+        if (SPLIT && valid(t + C::KSPLIT)) exp_issue_dc(t + C::KSPLIT, raw + C::RAW);
     }
     const bool sfirst = wave >= 4;
 #pragma unroll 1
     for (; valid(t); t += C::KSPLIT) {
         wait_vmcnt<0>();
-        if constexpr (C::EXP) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // dC tile written
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // dC tile written
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const bool more = valid(t + C::KSPLIT);
@@ -1236,14 +1083,14 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
             if constexpr (SPLIT) {
                 // tile k + 2's pooled dC into raw buffer k & 1 (tile k's, staged during tile k - 1)
                 if (valid(t + 2 * C::KSPLIT)) exp_issue_dc(t + 2 * C::KSPLIT, raw + b * C::RAW);
-            } else if constexpr (C::EXP) {
+            } else {
                 exp_issue_dc(t + C::KSPLIT, raw);
             }
         }
         // SPLIT: tile k + 1's raw dC landed by the wait above (its DMA was issued a tile ago)
         if (SPLIT && more && sfirst) sp_expand(smem + (b ^ 1) * BUF, raw + (b ^ 1) * C::RAW);
         const char* buf = smem + b * BUF;
-        if constexpr (SP && !(SLK_WIDE_WG_ABL & 2)) {
+        {
             typedef __attribute__((address_space(3))) bf16x4* lp4;
             typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
             const bf16x16 ones16 = __builtin_shufflevector(ones, ones, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
@@ -1280,45 +1127,14 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
                 }
             }
         }
-#pragma unroll
-        for (int j = 0; j < (SP ? 0 : C::KS); ++j) {
-            typedef __attribute__((address_space(3))) bf16x4* lp4;
-            bf16x8 av[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const char* pa = buf + a_base + i * 2 * C::NPXP * 16 + j * 32 * 16;
-                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp4)pa);
-                const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp4)(pa + 64));
-                av[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
-            if (do_db) {  // wave (wm, wn) sums co fragment wn
-                bf16x8 adb = av[0];
-#pragma unroll
-                for (int i = 1; i < 4; ++i) adb = wn == i ? av[i] : adb;
-                accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adb, ones, accb, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 9; ++u) {               // u = tap
-                const int toff = ((u / 3 - 1) * C::PW + (u % 3 - 1)) * 16;
-                const char* pb = buf + b_base + toff + j * (32 / C::HW) * C::PW * 16;
-                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp4)pb);
-                const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp4)(pb + 64));
-                const bf16x8 bv = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                if (SLK_WIDE_PRIO & 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv, acc[i][u], 0, 0, 0);
-                if (SLK_WIDE_PRIO & 2) __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        // EXP: the next tile's dC, routed into the other buffer (free since this tile's barrier) once
+        // the next tile's dC, routed into the other buffer (free since this tile's barrier) once
         // this wave's staging DMA has landed
         if constexpr (SPLIT) {
             if (more && !sfirst) sp_expand(smem + (b ^ 1) * BUF, raw + (b ^ 1) * C::RAW);
-        } else if constexpr (C::EXP) {
+        } else {
             if (more) {
                 wait_vmcnt<0>();
-                if constexpr (SP) sp_expand(smem + (b ^ 1) * BUF, raw);
-                else exp_expand_dc(smem + (b ^ 1) * BUF);
+                sp_expand(smem + (b ^ 1) * BUF, raw);
             }
         }
         b ^= 1;
@@ -1345,20 +1161,19 @@ __global__ __launch_bounds__(512, 1) void wide_wgrad_kernel(const uint16_t* __re
     }
 }
 
-using CfgWg2 = WgCfg<64, 128, 32, 4, 1>;   // dC = routed dp2 (EXP)
-using CfgWg3 = WgCfg<128, 256, 16, 8, 1>;   // dC = routed dcut (EXP)
+using CfgWg2 = WgCfg<64, 128, 32, 4>;   // dC = routed dp2
+using CfgWg3 = WgCfg<128, 256, 16, 8>;   // dC = routed dcut
 
 template <class C>
 static int launch_wgrad(const uint16_t* dc, const uint16_t* in, float* slabs, int B, void* stream,
-                        const uint8_t* dcode = nullptr) {
-    SLK_CHECK_ARG(B >= 0 && dc && in && slabs && (!C::EXP || dcode));
-    hipLaunchKernelGGL((wide_wgrad_kernel<C, SLK_WIDE_WG_SPARSE != 0>), dim3(256), dim3(512), 0, slk_stream(stream), dc, in,
-                       slabs, B, dcode);
+                        const uint8_t* dcode) {
+    SLK_CHECK_ARG(B >= 0 && dc && in && slabs && dcode);
+    hipLaunchKernelGGL(wide_wgrad_kernel<C>, dim3(256), dim3(512), 0, slk_stream(stream), dc, in, slabs, B, dcode);
     return slk_launch_status();
 }
 
 extern "C" int slk_wide_conv2_wgrad_nslab(int B) { return B >= 0 ? CfgWg2::KSPLIT : 0; }
-extern "C" int slk_wide_wgrad_form() { return SLK_WIDE_WG_SPARSE ? 1 : 0; }
+extern "C" int slk_wide_wgrad_form() { return 1; }  // 1: the 2:4-sparse form, the only one built (0 was the dense form)
 extern "C" int slk_wide_conv3_wgrad_nslab(int B) { return B >= 0 ? CfgWg3::KSPLIT : 0; }
 extern "C" int slk_wide_conv2_wgrad(const uint16_t* dp2, const uint8_t* code2, const uint16_t* a1, float* slabs, int B,
                                     void* stream) {

@@ -324,10 +324,7 @@ constexpr int AD_WAVES = 16;
 // waves over the slab range, partials added in wave order.
 // Round 6: 17-64 slabs (the conv3 and fc sets at B = 4096) as 4 waves per 64 columns, each summing every 4th
 // slab, partials added in order, 256 columns per block (a thread per column walked 64 slabs in 8 dependent rounds).
-#ifndef SLK_AD_MID
-#define SLK_AD_MID 1
-#endif
-constexpr int AD_COLS_MAX = SLK_AD_MID ? 16 : 64, AD_MID_MAX = 64;
+constexpr int AD_COLS_MAX = 16, AD_MID_MAX = 64;
 __host__ __device__ constexpr int adam_cols_per_block(int nslab) {
     return nslab <= AD_COLS_MAX ? 1024 : (nslab <= AD_MID_MAX ? 256 : 64);
 }

@@ -131,18 +131,6 @@ __global__ __launch_bounds__(256) void row_amax_kernel(const float* __restrict__
 #ifndef SLK_X3D_TRACE
 #define SLK_X3D_TRACE 0
 #endif
-// profiling only (wrong results): the launch heads' global reads replaced by values made from the index — bit 1 the
-// forward's W2 reads, bit 2 the dgrad's W2 reads, bit 4 the wgrads' act_amax / dp_amax reads. Against the product
-// build this bounds what the heads' memory latency costs per launch.
-#ifndef SLK_X3H_ABL
-#define SLK_X3H_ABL 0
-#endif
-// element e of a head's global operand (SLK_X3H_ABL bit set: a value made from the index, no load)
-template <int BIT>
-__device__ __forceinline__ float x3_head_ld(const float* __restrict__ p, int e) {
-    if constexpr ((SLK_X3H_ABL & BIT) != 0) return (float)((e & 1023) + 1) * 0x1p-12f;
-    else return p[e];
-}
 #if SLK_X3D_TRACE
 // profiling probe: per (workgroup, wave, unit) shader-clock stamps of the dgrad's phases (lane 0, vector stores)
 __device__ unsigned long long g_x3d_trace[256 * 8 * 128 * 8];
@@ -153,10 +141,11 @@ __device__ unsigned long long g_x3d_trace[256 * 8 * 128 * 8];
         if (lane == 0 && (u) < 128) buf[(((size_t)blockIdx.x * 8 + wave) * 128 + (u)) * 8 + (slot)] = _t;  \
     } while (0)
 #define X3D_TS(u, slot) X3_TS(g_x3d_trace, u, slot)
-#define X3Q_TS(u, slot) X3_TS(g_x3q_trace, u, slot)
-__device__ unsigned long long g_x3q_trace[256 * 8 * 128 * 8];
-extern "C" int slk_x3q_trace_read(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3q_trace), sizeof(g_x3q_trace)) == hipSuccess ? 0 : 1;
+// the sparse wgrad's stamps (conv2_wgrad_x3p_kernel)
+#define X3P_TS(u, slot) X3_TS(g_x3p_trace, u, slot)
+__device__ unsigned long long g_x3p_trace[256 * 8 * 128 * 8];
+extern "C" int slk_x3p_trace_read(void* dst) {
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3p_trace), sizeof(g_x3p_trace)) == hipSuccess ? 0 : 1;
 }
 // the forward's stamps: launch start (0, 7), weights in registers (1, 7), each unit's barrier (k, 0), end (127, 7)
 __device__ unsigned long long g_x3f_trace[256 * 8 * 128 * 8];
@@ -169,7 +158,7 @@ extern "C" int slk_x3d_trace_read(void* dst) {
 }
 #else
 #define X3D_TS(u, slot)
-#define X3Q_TS(u, slot)
+#define X3P_TS(u, slot)
 #define X3F_TS(u, slot)
 #endif
 
@@ -400,7 +389,7 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
     static_assert(WR * X3F_THREADS == W2_N && WR % 2 == 0, "a thread's W2 dwords, half per co half");
     float wv[WR];
 #pragma unroll
-    for (int r = 0; r < WR; ++r) wv[r] = x3_head_ld<1>(W2, tid + X3F_THREADS * r);
+    for (int r = 0; r < WR; ++r) wv[r] = W2[tid + X3F_THREADS * r];
     float bias[X3F_NT];
 #pragma unroll
     for (int nt = 0; nt < X3F_NT; ++nt) bias[nt] = b2[32 * ch + 16 * nt + n16];
@@ -759,12 +748,6 @@ __global__ __launch_bounds__(X3F_THREADS, 1) void conv2_fwd_pool_x3_kernel(
 // fragments for both co halves (2 x 9 x (h, l) = 144 VGPRs) stay in registers, its <= 4 accumulators live
 // across the part's two co halves.
 // ReLU bitmap of the cut (written by conv1_fwd_x3_kernel, layout there): u32 words per (ci, u), per sample
-#ifndef SLK_X3W_ROUND4
-#define SLK_X3W_ROUND4 0
-#endif
-#ifndef SLK_X3W_SPARSE
-#define SLK_X3W_SPARSE 1
-#endif
 constexpr int RB_SAMPLE = 4 * (A_PIX / 4);  // 676 u32 = 2,704 B per sample: [channel group 4][169]
 constexpr int X3D_THREADS = 512;
 constexpr int X3D_REC = 160;                       // bytes per image pixel: h 64 | l 64 | pad 32
@@ -776,15 +759,6 @@ constexpr int X3D_MPW = 4;                         // M tiles per wave and part 
 constexpr int X3D_GRID = 256;
 constexpr int X3D_ITEMS_MAX = 7 * P_HW * 8;        // (window, 4-co group) items of the largest part (672)
 static_assert(2 * X3D_IMG <= 163840, "LDS");
-// the fused dgrad's client epilogue on the f16 MFMA (split operands) instead of the f32 MFMA
-#ifndef SLK_X3D_EPI16
-#define SLK_X3D_EPI16 0
-#endif
-// profiling only (wrong results): bit 1 no dY staging, bit 2 no client epilogue, bit 4 its f32 MFMAs as one fma,
-// bit 8 no dY global loads (the staging stores kept)
-#ifndef SLK_X3D_ABL
-#define SLK_X3D_ABL 0
-#endif
 
 __device__ __forceinline__ int x3d_t0(int pt) { return pt == 0 ? 0 : (pt == 1 ? 15 : 29); }
 __device__ __forceinline__ int x3d_ybase(int pt) { return pt == 0 ? -2 : (pt == 1 ? 6 : 14); }
@@ -881,13 +855,8 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
                 // compiler wait for the loads on the spot (a full memory latency per unit)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-#if SLK_X3D_ABL & 8
-                    dv[r][j] = (float)((o + j) & 255) * 1e-3f;  // no global loads
-                    dcb[r][j] = (uint32_t)(o + j) & 3u;
-#else
                     dv[r][j] = dpooled[o + j * P_WIN];
                     dcb[r][j] = code[o + j * P_WIN];
-#endif
                 }
             }
         }
@@ -1003,7 +972,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
         static_assert(WR * X3D_THREADS == W2_N && (W2_N + WPAD * (W2_N / WKC)) * 4 + 64 <= 2 * X3D_IMG, "W2 staging");
         float wv[WR];
 #pragma unroll
-        for (int r = 0; r < WR; ++r) wv[r] = x3_head_ld<2>(W2, tid + X3D_THREADS * r);
+        for (int r = 0; r < WR; ++r) wv[r] = W2[tid + X3D_THREADS * r];
         if (pr < p1) load_dy(2 * pr);
         float wm = 0.f;
 #pragma unroll
@@ -1097,35 +1066,6 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
                 ++y0;
             }
         }
-#if SLK_X3D_EPI16
-        // the same GEMM on the f16 MFMA: g (scaled by 2^-22: |g| < 576 * 2^28 before it, so hi < 36,864)
-        // and x split hi/lo, K = the lane group's 8 (tile, r) pixels per instruction, 2 hi*hi + 4 cross
-        // products in two chains from zero per pair (the accumulation-bias note above)
-        f16x8 gh[2], gl[2], bh[2], bl[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            float gv[8], xw[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = 2 * s + (j >> 2), r = j & 3;
-                gv[j] = __uint_as_float(__float_as_uint(acc[i][r]) & (0u - ((mw[i] >> r) & 1u)));
-                xw[j] = xv[i][r];
-            }
-            x3_split8(gv, 0x1p-22f, gh[s], gl[s]);
-            x3_split8(xw, 1.f, bh[s], bl[s]);
-        }
-        f32x4 dh = f32x4{0.f, 0.f, 0.f, 0.f}, dc = f32x4{0.f, 0.f, 0.f, 0.f};
-        slk_keep(dh);
-        slk_keep(dc);
-        dh = mfma_f16(gh[0], bh[0], dh);
-        dc = mfma_f16(gh[0], bl[0], dc);
-        dh = mfma_f16(gh[1], bh[1], dh);
-        dc = mfma_f16(gl[0], bh[0], dc);
-        dc = mfma_f16(gh[1], bl[1], dc);
-        dc = mfma_f16(gl[1], bh[1], dc);
-        d1s[tid] = d1s[tid] + (dh + dc) * (us1e * 0x1p22f);
-        return;
-#endif
         f32x4 dr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1141,11 +1081,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
                     const uint32_t keep = 0u - ((mw[i] >> r) & 1u);
                     // (by value: __builtin_bit_cast of the vector element acc[i][r] read one element for all r)
                     const float gm = __uint_as_float(__float_as_uint(acc[i][r]) & keep);
-#if SLK_X3D_ABL & 4
-                    dr[r][0] = fmaf(gm, xv[i][r], dr[r][0]);
-#else
                     dr[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(gm, xv[i][r], dr[r], 0, 0, 0);
-#endif
                 }
             }
         }
@@ -1191,7 +1127,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
             // the next unit's dY (always: past the last unit it stages a clamped valid unit, unused).
             // Half the waves stage before their MFMAs, half after, so the two waves of a SIMD overlap
             // one's staging with the other's MFMAs (both staging at once left the SIMD's MFMA idle).
-            if (sfirst && !(SLK_X3D_ABL & 1)) {
+            if (sfirst) {
                 store_dy(unx, nimg);
                 load_dy(unx2);
             }
@@ -1218,7 +1154,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
                 if (st + 3 < NS) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             }
             X3D_TS(k, 2);
-            if (!sfirst && !(SLK_X3D_ABL & 1)) {
+            if (!sfirst) {
                 store_dy(unx, nimg);
                 load_dy(unx2);
             }
@@ -1246,11 +1182,7 @@ __global__ __launch_bounds__(X3D_THREADS, 1) void conv2_dgrad_x3_kernel(
         // epilogue: unscale (exact) and store 4 consecutive pixels per lane
         const float us1 = ldexpf(1.f, -x3_exp(amax_b)), us2 = ldexpf(1.f, -sw);
         if constexpr (C1W) {
-            if (!(SLK_X3D_ABL & 2)) c1w_epi(T0, T1, us1, q);
-            else {
-#pragma unroll
-                for (int i = 0; i < X3D_MPW; ++i) slk_keep(acc[i]);  // the MFMA stream stays live
-            }
+            c1w_epi(T0, T1, us1, q);
             X3D_TS(k - 1, 5);
         } else if (pack) {
             // the lane's 4 pixels are 4 consecutive elements of one mask word (A_PIX and p are multiples of 4);
@@ -1343,14 +1275,11 @@ constexpr int X3W_DYITEMS = 48 * 8;                  // (window, 4-co group) dY 
 static_assert(X3W_DYITEMS % 64 == 0, "whole waves of dY items");
 static_assert(2 * X3W_BUF <= 163840, "LDS");
 
-// X16 = true: the input image of a unit is the f16 image conv2_fwd_pool_x3 / conv1_fwd_x3 wrote (act16,
-// per-sample scale 2^s_b, dY compensated by 2^(sd + sx - s_b) as above; chunk slot kc ^ (x & 2), i.e. the 32-B ci-half slot h ^ ((x >> 1) & 1)), moved by LDS-DMA
-// one unit ahead straight into the image buffer: no gather loads, no split VALU.
-template <bool X16>
+// The f32-act form (slk_conv2_wgrad_x3). The form that read act16 images through this kernel (round 4) was
+// superseded by conv2_wgrad_x3p_kernel below.
 __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
     const float* __restrict__ act, const float* __restrict__ act_amax, const float* __restrict__ dpooled,
-    const float* __restrict__ dp_amax, const uint8_t* __restrict__ code, float* __restrict__ slabs, int B,
-    const uint16_t* __restrict__ act16 = nullptr) {
+    const float* __restrict__ dp_amax, const uint8_t* __restrict__ code, float* __restrict__ slabs, int B) {
     __shared__ __attribute__((aligned(1024))) char smem[2 * X3W_BUF];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1479,7 +1408,7 @@ __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
     // them on disjoint banks (chunks 8 pixels apart in one row were 2-way: tools/lds_banks.py)
     const int g4 = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
     int abase[3][2];  // dY: pixel q = 24 orow + 8 seg + qq (+4), co tile mi in slot mi ^ ((q >> 3) & 1)
-    int xbase[3][3];  // input per (this wave's K-step j, kx); X16 images keep ci half h in slot h ^ ((x >> 1) & 1)
+    int xbase[3][3];  // input per (this wave's K-step j, kx): ci half h in slot h
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int idx = 2 * (kp + 2 * j) + (g4 >> 1);
@@ -1490,14 +1419,9 @@ __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
             const int x = 8 * seg + qq + kx;
-            const int slot = X16 ? (h ^ ((x >> 1) & 1)) : h;
-            xbase[j][kx] = 2 * X3W_DYP + ((orow * A_HW + x) * 64) + slot * 32 + pp * 8;
+            xbase[j][kx] = 2 * X3W_DYP + ((orow * A_HW + x) * 64) + h * 32 + pp * 8;
         }
     }
-    // X16 staging: 2,080 16-B pieces per unit, lane-contiguous (the image is stored as it sits in LDS)
-    auto issue_x16 = [&](int uu, char* img) {
-        x3_issue_unit_img(act16, uu, __builtin_amdgcn_readfirstlane(tid >> 6), lane, lds_u32(img + 2 * X3W_DYP));
-    };
     typedef __fp16 hf4 __attribute__((__vector_size__(8)));
     typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) hf4* lp4;
@@ -1567,30 +1491,16 @@ __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
     const int u0 = min(ks * per, U), u1 = min(u0 + per, U);
     int u = u0;
     if (u < u1) {
-        if constexpr (X16) {
-            issue_x16(u, smem);
-        } else {
-            load_x(u);
-        }
+        load_x(u);
         load_dy(u);
-        if constexpr (!X16) split_x(smem);
+        split_x(smem);
         store_dy(smem, true);
-        if constexpr (!X16) load_x(min(u + 1, u1 - 1));
+        load_x(min(u + 1, u1 - 1));
         load_dy(min(u + 1, u1 - 1));
     }
     int k = 0;
 #pragma unroll 1
     for (; u < u1; ++u, ++k) {
-        // X16: this unit's image DMA landed; the 8 dY loads of load_dy, every wave's last memory
-        // instructions (issued after its DMA), may stay in flight
-        const bool dfirst = !X16 || tg == 1;
-        // X16: waves 6-7 hold no dY item (384 items = waves 0-5) and skip the routing (no redundant
-        // redo of item 383); their last memory instructions are then the DMA itself
-        const bool dstage = !(X16 && wave >= X3W_DYITEMS / 64);
-        if constexpr (X16) {
-            if (!dstage) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        }
         __syncthreads();  // image k&1 complete; image (k+1)&1 free
         const int nx = u + 1, nx2 = u + 2;
         const char* img = smem + (k & 1) * X3W_BUF;
@@ -1598,30 +1508,14 @@ __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
         // unit u+1's rows and dY were requested a whole unit ago. No branch around the staging (past the
         // last unit it re-stages a clamped valid unit nobody reads), so it shares one basic block with
         // the MFMAs and its VALU can fill their issue gaps
-        // X16: the tap-group-1 waves (the lighter MFMA share) route dY before their MFMAs, the tap-group-0
-        // waves after theirs, so the two waves of a SIMD overlap routing with MFMAs. store_dy goes before
-        // the DMA issue: the compiler does not count the asm DMAs, so its wait for the dY registers
-        // would otherwise also wait for the DMA just issued
-        if (dfirst && dstage) store_dy(nimg, nx < u1);
-        if constexpr (X16) {
-            // (spreading these pieces over the MFMA steps, as the forward does, measured 0.2258 -> 0.2388 ms:
-            // the pinned read/MFMA order does not absorb them)
-            issue_x16(min(nx, u1 - 1), nimg);
-        } else {
-            split_x(nimg);
-        }
-        if (dfirst && dstage) {
-            if constexpr (!X16) load_x(min(nx2, u1 - 1));
-            load_dy(min(nx2, u1 - 1));
-        }
+        store_dy(nimg, nx < u1);
+        split_x(nimg);
+        load_x(min(nx2, u1 - 1));
+        load_dy(min(nx2, u1 - 1));
         if (tg == 0) unit_mfma(img, std::integral_constant<int, 0>{});
         else unit_mfma(img, std::integral_constant<int, 1>{});
-        if (!dfirst && dstage) {
-            store_dy(nimg, nx < u1);
-            load_dy(min(nx2, u1 - 1));
-        }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (clamped) image DMA lands before LDS reuse
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (clamped) loads land before LDS reuse
     __syncthreads();
     // K parities: kp = 1 waves hand their sums to kp = 0 through LDS (region per (h, tg))
     constexpr int XN = 2 * 5 * 4;  // floats per lane
@@ -1667,284 +1561,6 @@ __global__ __launch_bounds__(X3W_THREADS, 1) void conv2_wgrad_x3_kernel(
     }
 }
 
-// ============================================================================ conv2 wgrad, both co halves per workgroup
-// The act16-image form of the x3 wgrad (round 5) with one workgroup per K share owning ALL of dW2: the
-// unit is (sample, sixth) = output rows 4t .. 4t + 3 (K = 96 pixels = 3 K-steps), so both co halves' dY
-// planes (4 x 6 KiB) and the unit's input image (rows 4t .. 4t + 5, 2 x 9.75 KiB) fit twice into LDS
-// (the 8-row unit with both co halves needed 164,864 B, 1 KiB over): the input image is moved by LDS-DMA
-// once for the 64 co instead of once per co half by two workgroups (the DMA of that image was 11 % of the
-// round-4 kernel), and no K-parity partial sums are exchanged at the end. 8 waves = (tap group tg, co half
-// c, ci half h), wave = 4 tg + 2 c + h: the two waves of a SIMD (w, w + 4) carry one tap group each; per
-// unit a wave does all 3 K-steps x its taps x both M tiles of its co half — the same fragment reads and
-// MFMAs per unit as the round-4 wave. dY staging as conv2_wgrad_x3_kernel (register loads two units
-// ahead, routed one unit ahead), items (4-co group, co half, window) with the co half's planes offset by
-// 64 B so a 16-lane store group (8 groups x 2 co halves of one window) covers 32 distinct banks.
-constexpr int X3Q_ROWS = 4;                              // output rows per unit (6 units per sample)
-constexpr int X3Q_Q = X3Q_ROWS * 24;                     // 96 output pixels = K per unit
-constexpr int X3Q_DYP = X3Q_Q * 64;                      // 6,144 B per dY plane (32 co of one co half)
-constexpr int X3Q_DYC = 2 * X3Q_DYP + 64;                // co half stride: h | l planes + 64 B
-constexpr int X3Q_XPIX = (X3Q_ROWS + 2) * A_HW;          // 156 input pixels per unit
-constexpr int X3Q_XP = X3Q_XPIX * 64;                    // 9,984 B per input plane
-constexpr int X3Q_DYOFF = 2 * X3Q_XP;                    // dY planes after the input planes (1 KiB aligned start)
-constexpr int X3Q_BUF = (X3Q_DYOFF + 2 * X3Q_DYC + 1023) / 1024 * 1024;  // 45,056 B per buffer
-constexpr int X3Q_NKS = 256;                             // K shares (slabs): one workgroup per CU
-constexpr int X3Q_DYITEMS = 24 * 16;                     // (window, 4-co group, co half) items per unit
-constexpr int X3Q_XPIECES = X3Q_XP / 1024 + 1;           // 10 DMA pieces per input plane (the last 768 B)
-static_assert(2 * X3Q_BUF <= 163840 && X3Q_XP % 1024 == 768 && (X3Q_DYC / 4) % 32 == 16, "x3q layout");
-
-// (round 5: 12 waves = 3 per SIMD at <= 168 VGPRs, tap groups of 3, measured the same: 0.2369 vs 0.2376 ms)
-constexpr int X3Q_THREADS = 512;
-constexpr int X3Q_WAVES = X3Q_THREADS / 64;
-constexpr int X3Q_NTMAX = 5;                             // taps per wave (max)
-
-// LDS-DMA of unit uu's input image (rows 4t .. 4t + 5 of both planes of the sample's act16 image)
-__device__ __forceinline__ void x3q_issue_img(const uint16_t* act16, int uu, int wave, int lane, uint32_t lds) {
-    const int b = uu / 6, t = uu - (uu / 6) * 6;
-    const char* src = reinterpret_cast<const char*>(act16) + (size_t)b * X3S_SAMPLE + t * (X3Q_ROWS * A_HW * 64);
-#pragma unroll
-    for (int r = 0; r < (2 * X3Q_XPIECES + X3Q_WAVES - 1) / X3Q_WAVES; ++r) {
-        const int k = wave + X3Q_WAVES * r;  // piece k of the 20: plane k / 10, piece k % 10
-        if (k < 2 * X3Q_XPIECES) {
-            const int pl = k >= X3Q_XPIECES ? 1 : 0, pp = k - X3Q_XPIECES * pl;
-            if (pp < X3Q_XPIECES - 1 || lane < (X3Q_XP % 1024) / 16)
-                glds16_so(src + pl * X3S_PLANE, (uint32_t)(pp * 1024 + lane * 16), lds + pl * X3Q_XP + pp * 1024);
-        }
-    }
-}
-
-__global__ __launch_bounds__(X3Q_THREADS, 1) void conv2_wgrad_x3q_kernel(
-    const uint16_t* __restrict__ act16, const float* __restrict__ act_amax, const float* __restrict__ dpooled,
-    const float* __restrict__ dp_amax, const uint8_t* __restrict__ code, float* __restrict__ slabs, int B) {
-    __shared__ __attribute__((aligned(1024))) char smem[2 * X3Q_BUF];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = wave & 1, c = (wave >> 1) & 1, tg = wave >> 2;
-    const int ks = blockIdx.x, nks = gridDim.x;
-    const int U = 6 * B;
-    float* red = reinterpret_cast<float*>(smem);  // prologue scratch (buffer 0, before any staging)
-    X3Q_TS(0, 7);
-
-    // launch scales: max over the batch of the per-sample maxima (as conv2_wgrad_x3_kernel)
-    float ma = 0.f, md = 0.f;
-    for (int i = tid; i < B; i += X3Q_THREADS) {
-        ma = fmaxf(ma, x3_head_ld<4>(act_amax, i));
-        md = fmaxf(md, x3_head_ld<4>(dp_amax, i));
-    }
-    ma = wave_max(ma);
-    md = wave_max(md);
-    if (lane == 0) {
-        red[wave] = ma;
-        red[16 + wave] = md;
-    }
-    __syncthreads();
-    ma = red[0];
-    md = red[16];
-#pragma unroll
-    for (int i = 1; i < X3Q_WAVES; ++i) {
-        ma = fmaxf(ma, red[i]);
-        md = fmaxf(md, red[16 + i]);
-    }
-    __syncthreads();
-    const int sx = x3_exp(ma), sd = x3_exp(md);
-    int sb_ld = 0;
-
-    // dY items: i = tid < 384 -> 4-co group dg = i & 7 of co half ci2 = (i >> 3) & 1, window dw = i >> 4
-    // (24 windows: 2 window rows x 12); waves 6-7 hold none
-    const bool dstage = tid < X3Q_DYITEMS;
-    const int dg = tid & 7, dc = (tid >> 3) & 1, dw = min(tid >> 4, 23);
-    float dv[4];
-    uint32_t dcb[4];
-    auto load_dy = [&](int uu) {
-        const int b = uu / 6, t = uu - (uu / 6) * 6;
-        const int w = (2 * t + dw / 12) * P_HW + dw % 12;
-        const size_t o = (size_t)b * P_SAMPLE + (32 * dc + 4 * dg) * P_WIN + w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dv[j] = dpooled[o + j * P_WIN];
-            dcb[j] = code[o + j * P_WIN];
-        }
-        sb_ld = max(x3_exp(act_amax[b]), sx);
-    };
-    float dbacc[4] = {0.f, 0.f, 0.f, 0.f};
-    auto store_dy = [&](char* img, bool real) {
-        const float dsc = ldexpf(1.f, sd + sx - sb_ld);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dbacc[j] = (real && dcb[j] != (uint32_t)CODE_NONE) ? dbacc[j] + dv[j] : dbacc[j];
-        uint32_t hv[2], lv[2];
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            const float a = dv[j] * dsc, cc = dv[j + 1] * dsc;
-            const _Float16 ha = (_Float16)a, hc = (_Float16)cc;
-            const _Float16 la = (_Float16)(a - (float)ha), lc = (_Float16)(cc - (float)hc);
-            hv[j / 2] = __builtin_bit_cast(uint32_t, f16x2{ha, hc});
-            lv[j / 2] = __builtin_bit_cast(uint32_t, f16x2{la, lc});
-        }
-        const uint32_t dcw = dcb[0] | (dcb[1] << 8) | (dcb[2] << 16) | (dcb[3] << 24);
-        const uint32_t cA = __builtin_amdgcn_perm(0u, dcw, 0x01010000u), cB = __builtin_amdgcn_perm(0u, dcw, 0x03030202u);
-        const int wy = dw / 12, wx = dw % 12;
-        char* plane = img + X3Q_DYOFF + dc * X3Q_DYC;
-#pragma unroll
-        for (int pos = 0; pos < 4; ++pos) {
-            const uint32_t T = 0xFFu << (8 * pos);
-            const uint32_t mA = __builtin_amdgcn_perm(0u, T, cA), mB = __builtin_amdgcn_perm(0u, T, cB);
-            const int q = (2 * wy + (pos >> 1)) * 24 + 2 * wx + (pos & 1);
-            // co tile (dg >> 2) sits in slot (dg >> 2) ^ ((q >> 3) & 1), as in conv2_wgrad_x3_kernel
-            char* o = plane + q * 64 + ((((dg >> 2) ^ (q >> 3)) & 1) * 32) + 8 * (dg & 3);
-            *reinterpret_cast<uint2*>(o) = make_uint2(hv[0] & mA, hv[1] & mB);
-            *reinterpret_cast<uint2*>(o + X3Q_DYP) = make_uint2(lv[0] & mA, lv[1] & mB);
-        }
-    };
-
-    // transposed-read bases (conv2_wgrad_x3_kernel's, every K-step j = 0..2 of the 4-row unit)
-    const int g4 = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-    int abase[3][2], xbase[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int idx = 2 * j + (g4 >> 1);
-        const int orow = 2 * (idx / 3) + (g4 & 1), seg = idx % 3;
-        const int q0 = 24 * orow + 8 * seg;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-            abase[j][mi] = X3Q_DYOFF + c * X3Q_DYC + (q0 + qq) * 64 + ((mi ^ ((q0 >> 3) & 1)) * 32) + pp * 8;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int x = 8 * seg + qq + kx;
-            xbase[j][kx] = ((orow * A_HW + x) * 64) + (h ^ ((x >> 1) & 1)) * 32 + pp * 8;
-        }
-    }
-    typedef __fp16 hf4 __attribute__((__vector_size__(8)));
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) hf4* lp4;
-    auto trr = [&](const char* p) -> f16x8 {
-        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp4)p));
-        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp4)(p + 4 * 64)));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-
-    f32x4 acc[2][X3Q_NTMAX];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int t = 0; t < X3Q_NTMAX; ++t) acc[mi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto unit_mfma = [&](const char* img, auto TG) {
-        constexpr int TGV = decltype(TG)::value;
-        constexpr int T0 = TGV ? 5 : 0, NT = TGV ? 4 : 5;
-        constexpr int N = 3 * NT;
-        f16x8 Ah[2][2], Al[2][2], Bh[3], Bl[3];
-        auto rdA = [&](int j, int slot) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                Ah[slot][mi] = trr(img + abase[j][mi]);
-                Al[slot][mi] = trr(img + X3Q_DYP + abase[j][mi]);
-            }
-        };
-        auto rdB = [&](int n, int slot) {
-            const int j = n / NT, tap = T0 + n % NT;
-            const int to = (tap / 3) * A_HW * 64;
-            Bh[slot] = trr(img + xbase[j][tap % 3] + to);
-            Bl[slot] = trr(img + X3Q_XP + xbase[j][tap % 3] + to);
-        };
-        rdA(0, 0);
-        rdB(0, 0);
-        rdB(1, 1);
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-            if (n + 2 < N) {
-                rdB(n + 2, (n + 2) % 3);
-                if ((n + 2) % NT == 0) rdA((n + 2) / NT, ((n + 2) / NT) & 1);
-            }
-            const int j = n / NT, t = n % NT;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                acc[mi][t] = mfma_x3(Ah[j & 1][mi], Al[j & 1][mi], Bh[n % 3], Bl[n % 3], acc[mi][t]);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-            if (n + 2 < N) {
-                if ((n + 2) % NT == 0) __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
-                else __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-            }
-        }
-    };
-
-    // a contiguous range of units per K share (the six parts of a sample back to back: shared halo rows
-    // and dY window rows come from L2)
-    const int per = (U + nks - 1) / nks;
-    const int u0 = min(ks * per, U), u1 = min(u0 + per, U);
-    int u = u0;
-    if (u < u1) {
-        x3q_issue_img(act16, u, wave, lane, lds_u32(smem));
-        if (dstage) {
-            load_dy(u);
-            store_dy(smem, true);
-            load_dy(min(u + 1, u1 - 1));
-        }
-    }
-    int k = 0;
-#pragma unroll 1
-    for (; u < u1; ++u, ++k) {
-        // this unit's image DMA landed; the 8 dY loads (every staging wave's last memory instructions,
-        // issued after its DMA) may stay in flight
-        X3Q_TS(k, 6);
-        if (!dstage) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        __syncthreads();  // buffer k&1 complete; buffer (k+1)&1 free
-        X3Q_TS(k, 0);
-        const int nx = u + 1, nx2 = u + 2;
-        const char* img = smem + (k & 1) * X3Q_BUF;
-        char* nimg = smem + ((k & 1) ^ 1) * X3Q_BUF;
-        // tap-group-1 waves (the lighter MFMA share) route dY before their MFMAs, tap-group-0 after:
-        // the two waves of a SIMD overlap routing with MFMAs; store_dy before the DMA issue (hipcc does
-        // not count the asm DMAs: its wait for the dY registers would also wait for them)
-        const bool dfirst = tg == 1;
-        if (dfirst && dstage) store_dy(nimg, nx < u1);
-        x3q_issue_img(act16, min(nx, u1 - 1), wave, lane, lds_u32(nimg));
-        if (dfirst && dstage) load_dy(min(nx2, u1 - 1));
-        X3Q_TS(k, 1);
-        if (tg == 0) unit_mfma(img, std::integral_constant<int, 0>{});
-        else unit_mfma(img, std::integral_constant<int, 1>{});
-        X3Q_TS(k, 2);
-        if (!dfirst && dstage) {
-            store_dy(nimg, nx < u1);
-            load_dy(min(nx2, u1 - 1));
-        }
-        X3Q_TS(k, 3);
-    }
-    X3Q_TS(127, 7);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (clamped) image DMA lands before LDS reuse
-    __syncthreads();
-    // db partials of the staging items -> LDS; co = 32 dc + 4 dg + j summed over the 24 windows in order
-    float* dbs = reinterpret_cast<float*>(smem);
-    if (dstage)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dbs[tid * 4 + j] = dbacc[j];
-    __syncthreads();
-    float* slab = slabs + (size_t)ks * (W2_N + C2);
-    if (tid < C2) {
-        const int cc = tid >> 5, g = (tid >> 2) & 7, j = tid & 3;
-        float sum = 0.f;
-        for (int w = 0; w < 24; ++w) sum += dbs[(w * 16 + cc * 8 + g) * 4 + j];
-        slab[W2_N + tid] = sum;
-    }
-    const float us1 = ldexpf(1.f, -sx), us2 = ldexpf(1.f, -sd);
-    const int ci = 16 * h + (lane & 15);
-    const int nt = tg ? 4 : 5, tap0 = 5 * tg;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-        for (int t = 0; t < X3Q_NTMAX; ++t)
-            if (t < nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = 32 * c + 16 * mi + 4 * (lane >> 4) + r;
-                    slab[(co * C1 + ci) * 9 + tap0 + t] = x3_unscale(acc[mi][t][r], us1, us2);
-                }
-    }
-}
-
 // ============================================================================ conv2 wgrad on the 2:4-sparse f16 MFMA
 // Round 6. dY is the max-pool routing of dpooled: in each 2 x 2 pool window at most ONE position carries a
 // value. Take the GEMM's K (output pixels) in blocks of 4 consecutive pixels of one output row starting at a
@@ -1968,16 +1584,7 @@ __global__ __launch_bounds__(X3Q_THREADS, 1) void conv2_wgrad_x3q_kernel(
 // register image of a lane's A fragment: one conflict-free ds_read_b128 per (M tile, plane) per K-step.
 // Waves: 4 M tiles (all 64 co) per wave, so every B fragment feeds 12 MFMAs; (ci half, tap group) items:
 // waves 0/1 taps 0-2, 4/5 taps 3-4, 2/3 taps 5-6, 6/7 taps 7-8 (ci half = wave & 1): SIMD pairs (w, w + 4)
-// carry 5, 5, 4, 4 taps. Scales, db and the slab format as conv2_wgrad_x3q_kernel.
-#ifndef SLK_X3P_PLAN
-#define SLK_X3P_PLAN 0  // 0: staging before (waves 4-7) / after (0-3) the MFMA steps; 1: in pieces between K-steps
-#endif
-#ifndef SLK_X3P_STG
-#define SLK_X3P_STG 0  // 0: items q = wave and 8 + wave (waves 0-3); 1: only the 4-tap SIMDs' waves (2, 3, 6, 7), 3 each
-#endif
-#ifndef SLK_X3P_ABL
-#define SLK_X3P_ABL 0  // profiling only (wrong results): 1 no in-loop dY staging, 2 no MFMA steps, 4 no in-loop DMA
-#endif
+// carry 5, 5, 4, 4 taps. Scales, db and the slab format as conv2_wgrad_x3_kernel.
 constexpr int X3P_THREADS = 512;
 constexpr int X3P_STEPS = 3;                                   // K64 steps per unit (192 pixels)
 constexpr int X3P_REC = X3P_STEPS * 4 * 64 * 16;               // 12,288 B per compressed dY plane
@@ -1989,27 +1596,20 @@ constexpr int X3P_ITEMS = C2 * 12;                             // (co, window ro
 constexpr int X3P_SBN = (163840 - 2 * X3P_BUF) / 4;            // per-sample scale table entries (11,264)
 static_assert(2 * X3P_BUF <= 163840 && X3P_ITEMS <= 2 * X3P_THREADS && X3P_ITEMS > X3P_THREADS, "x3p layout");
 
-#ifndef SLK_X3P_BAL
-#define SLK_X3P_BAL 0  // measured: 0.1677 vs 0.1648 ms unbalanced (profiles/r06_ab_wgrad_balance.txt): not the limiter
-#endif
 // Work of the four wave types (TGI = 2 ((wave >> 1) & 1) + (wave >> 2); ci half = wave & 1): (tap, M tiles) items,
 // 4 M tiles = all 64 co. Waves w and w + 4 share a SIMD, so SIMDs 0-1 carry TGI 0 + 1 and SIMDs 2-3 TGI 2 + 3.
-// Taps 0-2 | 3-4 | 5-6 | 7-8 gave them 5 and 4 taps (20 vs 16 (tap, M tile) items: the lighter SIMDs waited
-// at every unit barrier); BAL moves tap 2's M tiles 2-3 from TGI 0 to TGI 2: 18 items per SIMD.
+// Taps 0-2 | 3-4 | 5-6 | 7-8 give them 5 and 4 taps (20 vs 16 (tap, M tile) items). Moving tap 2's M tiles 2-3
+// from TGI 0 to TGI 2 (18 items per SIMD) measured 0.1677 vs 0.1648 ms unbalanced
+// (profiles/r06_ab_wgrad_balance.txt): the balance is not the limiter.
 template <int TGI>
 struct X3pTaps {
-    static constexpr bool BAL = SLK_X3P_BAL;
-    static constexpr int NT = (TGI == 0 || (TGI == 2 && BAL)) ? 3 : 2;
-    static constexpr int tap(int t) {
-        return TGI == 0 ? t : (TGI == 1 ? 3 + t : (TGI == 2 ? (t < 2 ? 5 + t : 2) : 7 + t));
-    }
-    static constexpr int mlo(int t) { return (TGI == 2 && t == 2) ? 2 : 0; }
-    static constexpr int mhi(int t) { return (TGI == 0 && t == 2 && BAL) ? 2 : 4; }
+    static constexpr int NT = TGI == 0 ? 3 : 2;
+    static constexpr int tap(int t) { return TGI == 0 ? t : (TGI == 1 ? 3 + t : (TGI == 2 ? 5 + t : 7 + t)); }
 };
 
-template <int TGI, class F>
+template <int TGI>
 __device__ __forceinline__ void x3p_steps(const char* img, const int (&pb)[X3P_STEPS][4], const int (&sw)[3], int arec,
-                                          int aidx, f32x4 (&acc)[3][4], F&& after_step) {
+                                          int aidx, f32x4 (&acc)[3][4]) {
     using TT = X3pTaps<TGI>;
     constexpr int NT = TT::NT;
     typedef __fp16 hf4 __attribute__((__vector_size__(8)));
@@ -2044,7 +1644,7 @@ __device__ __forceinline__ void x3p_steps(const char* img, const int (&pb)[X3P_S
                                                       __builtin_shufflevector(bl[2], bl[3], 0, 1, 2, 3, 4, 5, 6, 7),
                                                       0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
 #pragma unroll
-            for (int mt = TT::mlo(t); mt < TT::mhi(t); ++mt) {
+            for (int mt = 0; mt < 4; ++mt) {
                 f32x4 c = acc[t][mt];
                 c = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ah[mt], Bh, c, ix[mt], 0, 0);
                 c = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ah[mt], Bl, c, ix[mt], 0, 0);
@@ -2052,7 +1652,6 @@ __device__ __forceinline__ void x3p_steps(const char* img, const int (&pb)[X3P_S
                 acc[t][mt] = c;
             }
         }
-        after_step(s);
     }
 }
 
@@ -2069,13 +1668,13 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     const int ks = blockIdx.x, nks = gridDim.x;
     const int U = 3 * B;
     float* red = reinterpret_cast<float*>(smem);
-    X3Q_TS(0, 7);
+    X3P_TS(0, 7);
 
-    // launch scales: max over the batch of the per-sample maxima (as conv2_wgrad_x3q_kernel)
+    // launch scales: max over the batch of the per-sample maxima (as conv2_wgrad_x3_kernel)
     float ma = 0.f, md = 0.f;
     for (int i = tid; i < B; i += X3P_THREADS) {
-        ma = fmaxf(ma, x3_head_ld<4>(act_amax, i));
-        md = fmaxf(md, x3_head_ld<4>(dp_amax, i));
+        ma = fmaxf(ma, act_amax[i]);
+        md = fmaxf(md, dp_amax[i]);
     }
     ma = wave_max(ma);
     md = wave_max(md);
@@ -2098,24 +1697,13 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     // writes 16 consecutive 16-B records: 2-way banks instead of the 6-12-way of 12 items of one co), q = wave
     // and, for waves 0-3, 8 + wave. Per item the global offset within the unit and the two LDS destinations
     // (one per output row of the window row) do not depend on the unit: computed once.
-#if SLK_X3P_STG == 0
+    // (tried: 3 items each on the 4-tap SIMDs' waves 2, 3, 6, 7 only)
     constexpr int NI = 2;
-    const bool two = wave < 4;
-    const int nit = two ? 2 : 1;
-#else
-    constexpr int NI = 3;
-    const bool two = false;
-    const int sidx = (wave & 1) + 2 * (wave >> 2);           // waves 2, 3, 6, 7 -> 0, 1, 2, 3
-    const int nit = (wave & 2) ? 3 : 0;
-#endif
+    const int nit = wave < 4 ? 2 : 1;
     int goff[NI], ldo[NI][2];
 #pragma unroll
     for (int r = 0; r < NI; ++r) {
-#if SLK_X3P_STG == 0
         const int q = r == 0 ? wave : 8 + (wave & 3);
-#else
-        const int q = 3 * sidx + r;
-#endif
         const int wyl = q / 3, wq = q - (q / 3) * 3;
         goff[r] = lane * P_WIN + wyl * P_HW + 4 * wq;
 #pragma unroll
@@ -2152,7 +1740,7 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
 #if SLK_X3D_TRACE
                 if (r == 0) {
                     asm volatile("" ::"v"(v[0]), "v"(dcw[0]));
-                    X3Q_TS(trk, 4);
+                    X3P_TS(trk, 4);
                 }
 #endif
                 const uint32_t cw = dcw[r];
@@ -2193,7 +1781,7 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
 #pragma unroll
         for (int r = 0; r < NI; ++r)
             if (r < nit) store_dy1(img, real, r);
-        X3Q_TS(trk, 5);
+        X3P_TS(trk, 5);
     };
 
     // B (tr-read) lane bases: lane (gb, qq, pp) of block (s, jb) -> pixel (y, 4 xb + qq), channels 4 pp.. of
@@ -2221,7 +1809,7 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     const int u0 = min(ks * per, U), u1 = min(u0 + per, U);
     sb0 = u0 / 3;
     const int nsb = u1 > u0 ? (u1 - 1) / 3 - sb0 + 1 : 0;
-    for (int j = tid; j < nsb; j += X3P_THREADS) sbt[j] = sd + sx - max(x3_exp(x3_head_ld<4>(act_amax, sb0 + j)), sx);
+    for (int j = tid; j < nsb; j += X3P_THREADS) sbt[j] = sd + sx - max(x3_exp(act_amax[sb0 + j]), sx);
     __syncthreads();
     int u = u0;
     if (u < u1) {
@@ -2235,77 +1823,42 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
     for (; u < u1; ++u, ++k) {
         // this unit's image DMA landed; the dY loads (every wave's last memory instructions, issued after its
         // DMA pieces) may stay in flight
-        X3Q_TS(k, 6);
-        if ((SLK_X3P_ABL & 1) || nit == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (nit == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (nit == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        X3P_TS(k, 6);
+        if (nit == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         __syncthreads();  // buffer k&1 complete; buffer (k+1)&1 free
-        X3Q_TS(k, 0);
+        X3P_TS(k, 0);
         trk = k;
         const int nx = u + 1, nx2 = u + 2;
         const char* img = smem + (k & 1) * X3P_BUF;
         char* nimg = smem + ((k & 1) ^ 1) * X3P_BUF;
         // half the waves route dY before their MFMAs, half after (the two waves of a SIMD overlap routing with
         // MFMAs); store_dy before the DMA issue (hipcc does not count the asm DMAs)
-#if SLK_X3P_PLAN == 0
-        const bool dfirst = wave >= 4 && !(SLK_X3P_ABL & 1);
+        // (tried: the next unit's image pieces and dY routing in pieces between this unit's K-steps)
+        const bool dfirst = wave >= 4;
         if (dfirst) store_dy(nimg, nx < u1);
-        if (!(SLK_X3P_ABL & 4)) x3_issue_unit_img(act16, min(nx, u1 - 1), wave, lane, lds_u32(nimg));
+        x3_issue_unit_img(act16, min(nx, u1 - 1), wave, lane, lds_u32(nimg));
         if (dfirst) load_dy(min(nx2, u1 - 1));
-        auto hook = [&](int) {};
-        X3Q_TS(k, 1);
-#else
-        // plan 1: the next unit's image pieces and dY routing in pieces between this unit's K-steps; the dY
-        // loads last (after every DMA piece: the counted vmcnt at the top)
-        const char* srch = x3_unit_img_src(act16, min(nx, u1 - 1));
-        const uint32_t nl = lds_u32(nimg);
-        auto hook = [&](int st) {
-            if (st == 0) {
-                if (!(SLK_X3P_ABL & 4)) {
-                    x3_issue_img_full(srch, wave, lane, nl, 0);
-                    x3_issue_img_full(srch, wave, lane, nl, 1);
-                }
-                if (!(SLK_X3P_ABL & 1)) store_dy1(nimg, nx < u1, 0);
-            } else if (st == 1) {
-                if (!(SLK_X3P_ABL & 4)) {
-                    x3_issue_img_full(srch, wave, lane, nl, 2);
-                    x3_issue_img_full(srch, wave, lane, nl, 3);
-                    if (wave < 2) x3_issue_img_quarter(srch, wave, lane, nl);
-                }
-                if (!(SLK_X3P_ABL & 1) && two) store_dy1(nimg, nx < u1, 1);
-            } else {
-                if (!(SLK_X3P_ABL & 1)) load_dy(min(nx2, u1 - 1));
-            }
-        };
-#endif
-        if (!(SLK_X3P_ABL & 2)) {
-            if (tgi == 0) x3p_steps<0>(img, pb, sw, arec, aidx, acc, hook);
-            else if (tgi == 1) x3p_steps<1>(img, pb, sw, arec, aidx, acc, hook);
-            else if (tgi == 2) x3p_steps<2>(img, pb, sw, arec, aidx, acc, hook);
-            else x3p_steps<3>(img, pb, sw, arec, aidx, acc, hook);
-        } else {
-            hook(0);
-            hook(1);
-            hook(2);
-        }
-        X3Q_TS(k, 2);
-#if SLK_X3P_PLAN == 0
-        if (!dfirst && !(SLK_X3P_ABL & 1)) {
+        X3P_TS(k, 1);
+        if (tgi == 0) x3p_steps<0>(img, pb, sw, arec, aidx, acc);
+        else if (tgi == 1) x3p_steps<1>(img, pb, sw, arec, aidx, acc);
+        else if (tgi == 2) x3p_steps<2>(img, pb, sw, arec, aidx, acc);
+        else x3p_steps<3>(img, pb, sw, arec, aidx, acc);
+        X3P_TS(k, 2);
+        if (!dfirst) {
             store_dy(nimg, nx < u1);
             load_dy(min(nx2, u1 - 1));
         }
-#endif
-        X3Q_TS(k, 3);
+        X3P_TS(k, 3);
     }
-    X3Q_TS(127, 7);
+    X3P_TS(127, 7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (clamped) image DMA lands before LDS reuse
     __syncthreads();
     // db partials per item -> LDS; co's 12 items summed in order
     float* dbs = reinterpret_cast<float*>(smem);  // [item = 64 q + co]
 #pragma unroll
     for (int r = 0; r < NI; ++r)
-        if (r < nit) dbs[(SLK_X3P_STG == 0 ? (r == 0 ? wave : 8 + (wave & 3)) : 3 * ((wave & 1) + 2 * (wave >> 2)) + r) * 64 + lane] = dbacc[r];
+        if (r < nit) dbs[(r == 0 ? wave : 8 + (wave & 3)) * 64 + lane] = dbacc[r];
     __syncthreads();
     float* slab = slabs + (size_t)ks * (W2_N + C2);
     if (tid < C2) {
@@ -2320,7 +1873,7 @@ __global__ __launch_bounds__(X3P_THREADS, 1) void conv2_wgrad_x3p_kernel(
 #pragma unroll
         for (int t = 0; t < TT::NT; ++t)
 #pragma unroll
-            for (int mt = TT::mlo(t); mt < TT::mhi(t); ++mt)
+            for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int co = 16 * mt + 4 * (lane >> 4) + r;
@@ -2673,52 +2226,52 @@ extern "C" int slk_conv2_dgrad_x3_c1w(const float* dpooled, const float* dp_amax
     return slk_launch_status();
 }
 
-// round 5: the slab count of both x3 wgrad entries is the images kernel's (conv2_wgrad_x3q/x3p: 6 units a
-// sample, up to X3Q_NKS shares). The f32-act kernel (3 units a sample) keeps its own share count min(3B,
-// X3W_NKS) x 2 co halves (round 6, ADVICE r5: with the images kernel's count over half its shares were empty
-// below B = 86 and it launched 512 one-per-CU workgroups); the slabs past its shares are zeroed.
-extern "C" int slk_conv2_wgrad_x3_nslab(int B) { return B <= 0 ? 0 : (6 * B < X3Q_NKS ? 6 * B : X3Q_NKS); }
+// The slab count of both x3 wgrad entries: the images kernel's K shares (one workgroup per CU; a removed form
+// with 6 units a sample set the 6 B below it). The f32-act kernel (3 units a sample) keeps its own share count
+// min(3B, X3W_NKS) x 2 co halves (round 6, ADVICE r5: with the images kernel's count over half its shares were
+// empty below B = 86 and it launched 512 one-per-CU workgroups); the slabs past its shares are zeroed.
+constexpr int X3_WGRAD_NSLAB = 256;
+extern "C" int slk_conv2_wgrad_x3_nslab(int B) { return B <= 0 ? 0 : (6 * B < X3_WGRAD_NSLAB ? 6 * B : X3_WGRAD_NSLAB); }
 
 extern "C" int slk_conv2_wgrad_x3(const float* act, const float* act_amax, const float* dpooled, const float* dp_amax,
                                   const uint8_t* code, float* slabs, int B, void* stream) {
     SLK_CHECK_ARG(B >= 0 && act && act_amax && dpooled && dp_amax && code && slabs);
     if (B == 0) return 0;
     const int nslab = slk_conv2_wgrad_x3_nslab(B);
-#ifndef SLK_X3W_F32NKS
-#define SLK_X3W_F32NKS 1  // 0: the round-5 launch (nslab shares), kept for the A/B
-#endif
-    const int nks = SLK_X3W_F32NKS ? (3 * B < X3W_NKS ? 3 * B : X3W_NKS) : nslab;  // one slab per K share
+    const int nks = 3 * B < X3W_NKS ? 3 * B : X3W_NKS;  // one slab per K share
     if (nks < nslab) {
         const hipError_t e = hipMemsetAsync(slabs + (size_t)nks * (W2_N + C2), 0,
                                             sizeof(float) * (size_t)(nslab - nks) * (W2_N + C2), slk_stream(stream));
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(conv2_wgrad_x3_kernel<false>, dim3(2 * nks), dim3(X3W_THREADS), 0, slk_stream(stream), act,
-                       act_amax, dpooled, dp_amax, code, slabs, B, nullptr);
+    hipLaunchKernelGGL(conv2_wgrad_x3_kernel, dim3(2 * nks), dim3(X3W_THREADS), 0, slk_stream(stream), act, act_amax,
+                       dpooled, dp_amax, code, slabs, B);
     return slk_launch_status();
 }
 
-extern "C" int slk_conv2_wgrad_x3_form() { return SLK_X3W_ROUND4 ? 0 : (SLK_X3W_SPARSE ? 2 : 1); }
+// 2: the 2:4-sparse MFMA form (conv2_wgrad_x3p_kernel), the only one built (0 and 1 were the removed dense forms)
+extern "C" int slk_conv2_wgrad_x3_form() { return 2; }
+
+// A K share of conv2_wgrad_x3p_kernel keeps its samples' dY scales in an LDS table of X3P_SBN entries: a share of
+// ceil(3B / nslab) units touches at most that / 3 + 2 samples.
+constexpr bool x3p_batch_fits(int64_t B) {
+    const int64_t nks = 6 * B < X3_WGRAD_NSLAB ? 6 * B : X3_WGRAD_NSLAB;
+    return B <= 0 || ((3 * B + nks - 1) / nks) / 3 + 2 <= X3P_SBN;
+}
+// The first batch refused, and why no such batch exists: its act16 images and pooled gradient alone (249 + 106 GB)
+// exceed the MI355X's 288 GB of HBM.
+constexpr int64_t X3P_B_REFUSED = 2883243;
+static_assert(x3p_batch_fits(X3P_B_REFUSED - 1) && !x3p_batch_fits(X3P_B_REFUSED), "first batch past the scale table");
+static_assert(X3P_B_REFUSED * X3S_SAMPLE + X3P_B_REFUSED * P_SAMPLE * 4 > 288LL * 1000 * 1000 * 1000,
+              "the refused batches do not fit the device");
 
 extern "C" int slk_conv2_wgrad_x3s(const uint16_t* act16, const float* act_amax, const float* dpooled,
                                    const float* dp_amax, const uint8_t* code, float* slabs, int B, void* stream) {
     SLK_CHECK_ARG(B >= 0 && act16 && act_amax && dpooled && dp_amax && code && slabs);
+    SLK_CHECK_ARG(x3p_batch_fits(B));
     if (B == 0) return 0;
     const int nks = slk_conv2_wgrad_x3_nslab(B);
-#if SLK_X3W_ROUND4  // profiling A/B: the round-4 kernel (one co half per workgroup, 8-row units)
-    hipLaunchKernelGGL(conv2_wgrad_x3_kernel<true>, dim3(2 * nks), dim3(X3W_THREADS), 0, slk_stream(stream), nullptr,
-                       act_amax, dpooled, dp_amax, code, slabs, B, act16);
-#elif SLK_X3W_SPARSE  // round 6: the 2:4-sparse MFMA form (conv2_wgrad_x3p_kernel)
-    if (((3 * B + nks - 1) / nks) / 3 + 2 > X3P_SBN) {  // a K share's samples exceed the LDS scale table
-        hipLaunchKernelGGL(conv2_wgrad_x3q_kernel, dim3(nks), dim3(X3Q_THREADS), 0, slk_stream(stream), act16, act_amax,
-                           dpooled, dp_amax, code, slabs, B);
-        return slk_launch_status();
-    }
     hipLaunchKernelGGL(conv2_wgrad_x3p_kernel, dim3(nks), dim3(X3P_THREADS), 0, slk_stream(stream), act16, act_amax,
                        dpooled, dp_amax, code, slabs, B);
-#else
-    hipLaunchKernelGGL(conv2_wgrad_x3q_kernel, dim3(nks), dim3(X3Q_THREADS), 0, slk_stream(stream), act16, act_amax,
-                       dpooled, dp_amax, code, slabs, B);
-#endif
     return slk_launch_status();
 }

@@ -2,11 +2,11 @@
 build with -DSLK_X3D_TRACE=1 (tools/build_variant.sh x3dtrace "-DSLK_X3D_TRACE=1"): per (workgroup, wave,
 unit) shader-clock stamps at the unit barrier, around the staging and the MFMA loops and after the
 conv1-gradient epilogue. Prints the mean cycles per phase per wave slot.
---kernel wgrad: the same for conv2_wgrad_x3q_kernel (stamps at the unit barrier, after the first-half
-waves' dY routing + image DMA issue, after the MFMAs, after the second-half waves' routing).
+--kernel wgradp: the same for conv2_wgrad_x3p_kernel (stamps at the unit barrier, after the first-half
+waves' dY routing + image DMA issue, after the MFMAs, after the second-half waves' routing, and inside the staging).
 --kernel fwd: conv2_fwd_pool_x3_kernel<IN16> (slk_conv2_fwd_pool_x3i): launch start, weights in registers,
 every unit's barrier, end of the last unit — the head (start to the first unit barrier) against a unit.
-usage: python tools/x3d_trace.py build_abl/x3dtrace.so [--B 4096] [--kernel dgrad|wgrad|wgradp|fwd]"""
+usage: python tools/x3d_trace.py build_abl/x3dtrace.so [--B 4096] [--kernel dgrad|wgradp|fwd]"""
 import argparse
 import ctypes
 import os
@@ -25,7 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib")
     ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--kernel", default="dgrad", choices=["dgrad", "wgrad", "wgradp", "fwd"])
+    ap.add_argument("--kernel", default="dgrad", choices=["dgrad", "wgradp", "fwd"])
     args = ap.parse_args()
     from splitcnn import ops
     from splitcnn.data import SyntheticMNIST, init_models
@@ -59,7 +59,7 @@ def main():
     L.slk_conv2_dgrad_x3_c1w.argtypes = [P] * 7 + [ctypes.c_int, P]
     sl = torch.empty(L.slk_conv2_dgrad_x3_c1w_nslab(B), 320, device=dev)
     run = lambda: L.slk_conv2_dgrad_x3_c1w(p(dp), p(dpa), p(code), p(W2), p(xg), p(bits), p(sl), B, st)  # noqa: E731
-    if args.kernel in ("wgrad", "wgradp"):
+    if args.kernel == "wgradp":
         L.slk_conv2_wgrad_x3_nslab.restype = ctypes.c_int
         L.slk_conv2_wgrad_x3s.restype = ctypes.c_int
         L.slk_conv2_wgrad_x3s.argtypes = [P] * 6 + [ctypes.c_int, P]
@@ -80,7 +80,7 @@ def main():
         ms.append(e0.elapsed_time(e1))
     ms = sorted(ms[2:])
     buf = np.zeros(256 * 8 * NU * NS, dtype=np.uint64)
-    rd = {"dgrad": "slk_x3d_trace_read", "fwd": "slk_x3f_trace_read"}.get(args.kernel, "slk_x3q_trace_read")
+    rd = {"dgrad": "slk_x3d_trace_read", "fwd": "slk_x3f_trace_read"}.get(args.kernel, "slk_x3p_trace_read")
     rd = getattr(L, rd)
     assert rd(ctypes.c_void_p(buf.ctypes.data)) == 0
     T = buf.reshape(256, 8, NU, NS).astype(np.int64)
@@ -91,9 +91,6 @@ def main():
     G = 256
     if args.kernel == "fwd":
         fwd_report(T, min((3 * B + G - 1) // G, NU - 1))
-        return
-    if args.kernel == "wgrad":
-        wgrad_report(T, (6 * B + G - 1) // G)
         return
     if args.kernel == "wgradp":  # the sparse wgrad: 3 units per sample, nslab = min(6 B, 256) K shares
         per = (3 * B + G - 1) // G
@@ -177,7 +174,7 @@ def wgrad_report(T, nu):
         print("staging: cycles from its start to its data (the loads' wait) and then to its last store, by wave")
         for w in range(8):
             print(f"{w:>4} wait {dwait[:, w].mean():8.0f}  stores {sto[:, w].mean():8.0f}")
-    print("wave = 4 tg + 2 c + h; tg 1 (waves 4-7) route before their MFMAs; waves 6-7 route nothing")
+    print("waves 4-7 route before their MFMAs, waves 0-3 after")
     print(f"{'wave':>4} {'barrier':>8} {'route<':>8} {'mfma':>8} {'route>':>8} {'gap':>6} {'unit':>8}")
     for w in range(8):
         print(f"{w:>4} {bar[:, w].mean():8.0f} {pre[:, w].mean():8.0f} {mf[:, w].mean():8.0f} {post[:, w].mean():8.0f} "
