@@ -493,11 +493,49 @@ int slk_image_batch(const uint8_t* images, const uint8_t* labels, int n_images, 
  * slk_image_batch's x and plain labels; idx2 = idx gives its x and labels with a == b. prob outside [0, 1] or NaN
  * returns the invalid-argument status, as do slk_image_batch's own bad arguments and a null idx2. An idx2 outside
  * [0, n_images) behaves like an idx outside it (flag, then row 0 with row 0's draws). No byte outside the dataset
- * is ever addressed, for either source. Other Beta parameters and MixUp (a float blend) are not provided. */
+ * is ever addressed, for either source. Other Beta parameters and MixUp (a float blend) are slk_image_batch_blend's,
+ * below; this entry keeps its bits. */
 int slk_image_batch_mix(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
                         const int64_t* idx, const int64_t* idx2, int B, const float* mean, const float* std, int pad,
                         int flip_enabled, uint32_t seed, uint32_t epoch, double prob, float* x, int64_t* y,
                         int* err_flag, void* stream);
+
+/* slk_image_batch_mix with lam ~ Beta(alpha, alpha) from a quantile table, and MixUp (Zhang et al. 2018), chosen per
+ * sample, one launch, the same two shapes. The arguments are slk_image_batch_mix's, plus two DEVICE tables of 1024
+ * entries each, either of which may be NULL (not both), and switch_prob:
+ *   cut_table[k] = min(floor(sqrt(1 - q_k) * 2^32), 2^32 - 1)     the box side ratio of CutMix, as a 32-bit fraction
+ *   lam_table[k] = (float)q_k                                      the partner's weight of MixUp
+ * with q_k the quantile of Beta(alpha, alpha) at (k + 0.5) / 1024 (splitcnn.loss.beta_quantiles builds them; each
+ * table may have its own alpha). Primary i = idx[s] and partner i2 = idx2[s] get their own crop and flip draws
+ * h0..h2 exactly as in slk_image_batch. The primary's chain is continued, h3..h7 = lowbias32(previous + 0x9E3779B9):
+ *   apply = (uint64)h3 < (uint64)(prob * 4294967296.0)             (the samples slk_image_batch_mix would pick)
+ *   cut   = both tables given ? (uint64)h4 < (uint64)(switch_prob * 4294967296.0) : (cut_table != NULL)
+ *   k     = h5 >> 22                                               (table index, 0..1023)
+ *   cy    = (h6 * H) >> 32;  cx = (h7 * W) >> 32                   (as in slk_image_batch_mix)
+ * CutMix sample (apply && cut): side = ((uint64)cut_table[k] * H) >> 32; from side / 2 on, the box, the selection on
+ * the u8 pixels, wb = area / (H * W) and the label are slk_image_batch_mix's.
+ * MixUp sample (apply && !cut): wb = lam_table[k]. For every output pixel, pa and pb are the u8 pixels samples i and
+ * i2 would show there, each under its own crop and flip (padding is 0 in pixel space). In float32, every operation
+ * rounded on its own:
+ *   fa = (float)pa / 255.0f;  fb = (float)pb / 255.0f;  om = 1.0f - wb
+ *   f  = fadd_rn(fmul_rn(om, fa), fmul_rn(wb, fb))                 (two products and a sum, NOT an fma)
+ *   x  = (f - mean[c]) / std[c]
+ * and y[s] = wb > 0 ? labels[i] | labels[i2] << 8 | (int64)float_bits(wb) << 32 : labels[i]. wb = 0 (or a denormal)
+ * gives bit for bit sample i's plain image, wb = 1 sample i2's. The blend is made BEFORE Normalize, on the ToTensor
+ * values, and is neither fa + wb (fb - fa) nor a contracted form: those round differently.
+ * Unapplied sample: slk_image_batch's bits and the plain label. prob = 0 is bitwise slk_image_batch. With only
+ * cut_table given, a sample's apply, cy, cx equal slk_image_batch_mix's at the same (index, epoch, seed, prob).
+ * One lam per SAMPLE out of 1024 values (timm's mode="elem" on a quantile table), not one per batch.
+ * Both tables NULL, a misaligned table, prob or switch_prob outside [0, 1] or NaN, and every bad argument of
+ * slk_image_batch_mix return the invalid-argument status without a launch; B == 0 returns 0. An idx / idx2 outside
+ * [0, n_images) sets the flag and reads row 0 with row 0's draws. No byte outside the dataset is ever addressed, for
+ * either source. The tables are only read and their values are not validated: a lam_table entry outside [0, 1]
+ * reaches the soft heads' target check like any malformed label. */
+int slk_image_batch_blend(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                          const int64_t* idx, const int64_t* idx2, int B, const float* mean, const float* std, int pad,
+                          int flip_enabled, uint32_t seed, uint32_t epoch, double prob, const uint32_t* cut_table,
+                          const float* lam_table, double switch_prob, float* x, int64_t* y, int* err_flag,
+                          void* stream);
 
 
 /* ================================================================ lossless cut-exchange codec (K3 / K4)

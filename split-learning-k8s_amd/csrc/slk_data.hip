@@ -1,6 +1,7 @@
 // slk_data.hip — the batch loaders as one HBM-resident gather each: slk_mnist_batch (K2) and
 // slk_image_batch (K5's CIFAR-10 path with crop + flip augmentation, and MNIST with a crop), plus
-// slk_image_batch_mix, the same gather with CutMix and mixed labels.
+// slk_image_batch_mix, the same gather with CutMix and mixed labels, and slk_image_batch_blend, which draws the box
+// side or a MixUp weight from a Beta(alpha, alpha) quantile table per sample.
 //
 // The reference builds batches with DataLoader(train_dataset, batch_size=64, shuffle=True)
 // (client_part.py:98) over torchvision MNIST with ToTensor() + Normalize((0.1307,), (0.3081,))
@@ -380,4 +381,196 @@ extern "C" int slk_image_batch_mix(const uint8_t* images, const uint8_t* labels,
     return image_batch_mix_launch<1, 28, 28, SLK_IMAGE_QUADS_MNIST>(images, labels, n_images, idx, idx2, B, nrm, pad,
                                                                   flip_enabled, seed, epoch, apply_below, x, y, err_flag,
                                                                   stream);
+}
+
+// -------------------------------------------------------------------------------- slk_image_batch_blend
+// slk_image_batch_mix with the mixing weight drawn from a 1024-entry quantile table of Beta(alpha, alpha) instead of
+// the two-uniforms trick, and with MixUp (Zhang et al. 2018) as a second mode, chosen per sample (slk.h has the rule).
+// The primary's chain h3..h7 is read as apply (h3, as in the mix kernel), the mode (h4), the table index k = h5 >> 22
+// and the box centre (h6, h7, as in the mix kernel). The host folds "only one table given" into the mode threshold
+// (0: never CutMix, 2^32: always), so the table a sample's mode names is never NULL.
+//
+//   CutMix sample: side = (cut_table[k] * H) >> 32, then the mix kernel's box, masks and loads word for word.
+//   MixUp sample:  both sources are loaded for every quad; each goes through quad_bytes on its own, and the blend is
+//                  made in float32 on the two ToTensor values, every operation rounded on its own (blend_rn:
+//                  hipcc would contract a*b + c into an fma, which rounds once and differs).
+//   unapplied:     only source i is loaded (an empty box).
+//
+// The mode is uniform over a sample: whole waves at <3,32,32,4> (192 threads per sample), so neither branch below
+// diverges there; a <1,28,28,1> wave can hold the end of one sample and the start of the next, and the two branches
+// are kept to one table read and the partner's blend arithmetic. The table reads sit INSIDE their branches, one dword
+// per thread at one address per sample: a CutMix sample needs its side before it knows which loads to issue, so its
+// read is in front of them (one more L2 round trip in that sample's chain idx -> hash -> table -> pixels); a MixUp
+// sample's read is issued after all its pixel loads, and an unapplied sample reads no table.
+namespace {
+// om * fa + lam * fb as two rounded products and one rounded sum. HIP's __fmul_rn / __fadd_rn are plain '*' and '+',
+// which hipcc's default -ffp-contract=fast fuses into an fma like any other; the pragma takes the contract flag off
+// these three operations, and it stays off when the function is inlined.
+__device__ __forceinline__ float blend_rn(float om, float fa, float lam, float fb) {
+#pragma clang fp contract(off)
+    const float pa = om * fa, pb = lam * fb;
+    return pa + pb;
+}
+}  // namespace
+
+template <int C, int H, int W, int U>
+__global__ __launch_bounds__(256) void image_batch_blend_kernel(const uint32_t* __restrict__ words,
+                                                                const uint8_t* __restrict__ labels, int n_images,
+                                                                const int64_t* __restrict__ idx,
+                                                                const int64_t* __restrict__ idx2, int B, ImageNorm nrm,
+                                                                int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                                                                uint64_t apply_below, uint64_t cut_below,
+                                                                const uint32_t* __restrict__ cut_table,
+                                                                const float* __restrict__ lam_table,
+                                                                float4* __restrict__ x, int64_t* __restrict__ y,
+                                                                int* __restrict__ err) {
+    static_assert(W % 4 == 0 && (C * H * W) % 4 == 0 && C <= IMAGE_MAX_C, "quads of one row, whole words per image");
+    constexpr int QW = W / 4, QS = C * H * QW, TS = QS / U;
+    static_assert(QS % U == 0, "every thread of a sample makes U quads");
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)B * TS) return;
+    const int s = (int)(t / TS), r0 = (int)(t - (int64_t)s * TS);
+    int64_t i = idx[s], i2 = idx2[s];
+    if (i < 0 || i >= n_images) {        // out-of-range index: flag it, read row 0 (with row 0's draws)
+        if (r0 == 0 && err) *err = 1;
+        i = 0;
+    }
+    if (i2 < 0 || i2 >= n_images) {      // the partner likewise
+        if (r0 == 0 && err) *err = 1;
+        i2 = 0;
+    }
+    // both labels loaded by every thread and stored last by one (see image_batch_kernel)
+    const int64_t la = (int64_t)labels[i], lb = (int64_t)labels[i2];
+
+    const ImageDraws da = image_draws(i, seed, epoch, pad, flip_enabled);
+    const ImageDraws db = image_draws(i2, seed, epoch, pad, flip_enabled);
+    const uint32_t h3 = lowbias32(da.h2 + 0x9E3779B9u), h4 = lowbias32(h3 + 0x9E3779B9u);
+    const uint32_t h5 = lowbias32(h4 + 0x9E3779B9u), h6 = lowbias32(h5 + 0x9E3779B9u);
+    const uint32_t h7 = lowbias32(h6 + 0x9E3779B9u);
+    const bool apply = (uint64_t)h3 < apply_below;
+    const bool cut = apply && (uint64_t)h4 < cut_below, blend = apply && !cut;
+    const uint32_t k = h5 >> 22;         // table index, 0 .. 1023
+    int half = 0;
+    if (cut) half = (int)(((uint64_t)cut_table[k] * H) >> 32) / 2;
+    const int cy = (int)(((uint64_t)h6 * H) >> 32), cx = (int)(((uint64_t)h7 * W) >> 32);
+    const int y1 = min(max(cy - half, 0), H), y2 = cut ? min(max(cy + half, 0), H) : y1;   // no box: empty
+    const int x1 = min(max(cx - half, 0), W), x2 = min(max(cx + half, 0), W);
+    const int area = (y2 - y1) * (x2 - x1);
+    const int64_t last = (int64_t)n_images * (C * H * W / 4) - 1;   // the dataset's last word
+
+    int xa[U], xb[U], sa[U], sb[U];
+    uint32_t loa[U], hia[U], lob[U], hib[U], msk[U];   // msk: bytes of the quad that lie inside the box
+    bool lda[U], ldb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW), yo = (r / QW) % H, q = r % QW;
+        uint32_t m = 0;
+        if (yo >= y1 && yo < y2) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) m |= (4 * q + kk >= x1 && 4 * q + kk < x2) ? 0xffu << (8 * kk) : 0u;
+        }
+        msk[u] = m;
+        const int ysa = yo + da.dy - pad, ysb = yo + db.dy - pad;
+        xa[u] = (da.flip ? W - 4 - 4 * q : 4 * q) + da.dx - pad;
+        xb[u] = (db.flip ? W - 4 - 4 * q : 4 * q) + db.dx - pad;
+        lda[u] = m != 0xffffffffu && (unsigned)ysa < (unsigned)H && xa[u] > -4 && xa[u] < W;
+        ldb[u] = (blend || m != 0u) && (unsigned)ysb < (unsigned)H && xb[u] > -4 && xb[u] < W;
+        loa[u] = hia[u] = lob[u] = hib[u] = 0;
+        sa[u] = sb[u] = 0;
+        if (lda[u]) {
+            const int64_t a = (((int64_t)i * C + c) * H + ysa) * W + xa[u];    // byte address, may be < 0
+            const int64_t wi = a >> 2;
+            sa[u] = (int)(a & 3);
+            loa[u] = words[min(max(wi, (int64_t)0), last)];
+            hia[u] = words[min(max(wi + 1, (int64_t)0), last)];
+        }
+        if (ldb[u]) {
+            const int64_t a = (((int64_t)i2 * C + c) * H + ysb) * W + xb[u];
+            const int64_t wi = a >> 2;
+            sb[u] = (int)(a & 3);
+            lob[u] = words[min(max(wi, (int64_t)0), last)];
+            hib[u] = words[min(max(wi + 1, (int64_t)0), last)];
+        }
+    }
+    float lam = 0.0f;                    // the partner's weight of a MixUp sample; read behind the pixel loads
+    if (blend) lam = lam_table[k];
+    const float om = 1.0f - lam;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = r0 + u * TS;
+        const int c = r / (H * QW);
+        const uint32_t wa = lda[u] ? quad_bytes(loa[u], hia[u], sa[u], xa[u], W, da.flip) : 0u;
+        const uint32_t wb = ldb[u] ? quad_bytes(lob[u], hib[u], sb[u], xb[u], W, db.flip) : 0u;
+        const uint32_t w = blend ? wa : (wa & ~msk[u]) | (wb & msk[u]);
+        const float mean = c == 0 ? nrm.mean[0] : c == 1 ? nrm.mean[1] : nrm.mean[2];
+        const float stdv = c == 0 ? nrm.stdv[0] : c == 1 ? nrm.stdv[1] : nrm.stdv[2];
+        float f[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) f[kk] = (float)((w >> (8 * kk)) & 0xffu) / 255.0f;   // ToTensor
+        if (blend) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const float fb = (float)((wb >> (8 * kk)) & 0xffu) / 255.0f;
+                f[kk] = blend_rn(om, f[kk], lam, fb);
+            }
+        }
+        float v[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) v[kk] = (f[kk] - mean) / stdv;                       // Normalize
+        x[(int64_t)s * QS + r] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    if (r0 == 0) {
+        const float wgt = cut ? (float)area / (float)(H * W) : lam;       // IEEE division; 0 for an empty box
+        const bool mixed = cut ? area > 0 : lam > 0.0f;                   // lam is 0 unless blend
+        y[s] = mixed ? (int64_t)((uint64_t)la | ((uint64_t)lb << 8) | ((uint64_t)__float_as_uint(wgt) << 32)) : la;
+    }
+}
+
+template <int C, int H, int W, int U>
+static int image_batch_blend_launch(const uint8_t* images, const uint8_t* labels, int n_images, const int64_t* idx,
+                                    const int64_t* idx2, int B, const ImageNorm& nrm, int pad, int flip_enabled,
+                                    uint32_t seed, uint32_t epoch, uint64_t apply_below, uint64_t cut_below,
+                                    const uint32_t* cut_table, const float* lam_table, float* x, int64_t* y,
+                                    int* err_flag, void* stream) {
+    const int64_t total = (int64_t)B * (C * H * (W / 4) / U);
+    SLK_CHECK_ARG((total + 255) / 256 <= 0x7fffffff);
+    image_batch_blend_kernel<C, H, W, U><<<(unsigned)((total + 255) / 256), 256, 0, slk_stream(stream)>>>(
+        reinterpret_cast<const uint32_t*>(images), labels, n_images, idx, idx2, B, nrm, pad, flip_enabled, seed, epoch,
+        apply_below, cut_below, cut_table, lam_table, reinterpret_cast<float4*>(x), y, err_flag);
+    return slk_launch_status();
+}
+
+extern "C" int slk_image_batch_blend(const uint8_t* images, const uint8_t* labels, int n_images, int C, int H, int W,
+                                     const int64_t* idx, const int64_t* idx2, int B, const float* mean,
+                                     const float* stdv, int pad, int flip_enabled, uint32_t seed, uint32_t epoch,
+                                     double prob, const uint32_t* cut_table, const float* lam_table, double switch_prob,
+                                     float* x, int64_t* y, int* err_flag, void* stream) {
+    const bool cifar = C == 3 && H == 32 && W == 32, mnist = C == 1 && H == 28 && W == 28;
+    SLK_CHECK_ARG(cifar || mnist);
+    SLK_CHECK_ARG(B >= 0 && n_images > 0 && pad >= 0 && pad <= IMAGE_MAX_PAD);
+    SLK_CHECK_ARG(prob >= 0.0 && prob <= 1.0);                 // NaN fails both compares
+    SLK_CHECK_ARG(switch_prob >= 0.0 && switch_prob <= 1.0);
+    SLK_CHECK_ARG(cut_table || lam_table);
+    SLK_CHECK_ARG(((uintptr_t)cut_table & 3) == 0 && ((uintptr_t)lam_table & 3) == 0);
+    if (B == 0) return 0;
+    SLK_CHECK_ARG(images && labels && idx && idx2 && x && y && mean && stdv);
+    SLK_CHECK_ARG(((uintptr_t)images & 3) == 0 && ((uintptr_t)x & 15) == 0);
+    ImageNorm nrm = {};
+    for (int c = 0; c < C; ++c) {
+        nrm.mean[c] = mean[c];
+        nrm.stdv[c] = stdv[c];
+    }
+    const uint64_t apply_below = (uint64_t)(prob * 4294967296.0);   // apply iff h3 < prob * 2^32 (1.0: always)
+    // CutMix iff h4 < switch_prob * 2^32 with both tables; one table alone names the mode (never / always)
+    const uint64_t cut_below = cut_table && lam_table ? (uint64_t)(switch_prob * 4294967296.0)
+                               : cut_table ? (uint64_t)1 << 32 : 0;
+    if (cifar)
+        return image_batch_blend_launch<3, 32, 32, SLK_IMAGE_QUADS_CIFAR>(images, labels, n_images, idx, idx2, B, nrm,
+                                                                        pad, flip_enabled, seed, epoch, apply_below,
+                                                                        cut_below, cut_table, lam_table, x, y, err_flag,
+                                                                        stream);
+    return image_batch_blend_launch<1, 28, 28, SLK_IMAGE_QUADS_MNIST>(images, labels, n_images, idx, idx2, B, nrm, pad,
+                                                                    flip_enabled, seed, epoch, apply_below, cut_below,
+                                                                    cut_table, lam_table, x, y, err_flag, stream);
 }

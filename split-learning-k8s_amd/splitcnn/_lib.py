@@ -58,6 +58,8 @@ _SIGS = {
     "slk_wide_head_soft": [_P, _P, _P, _P, _P, _U, _U, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "slk_image_batch_mix": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _U, _U, ctypes.c_double, _P, _P, _P,
                             _P],
+    "slk_image_batch_blend": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _U, _U, ctypes.c_double, _P, _P,
+                              ctypes.c_double, _P, _P, _P, _P],
     "slk_fc_wgrad": [_P, _P, _P, _I, _P],
     "slk_fc_wgrad_nslab": [_I],
     "slk_fc_backward": [_P, _P, _P, _P, _P, _P, _I, _P],

@@ -175,7 +175,9 @@ class CifarLoader(ResidentLoader):
     [B,3,32,32] and y i64 [B] by one slk_image_batch launch per batch, eagerly, so every batch sees the
     loader's current `epoch`. `augment=None` (use it for the test split) is no crop and no flip: gather +
     ToTensor + Normalize(mean, std). `mix=CutMix(...)` (splitcnn.loss) pastes a box of the previous sample of the
-    batch into each sample in the same launch (slk_image_batch_mix) and yields mixed labels."""
+    batch into each sample in the same launch (slk_image_batch_mix) and yields mixed labels; `mix=MixUp(...)` blends
+    the two, `mix=Mix(...)` chooses per sample, and CutMix at another alpha draws from a Beta quantile table (all
+    three one slk_image_batch_blend launch)."""
 
     sample_shape = (3, 32, 32)
 

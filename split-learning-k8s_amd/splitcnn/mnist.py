@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .loss import CutMix
+from .loss import CutMix, check_mix, mix_tables
 
 _FILES = {True: ("train-images-idx3-ubyte", "train-labels-idx1-ubyte"),
           False: ("t10k-images-idx3-ubyte", "t10k-labels-idx1-ubyte")}
@@ -87,8 +87,9 @@ class ResidentLoader:
     must finish with a batch before asking for the one after next. `epoch` counts the completed passes (the
     augmentation draws are keyed on it; set_epoch(n) sets it); `err` is set by an out-of-range index.
 
-    `mix` (loss.CutMix) makes each batch one slk_image_batch_mix launch: sample s of a batch gets a box of its
-    partner idx.roll(1)[s] (the previous sample of the same batch, the ragged last one rolling within itself; the
+    `mix` (loss.CutMix, loss.MixUp or loss.Mix) makes each batch one slk_image_batch_mix launch (CutMix at alpha = 1)
+    or one slk_image_batch_blend launch (the others, with their Beta quantile tables built once at construction):
+    sample s of a batch gets a box of, or is blended with, its partner idx.roll(1)[s] (the previous sample of the same batch, the ragged last one rolling within itself; the
     permutation is already random, so no second one is drawn), and y holds mixed labels for a trainer built with
     loss=SoftCrossEntropy(...). Without `augment` the crop and flip are off (pad 0) and mix.seed keys the boxes."""
 
@@ -101,9 +102,7 @@ class ResidentLoader:
         self.shuffle = shuffle
         self.drop_last = drop_last
         self.augment = augment
-        if mix is not None and not isinstance(mix, CutMix):
-            raise TypeError(f"mix: expected splitcnn.loss.CutMix or None, got {type(mix).__name__}")
-        self.mix = mix
+        self.mix = check_mix(mix)
         self.epoch = 0
         self.gen = torch.Generator()
         if seed is not None:
@@ -113,6 +112,8 @@ class ResidentLoader:
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n = len(dataset)
         self._bufs = {}
+        # the Beta quantile tables of slk_image_batch_blend, built once (none for CutMix at alpha = 1)
+        self._cut_table, self._lam_table = mix_tables(mix, self.device)
 
     def __len__(self):
         full, rem = divmod(self.n, self.batch_size)
@@ -143,9 +144,15 @@ class ResidentLoader:
         return dict(pad=a.pad, flip=a.flip, seed=a.seed, epoch=self.epoch)
 
     def _mix_batch(self, idx, x, y, mean, std):
-        """One slk_image_batch_mix launch: partners are the batch rolled by one."""
-        return ops.image_batch_mix(self.images, self.labels, idx, idx.roll(1), mean=mean, std=std, prob=self.mix.prob,
-                                   x=x, y=y, err_flag=self.err, **self._augment_args())
+        """One slk_image_batch_mix launch (CutMix at alpha = 1) or one slk_image_batch_blend launch (any other mix):
+        partners are the batch rolled by one."""
+        if self._cut_table is None and self._lam_table is None:
+            return ops.image_batch_mix(self.images, self.labels, idx, idx.roll(1), mean=mean, std=std,
+                                       prob=self.mix.prob, x=x, y=y, err_flag=self.err, **self._augment_args())
+        return ops.image_batch_blend(self.images, self.labels, idx, idx.roll(1), mean=mean, std=std,
+                                     cut_table=self._cut_table, lam_table=self._lam_table, prob=self.mix.prob,
+                                     switch=getattr(self.mix, "switch", 0.5), x=x, y=y, err_flag=self.err,
+                                     **self._augment_args())
 
     def _batch(self, idx, x, y):
         raise NotImplementedError
@@ -164,8 +171,9 @@ class ResidentLoader:
 class DeviceLoader(ResidentLoader):
     """ResidentLoader over MnistIDX: x f32 [B,1,28,28] by one slk_mnist_batch launch per batch. With
     `augment` (cifar.Augment, e.g. Augment(pad=2, flip=False)) the batch comes from slk_image_batch<1,28,28>
-    instead: RandomCrop(28, padding=pad) (+ flip) before the same ToTensor + Normalize. With `mix` (loss.CutMix)
-    every batch is one slk_image_batch_mix<1,28,28> launch, with or without `augment`."""
+    instead: RandomCrop(28, padding=pad) (+ flip) before the same ToTensor + Normalize. With `mix` (loss.CutMix,
+    MixUp, Mix) every batch is one slk_image_batch_mix<1,28,28> or slk_image_batch_blend<1,28,28> launch, with or
+    without `augment`."""
 
     sample_shape = (1, 28, 28)
 
@@ -174,7 +182,7 @@ class DeviceLoader(ResidentLoader):
         super().__init__(dataset, batch_size, shuffle, seed, device, drop_last, augment, mix)
 
     def _batch(self, idx, x, y):
-        if self.mix is not None:   # slk_image_batch_mix<1,28,28>, with or without augment
+        if self.mix is not None:   # the mixing launches at <1,28,28>, with or without augment
             return self._mix_batch(idx, x, y, (ops.MNIST_MEAN,), (ops.MNIST_STD,))
         if self.augment is None:
             return ops.mnist_batch(self.images, self.labels, idx, x=x, y=y, err_flag=self.err)

@@ -998,6 +998,51 @@ def image_batch_mix(images, labels, idx, idx2, *, mean, std, prob=1.0, pad=0, fl
     return x, y
 
 
+MIX_TABLE = 1024   # entries of slk_image_batch_blend's quantile tables
+
+
+def image_batch_blend(images, labels, idx, idx2, *, mean, std, cut_table=None, lam_table=None, prob=1.0, switch=0.5,
+                      pad=0, flip=False, seed=0, epoch=0, x=None, y=None, err_flag=None):
+    """image_batch with CutMix at any Beta(alpha, alpha) and / or MixUp (slk_image_batch_blend): `cut_table` (1024
+    uint32 box-side fractions, as a torch.uint32 or int32 tensor of the same bits) and `lam_table` (1024 float32
+    weights) are device tensors built by loss.mix_tables; at least one is needed. With both, a sample is CutMix with
+    probability `switch`, else MixUp. y holds mixed labels; loss.mix_draws is the host twin. prob=0 is bitwise
+    image_batch."""
+    if images.dim() == 3:
+        images = images.unsqueeze(1)
+    if images.dim() != 4:
+        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
+    n, C, H, W = (int(d) for d in images.shape)
+    if labels.shape != (n,):
+        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C:
+        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
+    if cut_table is None and lam_table is None:
+        raise ValueError("image_batch_blend: needs cut_table, lam_table or both")
+    B = int(idx.shape[0])
+    pi = _dev(images, "images", dtype=torch.uint8)
+    tabs = []
+    for t, name, dtypes in ((cut_table, "cut_table", (torch.int32, torch.uint32)), (lam_table, "lam_table", (_F32,))):
+        if t is None:
+            tabs.append(None)
+            continue
+        if isinstance(t, torch.Tensor) and t.dtype not in dtypes:
+            raise TypeError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        tabs.append(_dev(t, name, (MIX_TABLE,), t.dtype if isinstance(t, torch.Tensor) else dtypes[0]))
+        if t.device != images.device:
+            raise ValueError(f"{name}: is on {t.device}, images on {images.device}")
+    x = _out(x, (B, C, H, W), images, name="x")
+    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    _lib.call("slk_image_batch_blend", pi, _dev(labels, "labels", dtype=torch.uint8), n, C, H, W,
+              _dev(idx, "idx", (B,), torch.int64), _dev(idx2, "idx2", (B,), torch.int64), B,
+              (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), int(pad), int(bool(flip)),
+              int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, float(prob), tabs[0], tabs[1], float(switch),
+              x.data_ptr(), y.data_ptr(),
+              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+    return x, y
+
+
 # ------------------------------------------------------------------------------------ widened head, soft targets
 def wide_head_soft(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale, grad_scale, smoothing, logits,
                    loss_i, dlogits, dcut, slabs, work, err_flag=None, b0=0):
