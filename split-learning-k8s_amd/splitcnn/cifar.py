@@ -18,6 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import ops
+from .loss import draw_chain
 from .mnist import ResidentLoader
 
 CIFAR_MEAN = (0.4914, 0.4822, 0.4465)
@@ -144,25 +145,11 @@ class Augment:
             raise ValueError(f"Augment: pad must be in [0, 8], got {self.pad}")
 
 
-def _lowbias32(x: np.ndarray) -> np.ndarray:
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7FEB352D)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846CA68B)
-    return x ^ (x >> np.uint32(16))
-
-
 def augment_draws(idx, epoch: int, seed: int, pad: int, flip: bool = True):
     """(dy, dx, flip) int64 arrays, the draws slk_image_batch makes for the dataset indices `idx` in `epoch`
     under `seed`: the host twin of the kernel's hash (include/slk.h), in uint32 / uint64 numpy arithmetic.
     The crop window of sample i starts at (dy - pad, dx - pad); dy, dx are in [0, 2 * pad]."""
-    i = np.asarray(idx).astype(np.int64).astype(np.uint32)
-    with np.errstate(over="ignore"):
-        e = (i * np.uint32(0x9E3779B1) + np.uint32(epoch & 0xFFFFFFFF) * np.uint32(0x85EBCA77)
-             + np.uint32(seed & 0xFFFFFFFF) * np.uint32(0xC2B2AE3D))
-        h0 = _lowbias32(e)
-        h1 = _lowbias32(h0 + np.uint32(0x9E3779B9))
-        h2 = _lowbias32(h1 + np.uint32(0x9E3779B9))
+    h0, h1, h2 = draw_chain(idx, epoch, seed, 3)
     span = np.uint64(2 * pad + 1)
     dy = (h0.astype(np.uint64) * span) >> np.uint64(32)
     dx = (h1.astype(np.uint64) * span) >> np.uint64(32)

@@ -13,6 +13,7 @@ built without `loss=` raises from check_labels instead of training on class a).
     CutMix(alpha=...) / MixUp / Mix     lam ~ Beta(alpha, alpha), MixUp, and a per-sample switch between the two (one
                                         slk_image_batch_blend launch per batch)
     pack_mixed / unpack_mixed           torch tensors on any device
+    draw_chain                          the hash chain every draw of the batch kernels comes from (numpy)
     cutmix_draws                        the host twin of the kernel's box draws (numpy, integers only)
     beta_quantiles / mix_tables         the 1024-entry quantile tables slk_image_batch_blend reads
     mix_draws                           the host twin of slk_image_batch_blend's draws
@@ -155,7 +156,7 @@ def soft_targets(y: torch.Tensor, label_smoothing: float = 0.0, dtype=torch.floa
     return (1.0 - label_smoothing) * t + label_smoothing / NUM_CLASSES
 
 
-# ------------------------------------------------------------------------------------ CutMix draws (host twin)
+# ------------------------------------------------------------------------------------ the kernels' draws (host twins)
 def _lowbias32(x: np.ndarray) -> np.ndarray:
     x = x ^ (x >> np.uint32(16))
     x = x * np.uint32(0x7FEB352D)
@@ -164,31 +165,43 @@ def _lowbias32(x: np.ndarray) -> np.ndarray:
     return x ^ (x >> np.uint32(16))
 
 
+def draw_chain(idx, epoch: int, seed: int, n: int):
+    """[h0, ..., h(n-1)]: the first n links of the hash chain the batch kernels key on (dataset index, epoch, seed)
+    (include/slk.h), as uint32 arrays shaped like `idx`. h0..h2 are the crop and the flip, h3..h7 the mixing draws."""
+    i = np.asarray(idx).astype(np.int64).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        hs = [_lowbias32(i * np.uint32(0x9E3779B1) + np.uint32(epoch & 0xFFFFFFFF) * np.uint32(0x85EBCA77)
+                         + np.uint32(seed & 0xFFFFFFFF) * np.uint32(0xC2B2AE3D))]
+        while len(hs) < n:
+            hs.append(_lowbias32(hs[-1] + np.uint32(0x9E3779B9)))
+    return hs
+
+
+def _scaled(h, n):
+    """(h * n) >> 32 in uint64, as int64: a 32-bit hash as a uniform draw from [0, n)."""
+    return ((h.astype(np.uint64) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def _box(cy, cx, half, H, W):
+    """(y1, y2, x1, x2): the box of half-side `half` centred on (cy, cx), clipped to the image."""
+    return np.clip(cy - half, 0, H), np.clip(cy + half, 0, H), np.clip(cx - half, 0, W), np.clip(cx + half, 0, W)
+
+
+def _below(h, p):
+    """h < p * 2^32, the kernels' test of a draw against a probability."""
+    return h.astype(np.uint64) < np.uint64(int(float(p) * 4294967296.0))
+
+
 def cutmix_draws(idx, epoch: int, seed: int, H: int, W: int, prob: float = 1.0):
     """(apply, y1, y2, x1, x2, wb): the box slk_image_batch_mix pastes into the samples with dataset indices `idx` in
     `epoch` under `seed` (include/slk.h), in uint32 / uint64 numpy arithmetic. apply is bool; the box is rows
     [y1, y2) x columns [x1, x2) (int64, reported also where apply is False); wb is the float32 label weight of the
     partner, area / (H * W) where applied and 0 elsewhere."""
-    i = np.asarray(idx).astype(np.int64).astype(np.uint32)
-    g = np.uint32(0x9E3779B9)
-    with np.errstate(over="ignore"):
-        h = _lowbias32(i * np.uint32(0x9E3779B1) + np.uint32(epoch & 0xFFFFFFFF) * np.uint32(0x85EBCA77)
-                       + np.uint32(seed & 0xFFFFFFFF) * np.uint32(0xC2B2AE3D))
-        hs = [h]
-        for _ in range(7):
-            h = _lowbias32(h + g)
-            hs.append(h)
-    h3, h4, h5, h6, h7 = (v.astype(np.uint64) for v in hs[3:8])
-    s32 = np.uint64(32)
-    apply = h3 < np.uint64(int(float(prob) * 4294967296.0))
-    side = np.maximum((h4 * np.uint64(H)) >> s32, (h5 * np.uint64(H)) >> s32).astype(np.int64)
-    cy, cx = ((h6 * np.uint64(H)) >> s32).astype(np.int64), ((h7 * np.uint64(W)) >> s32).astype(np.int64)
-    half = side // 2
-    y1, y2 = np.clip(cy - half, 0, H), np.clip(cy + half, 0, H)
-    x1, x2 = np.clip(cx - half, 0, W), np.clip(cx + half, 0, W)
+    h3, h4, h5, h6, h7 = draw_chain(idx, epoch, seed, 8)[3:]
+    apply = _below(h3, prob)
+    y1, y2, x1, x2 = _box(_scaled(h6, H), _scaled(h7, W), np.maximum(_scaled(h4, H), _scaled(h5, H)) // 2, H, W)
     area = np.where(apply, (y2 - y1) * (x2 - x1), 0)
-    wb = area.astype(np.float32) / np.float32(H * W)
-    return apply, y1, y2, x1, x2, wb
+    return apply, y1, y2, x1, x2, area.astype(np.float32) / np.float32(H * W)
 
 
 # ------------------------------------------------------------------------------------ Beta(alpha, alpha) tables
@@ -281,31 +294,17 @@ def mix_draws(idx, epoch: int, seed: int, H: int, W: int, prob: float = 1.0, swi
     lam_table[k] for an applied MixUp sample, 0 elsewhere."""
     if cut_table is None and lam_table is None:
         raise ValueError("mix_draws: needs cut_table, lam_table or both")
-    i = np.asarray(idx).astype(np.int64).astype(np.uint32)
-    g = np.uint32(0x9E3779B9)
-    with np.errstate(over="ignore"):
-        h = _lowbias32(i * np.uint32(0x9E3779B1) + np.uint32(epoch & 0xFFFFFFFF) * np.uint32(0x85EBCA77)
-                       + np.uint32(seed & 0xFFFFFFFF) * np.uint32(0xC2B2AE3D))
-        hs = [h]
-        for _ in range(7):
-            h = _lowbias32(h + g)
-            hs.append(h)
-    h3, h4, h5, h6, h7 = (v.astype(np.uint64) for v in hs[3:8])
-    s32 = np.uint64(32)
-    apply = h3 < np.uint64(int(float(prob) * 4294967296.0))
+    h3, h4, h5, h6, h7 = draw_chain(idx, epoch, seed, 8)[3:]
+    apply = _below(h3, prob)
     if cut_table is not None and lam_table is not None:
-        cut = h4 < np.uint64(int(float(switch) * 4294967296.0))
+        cut = _below(h4, switch)
     else:
-        cut = np.full(i.shape, cut_table is not None)
-    k = (h5 >> np.uint64(22)).astype(np.int64)
-    side = np.zeros(i.shape, dtype=np.int64)
+        cut = np.full(h3.shape, cut_table is not None)
+    k = (h5 >> np.uint32(22)).astype(np.int64)
+    side = np.zeros(h3.shape, dtype=np.int64)
     if cut_table is not None:
-        ct = np.asarray(cut_table).view(np.uint32).astype(np.uint64)
-        side = np.where(cut, (ct[k] * np.uint64(H)) >> s32, np.uint64(0)).astype(np.int64)
-    cy, cx = ((h6 * np.uint64(H)) >> s32).astype(np.int64), ((h7 * np.uint64(W)) >> s32).astype(np.int64)
-    half = side // 2
-    y1, y2 = np.clip(cy - half, 0, H), np.clip(cy + half, 0, H)
-    x1, x2 = np.clip(cx - half, 0, W), np.clip(cx + half, 0, W)
+        side = np.where(cut, _scaled(np.asarray(cut_table).view(np.uint32)[k], H), 0)
+    y1, y2, x1, x2 = _box(_scaled(h6, H), _scaled(h7, W), side // 2, H, W)
     area = np.where(apply & cut, (y2 - y1) * (x2 - x1), 0)
     wb = area.astype(np.float32) / np.float32(H * W)
     if lam_table is not None:

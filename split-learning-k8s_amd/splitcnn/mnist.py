@@ -89,9 +89,10 @@ class ResidentLoader:
 
     `mix` (loss.CutMix, loss.MixUp or loss.Mix) makes each batch one slk_image_batch_mix launch (CutMix at alpha = 1)
     or one slk_image_batch_blend launch (the others, with their Beta quantile tables built once at construction):
-    sample s of a batch gets a box of, or is blended with, its partner idx.roll(1)[s] (the previous sample of the same batch, the ragged last one rolling within itself; the
-    permutation is already random, so no second one is drawn), and y holds mixed labels for a trainer built with
-    loss=SoftCrossEntropy(...). Without `augment` the crop and flip are off (pad 0) and mix.seed keys the boxes."""
+    sample s of a batch gets a box of, or is blended with, its partner idx.roll(1)[s] (the previous sample of the
+    same batch, the ragged last one rolling within itself; the permutation is already random, so no second one is
+    drawn), and y holds mixed labels for a trainer built with loss=SoftCrossEntropy(...). Without `augment` the
+    crop and flip are off (pad 0) and mix.seed keys the boxes."""
 
     sample_shape: tuple = ()
 
@@ -112,8 +113,7 @@ class ResidentLoader:
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n = len(dataset)
         self._bufs = {}
-        # the Beta quantile tables of slk_image_batch_blend, built once (none for CutMix at alpha = 1)
-        self._cut_table, self._lam_table = mix_tables(mix, self.device)
+        self._cut_table, self._lam_table = mix_tables(mix, self.device)   # both None for CutMix at alpha = 1
 
     def __len__(self):
         full, rem = divmod(self.n, self.batch_size)

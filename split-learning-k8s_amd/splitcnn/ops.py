@@ -50,6 +50,10 @@ def _out(out, shape, like, dtype=_F32, name="out"):
     return out
 
 
+def _err_ptr(err_flag):
+    return None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32)
+
+
 def batch_of(x: torch.Tensor, tail: tuple, name: str) -> int:
     if x.dim() != 1 + len(tail) or tuple(x.shape[1:]) != tail:
         raise ValueError(f"{name}: expected shape [B,{','.join(map(str, tail))}], got {tuple(x.shape)}")
@@ -239,7 +243,7 @@ def fc_logits_xent(pooled, W3, b3, labels, grad_scale, logits=None, loss_i=None,
     logits = _out(logits, (B, 10), pooled, name="logits")
     loss_i = _out(loss_i, (B,), pooled, name="loss_i")
     dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     _lib.call("slk_fc_logits_xent", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
               _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"), _dev(loss_i, "loss_i"),
               _dev(dlogits, "dlogits"), float(grad_scale), eptr, B, _stream(pooled))
@@ -271,7 +275,7 @@ def _eval_outs(like, B, labels, loss_i, pred, err_flag):
     if labels is not None:
         lptr = _labels(labels, B)
         loss_i = _out(loss_i, (B,), like, name="loss_i")
-        eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+        eptr = _err_ptr(err_flag)
     liptr = _dev(loss_i, "loss_i", (B,)) if loss_i is not None else None
     return pred, loss_i, lptr, liptr, eptr
 
@@ -313,7 +317,7 @@ def xent_fwd_bwd(logits, labels, grad_scale, loss_i=None, dlogits=None, err_flag
     B = batch_of(logits, (10,), "logits")
     loss_i = _out(loss_i, (B,), logits, name="loss_i")
     dlogits = _out(dlogits, (B, 10), logits, name="dlogits")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     _lib.call("slk_xent_fwd_bwd", _dev(logits, "logits"), _labels(labels, B), _dev(loss_i, "loss_i"),
               _dev(dlogits, "dlogits"), float(grad_scale), eptr, B, _stream(logits))
     return loss_i, dlogits
@@ -340,7 +344,7 @@ def fc_xent(pooled, W3, b3, labels, grad_scale, logits=None, loss_i=None, dlogit
     loss_i = _out(loss_i, (B,), pooled, name="loss_i")
     dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
     dpooled = _out(dpooled, tuple(pooled.shape), pooled, name="dpooled")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     if dp_amax is not None:
         _lib.call("slk_fc_xent_amax", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
                   _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"),
@@ -361,7 +365,7 @@ def xent_soft_fwd_bwd(logits, labels, grad_scale, smoothing, loss_i=None, dlogit
     B = batch_of(logits, (10,), "logits")
     loss_i = _out(loss_i, (B,), logits, name="loss_i")
     dlogits = _out(dlogits, (B, 10), logits, name="dlogits")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     _lib.call("slk_xent_soft_fwd_bwd", _dev(logits, "logits"), _labels(labels, B), _dev(loss_i, "loss_i"),
               _dev(dlogits, "dlogits"), float(grad_scale), float(smoothing), eptr, B, _stream(logits))
     return loss_i, dlogits
@@ -374,7 +378,7 @@ def fc_logits_xent_soft(pooled, W3, b3, labels, grad_scale, smoothing, logits=No
     logits = _out(logits, (B, 10), pooled, name="logits")
     loss_i = _out(loss_i, (B,), pooled, name="loss_i")
     dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     _lib.call("slk_fc_logits_xent_soft", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
               _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"), _dev(loss_i, "loss_i"),
               _dev(dlogits, "dlogits"), float(grad_scale), float(smoothing), eptr, B, _stream(pooled))
@@ -389,7 +393,7 @@ def fc_xent_soft(pooled, W3, b3, labels, grad_scale, smoothing, logits=None, los
     loss_i = _out(loss_i, (B,), pooled, name="loss_i")
     dlogits = _out(dlogits, (B, 10), pooled, name="dlogits")
     dpooled = _out(dpooled, tuple(pooled.shape), pooled, name="dpooled")
-    eptr = _dev(err_flag, "err_flag", (1,), torch.int32) if err_flag is not None else None
+    eptr = _err_ptr(err_flag)
     _lib.call("slk_fc_xent_soft", _dev(pooled, "pooled"), _dev(W3, "fc1.weight", (10, 9216)),
               _dev(b3, "fc1.bias", (10,)), _labels(labels, B), _dev(logits, "logits"), _dev(loss_i, "loss_i"),
               _dev(dlogits, "dlogits"), _dev(dpooled, "dpooled"),
@@ -588,31 +592,22 @@ def sgd_multi_from_slabs(segments, lr, loss=None):
     k = len(segments)
     if not 0 <= k <= 4:
         raise ValueError("sgd_multi_from_slabs: at most 4 segments")
-    P = ctypes.c_void_p
-    params, grads, slabs = (P * 4)(), (P * 4)(), (P * 4)()
-    nslab, ns = (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+    cols = [[], [], [], [], []]
     stream_of = None
-    for i, (param, grad, sl) in enumerate(segments):
+    for param, grad, sl in segments:
         nsl, n = sl.shape
         if param is None and grad is None:
             raise ValueError("sgd_multi_from_slabs: a segment needs a param or a grad")
-        params[i] = _dev(param, "param", (n,)) if param is not None else None
-        grads[i] = _dev(grad, "grad", (n,)) if grad is not None else None
-        slabs[i] = _dev(sl, "slabs")
-        nslab[i], ns[i] = nsl, n
+        row = (_dev(param, "param", (n,)) if param is not None else None,
+               _dev(grad, "grad", (n,)) if grad is not None else None, _dev(sl, "slabs"), int(nsl), int(n))
+        for c, v in zip(cols, row):
+            c.append(v)
         stream_of = (param if param is not None else grad) if stream_of is None else stream_of
-    lv, ln, lsc, ring, cap, ctr = None, 0, 0.0, None, 0, None
-    if loss is not None:
-        values, lsc, ring_t, counter = loss
-        lv, ln = _dev(values, "values"), values.numel()
-        ring, cap = _dev(ring_t, "ring"), ring_t.numel()
-        ctr = _dev(counter, "counter", (1,), torch.int32)
-        stream_of = values if stream_of is None else stream_of
+    if stream_of is None and loss is not None:
+        stream_of = loss[0]
     if stream_of is None:
         return
-    cast = lambda a: ctypes.cast(a, P)  # noqa: E731
-    _lib.call("slk_sgd_multi_from_slabs", cast(params), cast(grads), cast(slabs), cast(nslab), cast(ns), k,
-              float(lr), lv, ln, float(lsc), ring, cap, ctr, _stream(stream_of))
+    _lib.call("slk_sgd_multi_from_slabs", *_host_arrays(cols), k, float(lr), *_loss_args(loss), _stream(stream_of))
 
 
 def _host_arrays(columns, n_int=2, k=4):
@@ -939,8 +934,33 @@ def mnist_batch(images, labels, idx, x=None, y=None, err_flag=None, mean=MNIST_M
     _lib.call("slk_mnist_batch", _dev(images, "images", dtype=torch.uint8),
               _dev(labels, "labels", dtype=torch.uint8), n, _dev(idx, "idx", (B,), torch.int64), B,
               float(mean), float(std), x.data_ptr(), y.data_ptr(),
-              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+              _err_ptr(err_flag), _stream(x))
     return x, y
+
+
+def _image_front(images, labels, idx, mean, std, x, y):
+    """What image_batch, image_batch_mix and image_batch_blend check and allocate alike: (images as [N,C,H,W],
+    (n, C, H, W), mean and std as c_float arrays, B, x, y)."""
+    if images.dim() == 3:
+        images = images.unsqueeze(1)
+    if images.dim() != 4:
+        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
+    n, C, H, W = (int(d) for d in images.shape)
+    if labels.shape != (n,):
+        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != C or len(std) != C:
+        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
+    B = int(idx.shape[0])
+    x = _out(x, (B, C, H, W), images, name="x")
+    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    return images, (n, C, H, W), (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), B, x, y
+
+
+def _image_tail(pad, flip, seed, epoch, x, y, err_flag, *mode_args):
+    """The arguments the three entries end with; `mode_args` are the entry's own, between epoch and x."""
+    return (int(pad), int(bool(flip)), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, *mode_args, x.data_ptr(),
+            y.data_ptr(), _err_ptr(err_flag), _stream(x))
 
 
 def image_batch(images, labels, idx, *, mean, std, pad=0, flip=False, seed=0, epoch=0, x=None, y=None,
@@ -950,24 +970,10 @@ def image_batch(images, labels, idx, *, mean, std, pad=0, flip=False, seed=0, ep
     the draws are keyed on (dataset index, epoch, seed) (include/slk.h; cifar.augment_draws is their host
     twin). pad=0, flip=False is plain gather + normalise. The library decides which (C,H,W) and pad it serves:
     anything else raises _lib.SLKError (invalid argument)."""
-    if images.dim() == 3:
-        images = images.unsqueeze(1)
-    if images.dim() != 4:
-        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
-    n, C, H, W = (int(d) for d in images.shape)
-    if labels.shape != (n,):
-        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
-    mean, std = [float(m) for m in mean], [float(s) for s in std]
-    if len(mean) != C or len(std) != C:
-        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
-    B = int(idx.shape[0])
-    x = _out(x, (B, C, H, W), images, name="x")
-    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    images, dims, mean, std, B, x, y = _image_front(images, labels, idx, mean, std, x, y)
     _lib.call("slk_image_batch", _dev(images, "images", dtype=torch.uint8),
-              _dev(labels, "labels", dtype=torch.uint8), n, C, H, W, _dev(idx, "idx", (B,), torch.int64), B,
-              (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), int(pad), int(bool(flip)),
-              int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, x.data_ptr(), y.data_ptr(),
-              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+              _dev(labels, "labels", dtype=torch.uint8), *dims, _dev(idx, "idx", (B,), torch.int64), B, mean, std,
+              *_image_tail(pad, flip, seed, epoch, x, y, err_flag))
     return x, y
 
 
@@ -977,24 +983,11 @@ def image_batch_mix(images, labels, idx, idx2, *, mean, std, prob=1.0, pad=0, fl
     pasted in, each under its own crop and flip; y holds mixed labels (splitcnn.loss.unpack_mixed). The box is keyed
     on (idx[s], epoch, seed) and applied with probability `prob` (loss.cutmix_draws is the host twin). prob=0 is
     bitwise image_batch."""
-    if images.dim() == 3:
-        images = images.unsqueeze(1)
-    if images.dim() != 4:
-        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
-    n, C, H, W = (int(d) for d in images.shape)
-    if labels.shape != (n,):
-        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
-    mean, std = [float(m) for m in mean], [float(s) for s in std]
-    if len(mean) != C or len(std) != C:
-        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
-    B = int(idx.shape[0])
-    x = _out(x, (B, C, H, W), images, name="x")
-    y = _out(y, (B,), images, dtype=torch.int64, name="y")
+    images, dims, mean, std, B, x, y = _image_front(images, labels, idx, mean, std, x, y)
     _lib.call("slk_image_batch_mix", _dev(images, "images", dtype=torch.uint8),
-              _dev(labels, "labels", dtype=torch.uint8), n, C, H, W, _dev(idx, "idx", (B,), torch.int64),
-              _dev(idx2, "idx2", (B,), torch.int64), B, (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std),
-              int(pad), int(bool(flip)), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, float(prob), x.data_ptr(),
-              y.data_ptr(), None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+              _dev(labels, "labels", dtype=torch.uint8), *dims, _dev(idx, "idx", (B,), torch.int64),
+              _dev(idx2, "idx2", (B,), torch.int64), B, mean, std,
+              *_image_tail(pad, flip, seed, epoch, x, y, err_flag, float(prob)))
     return x, y
 
 
@@ -1008,19 +1001,9 @@ def image_batch_blend(images, labels, idx, idx2, *, mean, std, cut_table=None, l
     weights) are device tensors built by loss.mix_tables; at least one is needed. With both, a sample is CutMix with
     probability `switch`, else MixUp. y holds mixed labels; loss.mix_draws is the host twin. prob=0 is bitwise
     image_batch."""
-    if images.dim() == 3:
-        images = images.unsqueeze(1)
-    if images.dim() != 4:
-        raise ValueError(f"images: expected shape [N,C,H,W] or [N,H,W], got {tuple(images.shape)}")
-    n, C, H, W = (int(d) for d in images.shape)
-    if labels.shape != (n,):
-        raise ValueError(f"labels: expected shape ({n},), got {tuple(labels.shape)}")
-    mean, std = [float(m) for m in mean], [float(s) for s in std]
-    if len(mean) != C or len(std) != C:
-        raise ValueError(f"mean / std: expected {C} values each, got {len(mean)} and {len(std)}")
+    images, dims, mean, std, B, x, y = _image_front(images, labels, idx, mean, std, x, y)
     if cut_table is None and lam_table is None:
         raise ValueError("image_batch_blend: needs cut_table, lam_table or both")
-    B = int(idx.shape[0])
     pi = _dev(images, "images", dtype=torch.uint8)
     tabs = []
     for t, name, dtypes in ((cut_table, "cut_table", (torch.int32, torch.uint32)), (lam_table, "lam_table", (_F32,))):
@@ -1032,14 +1015,9 @@ def image_batch_blend(images, labels, idx, idx2, *, mean, std, cut_table=None, l
         tabs.append(_dev(t, name, (MIX_TABLE,), t.dtype if isinstance(t, torch.Tensor) else dtypes[0]))
         if t.device != images.device:
             raise ValueError(f"{name}: is on {t.device}, images on {images.device}")
-    x = _out(x, (B, C, H, W), images, name="x")
-    y = _out(y, (B,), images, dtype=torch.int64, name="y")
-    _lib.call("slk_image_batch_blend", pi, _dev(labels, "labels", dtype=torch.uint8), n, C, H, W,
-              _dev(idx, "idx", (B,), torch.int64), _dev(idx2, "idx2", (B,), torch.int64), B,
-              (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), int(pad), int(bool(flip)),
-              int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, float(prob), tabs[0], tabs[1], float(switch),
-              x.data_ptr(), y.data_ptr(),
-              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), _stream(x))
+    _lib.call("slk_image_batch_blend", pi, _dev(labels, "labels", dtype=torch.uint8), *dims,
+              _dev(idx, "idx", (B,), torch.int64), _dev(idx2, "idx2", (B,), torch.int64), B, mean, std,
+              *_image_tail(pad, flip, seed, epoch, x, y, err_flag, float(prob), tabs[0], tabs[1], float(switch)))
     return x, y
 
 
@@ -1055,5 +1033,5 @@ def wide_head_soft(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale,
               float(smoothing), _dev(logits, "logits", (B, 10)), _dev(loss_i, "loss_i", (B,)),
               _dev(dlogits, "dlogits", (B, 10)), _dev(dcut, "dcut", tuple(cut.shape), torch.bfloat16),
               _dev(slabs, "slabs"), _dev(work, "work"),
-              None if err_flag is None else _dev(err_flag, "err_flag", (1,), torch.int32), int(b0), B, _stream(cut))
+              _err_ptr(err_flag), int(b0), B, _stream(cut))
     return dcut, loss_i, slabs

@@ -154,6 +154,10 @@ def test_mix_fallback_and_refusals(gpu, data):
     assert np.array_equal(x.view(np.uint32), wx.view(np.uint32)) and np.array_equal(y, wy)   # row 0 with row 0's draws
     assert _run(data, src, src2, gpu, **kw)[2] == 0
     assert _run(data, np.array([5, 6]), np.array([7, N]), gpu, **kw)[2] == 1                 # idx2 alone
+    assert _run(data, np.array([-3, 6]), np.array([7, 8]), gpu, **kw)[2] == 1                # idx alone
+    # B = 1: its own partner, and another row's
+    for one, two in (([7], [7]), ([7], [N - 1]), ([0], [3])):
+        _check(data, np.array(one), np.array(two), gpu, **kw)
 
     C, H, W = data["shape"]
     ids = torch.zeros(4, dtype=torch.int64, device=gpu)
