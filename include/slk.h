@@ -820,6 +820,39 @@ int slk_cut8_encode(const void* x_bf16, int n, int fmt, void* rec, void* stream)
 int slk_cut8_decode(const void* rec, int n, int fmt, void* out_bf16, int* err_flag, void* stream);
 int slk_cut8_roundtrip(const void* x_bf16, int n, int fmt, void* out_bf16, void* stream);
 int64_t slk_cut8_record_bytes(void); /* 16400 */
+/* FP8 cut records: stochastic rounding. The record format, e, poisoning, the decode and the saturation at the top of
+ * bf16's range are those above; a record written here is an ordinary record for slk_cut8_decode. Only the conversion
+ * of y_i = x_i * 2^-e changes: each element goes to one of its two neighbouring codes, with probabilities that make
+ * the expectation equal to y_i.
+ * The random word (all uint32 arithmetic, lowbias32 as in the K5 dropout mask): with g = row0 + the sample's row in
+ * the launch, t = *step (a device int32[1] the kernel reads and never writes; a captured graph follows it) and i the
+ * element's index 0..16383,
+ *   base = lowbias32(g * 0x9E3779B1 + t * 0x85EBCA77 + seed * 0xC2B2AE3D + (fmt + 1) * 0x27D4EB2F)
+ *   r_i  = lowbias32(base + i * 0x9E3779B1)
+ * so a slice of rows encoded with its own row0 gives the rows of the whole launch.
+ * The rounding: |y| = sig * 2^q with the integer sig < 256 of the bf16 value; p = floor(log2 |y|), pe = max(p, emin),
+ * and the target's quantum is 2^s units of sig, s = pe - m - q. For s <= 0 the value is representable and the code
+ * is the nearest-rounding code. Otherwise k = sig >> s, rem = sig - (k << s), and the magnitude code is k + up with
+ * the exponent field (pe - emin) << m added on, so a carry lands in the exponent by the addition; the sign is
+ * copied, and a zero result keeps the sign of x_i. With nb = 23 - m (20 for e4m3, 21 for e5m2) and R = r_i >> (32 - nb),
+ *   T = rem << (nb - s) for s <= nb, rem >> (s - nb) above;   up = (R + T) >> nb   (the carry out of nb bits)
+ * — the mapping of gfx950's v_cvt_sr_fp8_f32 / v_cvt_sr_bf8_f32 (they add r's top nb bits to the float32 fraction
+ * bits they discard), which the kernels use; cut8::encode_one_sr (csrc/slk_cut8.h) is this rule in integer C++ and
+ * the specification. rem = 0 never rounds up; for s <= nb exactly rem * 2^(nb - s) of the 2^nb values of R round up,
+ * P(up) = rem / 2^s; for s > nb (a result more than nb - 8 binades below the smallest subnormal's) the count is
+ * floor(rem * 2^(nb - s)), a downward bias below 2^-nb of one quantum. |y| <= F_MAX and F_MAX is representable, so
+ * nothing saturates and no NaN or inf code is produced.
+ * Error: |x - x^| < max(|x| * 2^-m, 2^e * 2^(emin-m)), strict, twice the nearest bound. A value that nearest
+ * rounding reproduces is reproduced for every r: roundtrip_sr(roundtrip(x)) == roundtrip(x) bit for bit, except for
+ * the saturated 0x7F7F / 0xFF7F at the top of bf16's range, which is no multiple of a quantum and goes to either of
+ * its neighbours (the upper one saturates again).
+ * slk_cut8_roundtrip_sr is bitwise decode(encode_sr(x)); out may equal x. Poisoned and all-zero samples, the launch
+ * shape and the refusals are those of slk_cut8_encode / slk_cut8_roundtrip; also refused: a NULL step or one that is
+ * not 4-byte aligned, and row0 < 0. */
+int slk_cut8_encode_sr(const void* x_bf16, int n, int fmt, void* rec, uint32_t seed, const int* step, int row0,
+                       void* stream);
+int slk_cut8_roundtrip_sr(const void* x_bf16, int n, int fmt, void* out_bf16, uint32_t seed, const int* step, int row0,
+                          void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -65,6 +65,60 @@ template <int FMT> SLK_CUT8_FN uint32_t encode_one(uint32_t b, int e) {
     return sign | (r + ((uint32_t)(pe - EMIN) << M));
 }
 
+// ---- stochastic rounding (include/slk.h, "FP8 cut records: stochastic rounding"). These functions are the
+// specification: the kernels' default build converts with v_cvt_sr_fp8_f32 / v_cvt_sr_bf8_f32, whose mapping from the
+// random word to the rounding direction sr_up restates (measured: tools/cut8_sr_check.py), and a -DSLK_CUT8_HWCVT=0
+// build runs encode_one_sr itself.
+SLK_CUT8_FN uint32_t hash32(uint32_t x) {   // lowbias32 (slk_common.h), here for the host as well
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The key of one sample: g its global row, t the step counter's value, all uint32.
+SLK_CUT8_FN uint32_t sr_base(uint32_t g, uint32_t t, uint32_t seed, int fmt) {
+    return hash32(g * 0x9E3779B1u + t * 0x85EBCA77u + seed * 0xC2B2AE3Du + (uint32_t)(fmt + 1) * 0x27D4EB2Fu);
+}
+// The random word of element i.
+SLK_CUT8_FN uint32_t sr_word(uint32_t base, uint32_t i) { return hash32(base + i * 0x9E3779B1u); }
+
+// Whether sig = (k << s) + rem, 0 <= rem < 2^s, s >= 1, goes to k + 1: the instruction's rule. It keeps float32's
+// 23 fraction bits, of which the target has M, so NB = 23 - M bits are discarded in the normal range; it adds the top
+// NB bits of r to them and rounds up on the carry. In the subnormal range it first shifts the fraction right,
+// dropping what falls off the end, so T below is rem's 2^-s scaled to NB bits, floored where s > NB. For s <= NB
+// exactly rem * 2^(NB - s) of the 2^NB values of r >> (32 - NB) carry: P(up) = rem / 2^s, and rem = 0 never does.
+template <int FMT> SLK_CUT8_FN uint32_t sr_up(uint32_t rem, int s, uint32_t r) {
+    constexpr int NB = 23 - Fmt<FMT>::M;   // 20 (e4m3), 21 (e5m2)
+    const uint32_t T = s <= NB ? rem << (NB - s) : (s - NB < 8 ? rem >> (s - NB) : 0u);   // rem < 2^8
+    return ((r >> (32 - NB)) + T) >> NB;
+}
+
+// encode_one with stochastic rounding under the random word r: one of the two neighbouring codes of x * 2^-e, the
+// lower one in magnitude (truncation) plus sr_up. A representable value (s <= 0, or rem == 0) is its own code for
+// every r; the upper neighbour of the largest value below F_MAX is F_MAX itself, so nothing saturates.
+template <int FMT> SLK_CUT8_FN uint32_t encode_one_sr(uint32_t b, int e, uint32_t r) {
+    constexpr int M = Fmt<FMT>::M, EMIN = Fmt<FMT>::EMIN;
+    const uint32_t sign = (b >> 8) & 0x80u;
+    const int ex = (int)((b >> 7) & 0xffu);
+    const uint32_t sig = (b & 0x7fu) | (ex ? 0x80u : 0u);
+    if (sig == 0) return sign;
+    const int q = (ex ? ex : 1) - 134 - e;
+    const int p = (31 - __builtin_clz(sig)) + q;
+    const int pe = p > EMIN ? p : EMIN;
+    const int s = pe - M - q;
+    uint32_t c;
+    if (s <= 0) {
+        c = sig << -s;
+    } else {
+        const uint32_t k = s < 8 ? sig >> s : 0u;   // sig < 2^8
+        c = k + sr_up<FMT>(sig - (s < 8 ? k << s : 0u), s, r);
+    }
+    return sign | (c + ((uint32_t)(pe - EMIN) << M));
+}
+
 // fp8 code -> float32 bits (exact; NaN and inf codes become a float32 NaN / inf of the code's sign).
 template <int FMT> SLK_CUT8_FN uint32_t decode_bits(uint32_t c) {
     constexpr int M = Fmt<FMT>::M, EMIN = Fmt<FMT>::EMIN;

@@ -11,6 +11,11 @@
 // exact float32 product x * 2^-e, and v_cvt_f32_fp8 / v_cvt_f32_bf8 back; -DSLK_CUT8_HWCVT=0 builds the integer
 // arithmetic of slk_cut8.h instead — the form that compiles for the host, where it was checked against torch's
 // float8 casts — and tools/cut8_cvt_check.py compares the two builds bit for bit.
+//
+// The _sr entries run the same per-sample skeleton with another rounding (the Round parameter below): each element
+// goes to one of its two neighbouring codes under a random word keyed on (seed, *step, global row, element) —
+// v_cvt_sr_fp8_f32 / v_cvt_sr_bf8_f32, or cut8::encode_one_sr, which restates them, with -DSLK_CUT8_HWCVT=0
+// (tools/cut8_sr_check.py compares the two builds and the instruction's rule).
 #include "slk_common.h"
 #include "slk_cut8.h"
 
@@ -89,14 +94,59 @@ __device__ __forceinline__ uint32_t code_bits(uint32_t word) {
 #endif
 }
 
-// 16 elements (two vectors of bf16) -> 16 fp8 codes, byte i the code of element i.
+// encode4 under stochastic rounding: element k of the four has the random word rnd[k].
 template <int FMT>
-__device__ __forceinline__ u32x4 encode16(const u32x4& lo, const u32x4& hi, int e) {
+__device__ __forceinline__ uint32_t encode4_sr(uint32_t a, uint32_t b, int e, const uint32_t (&rnd)[4]) {
+#if SLK_CUT8_HWCVT
+    const float s = __uint_as_float((uint32_t)(127 - e) << 23);   // exact products, as in encode4
+    const float f0 = __uint_as_float(a << 16) * s, f1 = __uint_as_float(a & 0xffff0000u) * s;
+    const float f2 = __uint_as_float(b << 16) * s, f3 = __uint_as_float(b & 0xffff0000u) * s;
+    int w = 0;
+    if (FMT == 0) {
+        w = __builtin_amdgcn_cvt_sr_fp8_f32(f0, rnd[0], w, 0);
+        w = __builtin_amdgcn_cvt_sr_fp8_f32(f1, rnd[1], w, 1);
+        w = __builtin_amdgcn_cvt_sr_fp8_f32(f2, rnd[2], w, 2);
+        return (uint32_t)__builtin_amdgcn_cvt_sr_fp8_f32(f3, rnd[3], w, 3);
+    }
+    w = __builtin_amdgcn_cvt_sr_bf8_f32(f0, rnd[0], w, 0);
+    w = __builtin_amdgcn_cvt_sr_bf8_f32(f1, rnd[1], w, 1);
+    w = __builtin_amdgcn_cvt_sr_bf8_f32(f2, rnd[2], w, 2);
+    return (uint32_t)__builtin_amdgcn_cvt_sr_bf8_f32(f3, rnd[3], w, 3);
+#else
+    return cut8::encode_one_sr<FMT>(a & 0xffffu, e, rnd[0]) | (cut8::encode_one_sr<FMT>(a >> 16, e, rnd[1]) << 8) |
+           (cut8::encode_one_sr<FMT>(b & 0xffffu, e, rnd[2]) << 16) | (cut8::encode_one_sr<FMT>(b >> 16, e, rnd[3]) << 24);
+#endif
+}
+
+// The rounding of a launch: four elements starting at element `i` of the sample -> four codes.
+struct Nearest {
+    template <int FMT> __device__ __forceinline__ uint32_t encode4(uint32_t a, uint32_t b, int e, uint32_t) const {
+        return ::encode4<FMT>(a, b, e);
+    }
+};
+struct Stochastic {
+    uint32_t base;   // cut8::sr_base of the block's sample
+    template <int FMT> __device__ __forceinline__ uint32_t encode4(uint32_t a, uint32_t b, int e, uint32_t i) const {
+        const uint32_t rnd[4] = {cut8::sr_word(base, i), cut8::sr_word(base, i + 1), cut8::sr_word(base, i + 2),
+                                 cut8::sr_word(base, i + 3)};
+        return encode4_sr<FMT>(a, b, e, rnd);
+    }
+};
+// The block's rounding from the kernel's trailing arguments: none (Nearest), or (seed, step, row0) — step a device
+// int32 the kernel reads and never writes, row0 the global row of the launch's first sample.
+template <int FMT, class Round> __device__ __forceinline__ Round block_round() { return Round{}; }
+template <int FMT, class Round> __device__ __forceinline__ Round block_round(uint32_t seed, const int* step, int row0) {
+    return Round{cut8::sr_base((uint32_t)row0 + blockIdx.x, (uint32_t)*step, seed, FMT)};
+}
+
+// 16 elements (two vectors of bf16) starting at element i of the sample -> 16 fp8 codes, byte k the code of i + k.
+template <int FMT, class Round>
+__device__ __forceinline__ u32x4 encode16(const u32x4& lo, const u32x4& hi, int e, const Round& round, uint32_t i) {
     u32x4 out;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         const u32x4& src = w < 2 ? lo : hi;
-        out[w] = encode4<FMT>(src[2 * (w & 1)], src[2 * (w & 1) + 1], e);
+        out[w] = round.template encode4<FMT>(src[2 * (w & 1)], src[2 * (w & 1) + 1], e, i + 4 * w);
     }
     return out;
 }
@@ -125,9 +175,11 @@ __device__ __forceinline__ void store_nan_row(uint16_t* __restrict__ out) {
     }
 }
 
-template <int FMT>
-__global__ __launch_bounds__(THREADS) void cut8_encode_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ rec) {
+template <int FMT, class Round, class... Key>
+__global__ __launch_bounds__(THREADS) void cut8_encode_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ rec,
+                                                              Key... key) {
     __shared__ uint32_t red[4];
+    const Round round = block_round<FMT, Round>(key...);
     Sample s;
     load_sample(x + (size_t)blockIdx.x * cut8::SAMPLE, s);
     const uint32_t a = block_amax_bits(s, red);
@@ -141,7 +193,7 @@ __global__ __launch_bounds__(THREADS) void cut8_encode_kernel(const uint16_t* __
 #pragma unroll
     for (int j = 0; j < CHUNKS; ++j) {
         const u32x4 zero = {0u, 0u, 0u, 0u};
-        const u32x4 codes = poison ? zero : encode16<FMT>(s.v[2 * j], s.v[2 * j + 1], e);
+        const u32x4 codes = poison ? zero : encode16<FMT>(s.v[2 * j], s.v[2 * j + 1], e, round, (uint32_t)chunk_elem(j));
         *reinterpret_cast<u32x4*>(r + cut8::HEADER + chunk_elem(j)) = codes;
     }
 }
@@ -173,10 +225,12 @@ __global__ __launch_bounds__(THREADS) void cut8_decode_kernel(const uint8_t* __r
 }
 
 // decode(encode(x)) without the record; x and out are not __restrict__: they may be the same buffer (a block
-// has read its whole sample, and passed the reduction's barrier, before its first store).
-template <int FMT>
-__global__ __launch_bounds__(THREADS) void cut8_roundtrip_kernel(const uint16_t* x, uint16_t* out) {
+// has read its whole sample, and passed the reduction's barrier, before its first store); the step counter is read
+// before that barrier too.
+template <int FMT, class Round, class... Key>
+__global__ __launch_bounds__(THREADS) void cut8_roundtrip_kernel(const uint16_t* x, uint16_t* out, Key... key) {
     __shared__ uint32_t red[4];
+    const Round round = block_round<FMT, Round>(key...);
     Sample s;
     load_sample(x + (size_t)blockIdx.x * cut8::SAMPLE, s);
     const uint32_t a = block_amax_bits(s, red);
@@ -188,7 +242,7 @@ __global__ __launch_bounds__(THREADS) void cut8_roundtrip_kernel(const uint16_t*
     const int e = cut8::scale_exp<FMT>(a);
 #pragma unroll
     for (int j = 0; j < CHUNKS; ++j) {
-        const u32x4 codes = encode16<FMT>(s.v[2 * j], s.v[2 * j + 1], e);
+        const u32x4 codes = encode16<FMT>(s.v[2 * j], s.v[2 * j + 1], e, round, (uint32_t)chunk_elem(j));
         u32x4 lo, hi;
         decode16<FMT>(codes, e, lo, hi);
         u32x4* p = reinterpret_cast<u32x4*>(o + chunk_elem(j));
@@ -198,6 +252,7 @@ __global__ __launch_bounds__(THREADS) void cut8_roundtrip_kernel(const uint16_t*
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 }  // namespace
 
 extern "C" int64_t slk_cut8_record_bytes() { return cut8::RECORD; }
@@ -208,8 +263,8 @@ extern "C" int slk_cut8_encode(const void* x_bf16, int n, int fmt, void* rec, vo
     SLK_CHECK_ARG(x_bf16 && rec && aligned16(x_bf16) && aligned16(rec));
     const uint16_t* x = static_cast<const uint16_t*>(x_bf16);
     uint8_t* r = static_cast<uint8_t*>(rec);
-    if (fmt == 0) cut8_encode_kernel<0><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r);
-    else cut8_encode_kernel<1><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r);
+    if (fmt == 0) cut8_encode_kernel<0, Nearest><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r);
+    else cut8_encode_kernel<1, Nearest><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r);
     return slk_launch_status();
 }
 
@@ -231,7 +286,31 @@ extern "C" int slk_cut8_roundtrip(const void* x_bf16, int n, int fmt, void* out_
     SLK_CHECK_ARG(x_bf16 && out_bf16 && aligned16(x_bf16) && aligned16(out_bf16));
     const uint16_t* x = static_cast<const uint16_t*>(x_bf16);
     uint16_t* o = static_cast<uint16_t*>(out_bf16);
-    if (fmt == 0) cut8_roundtrip_kernel<0><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o);
-    else cut8_roundtrip_kernel<1><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o);
+    if (fmt == 0) cut8_roundtrip_kernel<0, Nearest><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o);
+    else cut8_roundtrip_kernel<1, Nearest><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o);
+    return slk_launch_status();
+}
+
+extern "C" int slk_cut8_encode_sr(const void* x_bf16, int n, int fmt, void* rec, uint32_t seed, const int* step, int row0,
+                                  void* stream) {
+    SLK_CHECK_ARG(n >= 0 && (fmt == 0 || fmt == 1) && row0 >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(x_bf16 && rec && aligned16(x_bf16) && aligned16(rec) && step && aligned4(step));
+    const uint16_t* x = static_cast<const uint16_t*>(x_bf16);
+    uint8_t* r = static_cast<uint8_t*>(rec);
+    if (fmt == 0) cut8_encode_kernel<0, Stochastic><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r, seed, step, row0);
+    else cut8_encode_kernel<1, Stochastic><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, r, seed, step, row0);
+    return slk_launch_status();
+}
+
+extern "C" int slk_cut8_roundtrip_sr(const void* x_bf16, int n, int fmt, void* out_bf16, uint32_t seed, const int* step,
+                                     int row0, void* stream) {
+    SLK_CHECK_ARG(n >= 0 && (fmt == 0 || fmt == 1) && row0 >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(x_bf16 && out_bf16 && aligned16(x_bf16) && aligned16(out_bf16) && step && aligned4(step));
+    const uint16_t* x = static_cast<const uint16_t*>(x_bf16);
+    uint16_t* o = static_cast<uint16_t*>(out_bf16);
+    if (fmt == 0) cut8_roundtrip_kernel<0, Stochastic><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o, seed, step, row0);
+    else cut8_roundtrip_kernel<1, Stochastic><<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(x, o, seed, step, row0);
     return slk_launch_status();
 }

@@ -119,6 +119,8 @@ _SIGS = {
     "slk_cut8_decode": [_P, _I, _I, _P, _P, _P],
     "slk_cut8_roundtrip": [_P, _I, _I, _P, _P],
     "slk_cut8_record_bytes": [],
+    "slk_cut8_encode_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
+    "slk_cut8_roundtrip_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

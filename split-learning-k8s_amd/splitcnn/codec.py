@@ -20,6 +20,7 @@ from .ops import _dev, _stream
 CUT8_SAMPLE = 16384      # bf16 elements of one K5 cut [256,8,8] or of one cut-gradient row
 CUT8_RECORD = 16400      # bytes of one record: a 16-byte header and one fp8 code per element
 CUT8_FORMATS = {"e4m3": 0, "e5m2": 1}
+CUT8_ROUNDINGS = ("nearest", "stochastic")
 
 
 class CutCodec:
@@ -93,20 +94,64 @@ class Fp8Cut:
     either may be None, which leaves that direction dense bf16. The formats are constructor constants passed to the
     kernels by value: a captured graph keeps them, and there is no setter.
 
+    `rounding` is "nearest" (round to nearest even), "stochastic", or a dict per direction such as
+    {"bwd": "stochastic"} (a missing key means nearest). A stochastic direction sends every element to one of its two
+    neighbouring codes with probabilities that make the expectation equal to the value (include/slk.h, "FP8 cut records:
+    stochastic rounding"), under a random word keyed on (`seed`, a device step counter, the global row row0 + row,
+    the element): its encode / roundtrip take `step`, a device int32[1] the kernel reads at run time — a captured
+    graph follows it — and `row0`, the global row of the first sample, so a slice of a batch encodes to the bits of
+    the whole batch. `rounding` and `seed` are constructor constants passed to the kernels by value like the formats:
+    a captured graph keeps them, and there is no setter. decode does not depend on the rounding.
+
     A sample is 16,384 contiguous bf16 elements: x / out are [n, ...] with 16,384 elements per row, records are
     uint8 [n, 16400]. Every method works on caller-visible buffers and launches on the tensor's current stream."""
 
-    def __init__(self, fwd="e4m3", bwd="e5m2"):
+    def __init__(self, fwd="e4m3", bwd="e5m2", rounding="nearest", seed: int = 0):
         for name, v in (("fwd", fwd), ("bwd", bwd)):
             if v is not None and v not in CUT8_FORMATS:
                 raise ValueError(f"Fp8Cut: {name}={v!r}; expected one of {sorted(CUT8_FORMATS)} or None")
         if fwd is None and bwd is None:
             raise ValueError("Fp8Cut: fwd and bwd are both None — that is the dense exchange (pass no codec)")
         self.fwd, self.bwd = fwd, bwd
+        if isinstance(rounding, dict):
+            extra = sorted(set(rounding) - {"fwd", "bwd"}, key=repr)
+            if extra:
+                raise ValueError(f"Fp8Cut: rounding has keys {extra}; expected 'fwd' and / or 'bwd'")
+            rounding = {d: rounding.get(d, "nearest") for d in ("fwd", "bwd")}
+        else:
+            rounding = {"fwd": rounding, "bwd": rounding}
+        for d, v in rounding.items():
+            if not isinstance(v, str) or v not in CUT8_ROUNDINGS:
+                raise ValueError(f"Fp8Cut: rounding of {d} is {v!r}; expected one of {list(CUT8_ROUNDINGS)}")
+            if v == "stochastic" and self.format(d) is None:
+                raise ValueError(f"Fp8Cut: rounding of {d} is 'stochastic' but {d}=None leaves that direction dense; "
+                                 f"name the other direction alone: rounding={{'{'bwd' if d == 'fwd' else 'fwd'}': "
+                                 "'stochastic'}")
+        self._rounding = rounding
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"Fp8Cut: seed={seed!r}; expected an integer in [0, 2^32)")
+        self.seed = seed
+        self._nearest = None
         self._bufs = {}
 
     def __repr__(self):
-        return f"Fp8Cut(fwd={self.fwd!r}, bwd={self.bwd!r})"
+        r = self._rounding
+        shown = r["fwd"] if r["fwd"] == r["bwd"] else r
+        return f"Fp8Cut(fwd={self.fwd!r}, bwd={self.bwd!r}, rounding={shown!r}, seed={self.seed})"
+
+    def rounding_of(self, direction: str) -> str:
+        """The rounding of "fwd" / "bwd": "nearest" or "stochastic"."""
+        self.format(direction)
+        return self._rounding[direction]
+
+    def nearest(self) -> "Fp8Cut":
+        """This codec's formats with round-to-nearest in both directions (what evaluation uses): self if it is that
+        already, otherwise one twin kept for the codec's lifetime, so its buffers stay valid under a captured graph."""
+        if all(v == "nearest" for v in self._rounding.values()):
+            return self
+        if self._nearest is None:
+            self._nearest = Fp8Cut(self.fwd, self.bwd)
+        return self._nearest
 
     def format(self, direction: str):
         """The format name of "fwd" / "bwd", or None where that direction stays dense."""
@@ -149,11 +194,30 @@ class Fp8Cut:
             self._bufs[k] = t
         return t
 
-    def encode(self, x, rec, direction: str = "fwd"):
-        """x (bf16 [n, ...]) -> rec (uint8 [n, 16400]) in `direction`'s format."""
+    def _key(self, direction, x, step, row0):
+        """(seed, step pointer, row0) of a stochastic launch, checked; None where `direction` rounds to nearest."""
+        if self.rounding_of(direction) != "stochastic":
+            return None
+        if step is None:
+            raise ValueError(f"Fp8Cut: the {direction} direction rounds stochastically and needs step=, a device "
+                             "int32[1] counter (a stage's step_ctr)")
+        _dev(step, "step", (1,), torch.int32)
+        if step.device != x.device:
+            raise ValueError(f"step: on {step.device}, the tensor is on {x.device}")
+        if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 < 2 ** 31:
+            raise ValueError(f"row0={row0!r}; expected an integer in [0, 2^31)")
+        return self.seed, step.data_ptr(), row0
+
+    def encode(self, x, rec, direction: str = "fwd", step=None, row0: int = 0):
+        """x (bf16 [n, ...]) -> rec (uint8 [n, 16400]) in `direction`'s format and rounding; a stochastic direction
+        needs `step` (device int32[1]) and takes `row0`, the global row of x[0]."""
         fmt, n = self._fmt(direction), self._rows(x, "x")
         self._records(rec, n)
-        _lib.call("slk_cut8_encode", x.data_ptr(), n, fmt, rec.data_ptr(), _stream(x))
+        key = self._key(direction, x, step, row0)
+        if key is None:
+            _lib.call("slk_cut8_encode", x.data_ptr(), n, fmt, rec.data_ptr(), _stream(x))
+        else:
+            _lib.call("slk_cut8_encode_sr", x.data_ptr(), n, fmt, rec.data_ptr(), *key, _stream(x))
         return rec
 
     def decode(self, rec, out, err_flag, direction: str = "fwd"):
@@ -165,12 +229,17 @@ class Fp8Cut:
         _lib.call("slk_cut8_decode", rec.data_ptr(), n, fmt, out.data_ptr(), err_flag.data_ptr(), _stream(out))
         return out
 
-    def roundtrip(self, x, out, direction: str):
-        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x."""
+    def roundtrip(self, x, out, direction: str, step=None, row0: int = 0):
+        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x. `step` and `row0`
+        as for encode."""
         fmt, n = self._fmt(direction), self._rows(x, "x")
         if self._rows(out, "out") != n:
             raise ValueError(f"out: expected {n} samples like x, got {out.shape[0]}")
-        _lib.call("slk_cut8_roundtrip", x.data_ptr(), n, fmt, out.data_ptr(), _stream(x))
+        key = self._key(direction, x, step, row0)
+        if key is None:
+            _lib.call("slk_cut8_roundtrip", x.data_ptr(), n, fmt, out.data_ptr(), _stream(x))
+        else:
+            _lib.call("slk_cut8_roundtrip_sr", x.data_ptr(), n, fmt, out.data_ptr(), *key, _stream(x))
         return out
 
 

@@ -861,7 +861,9 @@ class WideHub:
     the sender encodes the part into one uint8 tensor, the receiver decodes it where the dense tensor would have
     landed (the server into its `cuts` slice before accumulate; it encodes each `dcuts` slice before sending) — so
     the step is exactly wide.WideTrainer(cut_codec=...)'s at batch (N-1)*B. A direction set to None travels dense
-    bf16. HIP kernels: the stage must be on a CUDA device. Every rank that decodes keeps `err_flag` (a malformed
+    bf16. A direction the codec rounds stochastically is encoded under the sender's step_ctr (not yet ticked: the
+    client ticks in step_from_grads, the server in finish_step) and the part's first row in the concatenated batch,
+    rank * B + k * b — the server's b0 — so the words are the fused step's. HIP kernels: the stage must be on a CUDA device. Every rank that decodes keeps `err_flag` (a malformed
     record decodes to NaNs and sets it); check_exchange() reads it. `exchange_bytes` counts what this rank sent and
     received in the last step, `dense_bytes` what the dense exchange would have moved."""
 
@@ -926,7 +928,7 @@ class WideHub:
             sl = slice(k * b, (k + 1) * b)
             cut = c.forward(x[sl], tag=k)
             if f8:
-                cut = q.encode(cut, q.records(("fwd", k), b, x.device), "fwd")
+                cut = q.encode(cut, q.records(("fwd", k), b, x.device), "fwd", step=c.step_ctr, row0=self.rank * B + k * b)
             sends.append(isend(cut, self.server_rank, fw))
             sends.append(isend(y[sl], self.server_rank, fw))
         for k in range(m):
@@ -969,8 +971,10 @@ class WideHub:
                     r.wait()
                 if f8:
                     q.decode(recs[c, k], cuts[sl], self.err_flag, "fwd")
-                s.accumulate(cuts[sl], labels[sl], 1.0 / G, c * B + k * b, part, m * nc, dcut=dcuts[sl])
-                out = q.encode(dcuts[sl], q.records(("bwd", c, k), b, device), "bwd") if b8 else dcuts[sl]
+                b0 = c * B + k * b
+                s.accumulate(cuts[sl], labels[sl], 1.0 / G, b0, part, m * nc, dcut=dcuts[sl])
+                out = (q.encode(dcuts[sl], q.records(("bwd", c, k), b, device), "bwd", step=s.step_ctr, row0=b0)
+                       if b8 else dcuts[sl])
                 sends.append(isend(out, c, bw))
                 part += 1
         s.finish_step(m * nc, step=self.global_step)

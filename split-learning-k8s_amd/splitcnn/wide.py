@@ -647,7 +647,12 @@ class WideTrainer(GraphedTrainer):
     through, exactly what the wire does — two slk_cut8_roundtrip launches inside the captured graph (one per
     direction that is not None). evaluate / eval_batch / predict quantise the cut the same way, on the live and on
     the averaged weights: that is what a deployed server receives. The formats are by-value constants a captured
-    graph keeps (no setter); cut_codec=None launches nothing new."""
+    graph keeps (no setter); cut_codec=None launches nothing new. A direction the codec rounds stochastically
+    (Fp8Cut(rounding=...)) launches slk_cut8_roundtrip_sr with row0 = 0 and a stage counter the graph follows: the
+    cut under the client's step_ctr, the cut gradient under the server's, each read before its stage's tick (the
+    gradient is rounded between the head and the server's Adam), so load_optimizer_state reproduces the bits and
+    the step stays dist.WideHub(codec=...)'s. Evaluation and prediction round the cut to nearest whatever the
+    training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd)."""
 
     input_shape = (3, 32, 32)
 
@@ -665,21 +670,34 @@ class WideTrainer(GraphedTrainer):
                                       schedule=self.client.schedule, clip=self.client.clip, loss=loss,
                                       ema=self.client.ema_cfg)
 
-    def _wire(self, t, direction, name):
+    def _wire(self, t, direction, name, step=None):
         """What the other side of an FP8 exchange receives for t: roundtrip(t) in `direction`'s format, in the
         server stage's buffer `name` (fwd) or in place (bwd: the server's own dcut buffer); t itself without a
-        codec or where the direction is dense."""
+        codec or where the direction is dense. `step` is the stage counter a stochastic direction is keyed on
+        (row0 = 0: t is the whole batch); without it — evaluation — the rounding is to nearest."""
         q = self.cut_codec
         if q is None or q.format(direction) is None:
             return t
+        if step is None:
+            q = q.nearest()
         out = self.server._b(name, tuple(t.shape), _BF) if name is not None else t
         with TIMER("cut8_roundtrip"):
-            return q.roundtrip(t, out, direction)
+            if q.rounding_of(direction) == "stochastic":
+                return q.roundtrip(t, out, direction, step=step)
+            return q.roundtrip(t, out, direction)   # today's call, argument for argument
 
     def _eager(self, x, y):
-        c = self.client
-        dcut, _ = self.server.step_request(self._wire(c.forward(x), "fwd", "cut_q"), y)
-        c.backward_step(self._wire(dcut, "bwd", None))
+        c, s, q = self.client, self.server, self.cut_codec
+        cut = self._wire(c.forward(x), "fwd", "cut_q", c.step_ctr)
+        if q is not None and q.format("bwd") is not None and q.rounding_of("bwd") == "stochastic":
+            # step_request with the gradient rounded before the server's tick: its words are this step's
+            dcut, loss_i, sf = s.forward_backward(cut, y, 1.0 / cut.shape[0])
+            dcut = self._wire(dcut, "bwd", None, s.step_ctr)
+            s.log_loss(loss_i)
+            s.step_from_slabs(sf)
+        else:
+            dcut = self._wire(s.step_request(cut, y)[0], "bwd", None, s.step_ctr)
+        c.backward_step(dcut)
 
     def _state(self):
         c, s = self.client, self.server
