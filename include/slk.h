@@ -57,10 +57,46 @@ const char* slk_error_string(int err);
  * splitcnn/_lib.py refuses a library whose id differs from the tree's. */
 const char* slk_build_id(void);
 
+/* ---------------------------------------------------------------- NaN and +-inf
+ * What every entry of the convolution path (client stage, server stage, the x3 and K5 forms) does with a non-finite
+ * operand. It DEVIATES from torch in clause 2: torch's relu and max_pool2d return NaN for a NaN, these kernels +0.
+ * tests/nonfinite_ref.py states the rule in float64, tests/test_nonfinite_k2_gpu.py holds every K2 entry to it.
+ *
+ * 1. Arithmetic is IEEE. A non-finite operand of a product propagates into every accumulator the product is summed
+ *    into (0 x NaN = NaN, 0 x inf = NaN), except under clause 4.
+ * 2. ReLU and max-pool are selects. ReLU is v > 0 ? v : +0. The pooled value is the maximum of the window's values that
+ *    compare greater than 0, else +0 with code 4 (CODE_NONE). A NaN or -inf pre-activation gives +0; a +inf is kept
+ *    and its code is its index. A code byte is always 0, 1, 2, 3 or 4. NOT torch: a NaN weight, bias or input pixel
+ *    is erased here and the logged loss stays finite where the reference logs NaN (README, "NaN and +-inf").
+ *    The x3 forwards scan a window from its FIRST raw accumulator with a strict > (csrc/slk_x3.hip pool_piece): a NaN
+ *    in that position gives +0 / code 4 for the window, a NaN in another position is skipped.
+ * 3. Scaling maxima ignore NaN (fmaxf): slk_row_amax, the fused maxima of slk_fc_dgrad_amax / slk_fc_backward /
+ *    slk_fc_xent_amax, conv1_cut_bound of slk_conv1_fwd_amax / slk_conv1_fwd_x3, the x3sa forward's own maximum. An
+ *    infinite maximum gives scale exponent 0 (csrc/slk_x3.hip x3_exp). An x3 kernel then splits a +-inf operand into
+ *    (+-inf, inf - inf = NaN), so every output it reaches is NaN before clause 2 applies, and the weight gradients'
+ *    launch-wide scale moves for every sample; the f32 forms (Winograd, direct) keep +-inf, except that Winograd's
+ *    transforms (B^T d B, G g G^T, A^T m A: csrc/slk_wino.hip) meet inf - inf and may turn it into NaN inside the
+ *    2 x 2 tiles (all nine taps of a weight gradient) the infinity reaches.
+ * 4. Products that are never formed. A pooled gradient exists only where a code routes it. The 2:4-sparse weight
+ *    gradients (slk_conv2_wgrad_x3s, the K5 weight gradients) skip exact zeros of dY: a non-finite activation that
+ *    meets only exact zeros of dY may or may not make its column non-finite. Staged zero padding IS multiplied: a
+ *    poisoned weight of a dgrad or of a padded (K5) forward may reach every pixel of its channel's planes, and a
+ *    poisoned gradient at a border pixel every tap of its channel in the K5 weight gradients.
+ * 5. Masks are selects. A gradient at a position whose ReLU bit or routing code excludes it is +0 whatever came in
+ *    (the Winograd dgrad expands a window with a bit-mask AND, so its cut gradient is non-finite exactly where the
+ *    direct kernel's is; the Winograd wgrad drops a blocked window's value before its table multiply).
+ * 6. Samples are independent in every entry whose output has a batch dimension: another sample's NaN or inf changes
+ *    no bit of a clean sample's output. Slabs the poisoned sample does not feed are unchanged.
+ * 7. Heads, optimizers, EMA, both codecs and the loaders keep the contracts stated at their declarations. The K5
+ *    head's dropout is a select ((keep bit) ? d * keep_scale : 0, csrc/slk_wide_head.hip): a DROPPED NaN or inf feature
+ *    is 0 (torch's Dropout multiplies by the mask and keeps a NaN), a kept one is an ordinary operand of clause 1.
+ * The supported check is Python's GraphedTrainer.check_finite() (parameters, optimizer state, averaged blocks). */
+
 /* ---------------------------------------------------------------- client stage (ModelPartA) */
 
-/* act = relu(conv2d(x, W1, b1)), stride 1, no padding.
- * Replaces ModelPartA.forward (src/model_def.py:11-12) as called at src/client_part.py:114. */
+/* act = conv2d(x, W1, b1) > 0 ? conv2d(x, W1, b1) : +0, stride 1, no padding: torch's relu except for a NaN
+ * pre-activation, which gives +0 (clause 2 above).
+ * Replaces ModelPartA.forward (src/model_def.py:11-12) as called at src/client_part.py:114 on finite operands. */
 int slk_conv1_fwd(const float* x, const float* W1, const float* b1, float* act, int B, void* stream);
 
 /* slk_conv1_fwd that also writes act_amax[b], the per-sample scale value of the x3 conv2 kernels: since
@@ -88,7 +124,8 @@ int slk_conv1_wgrad_remask(const float* x, const float* W1, const float* b1, con
 
 /* pooled = maxpool2(relu(conv2d(act, W2, b2))) and its argmax code, fused (Winograd F(2x2,3x3) on
  * the f32 MFMA: one transformed 2x2 output tile = one pool window). Replaces ModelPartB.forward lines
- * src/model_def.py:25-27 as called at src/server_part.py:48. */
+ * src/model_def.py:25-27 as called at src/server_part.py:48 on finite operands; relu and maxpool2 are clause 2's
+ * selects ("NaN and +-inf" above: a NaN pre-activation is dropped, not propagated as torch does). */
 int slk_conv2_fwd_pool(const float* act, const float* W2, const float* b2, float* pooled,
                        uint8_t* code, int B, void* stream);
 /* The same op as a direct implicit GEMM (f32 MFMA, k-ordered fma chains); kept as the A/B and
@@ -212,7 +249,9 @@ int slk_conv2_wgrad_direct_nslab(int B);
  * v_mfma_f32_16x16x32_f16 (hi*hi + hi*lo + lo*hi) into an f32 accumulator: per-product relative error
  * <= ~7e-7 (csrc/slk_x3.hip). Operand scales: weights per launch (from max|W2|), data per sample from a
  * caller-supplied per-sample max |.| (slk_row_amax, or a producer that emits it); the arrays must bound
- * their rows (a too-small bound overflows f16 to inf). Replace the same reference lines as the f32 ops. */
+ * their rows (a too-small bound overflows f16 to inf). Replace the same reference lines as the f32 ops.
+ * Non-finite operands (clause 3 above): NaN never enters a scale; a +-inf operand of any x3 entry becomes NaN in every
+ * output it reaches (forwards: then +0 / code 4 by clause 2), where the f32 forms would pass +inf on. */
 
 /* amax[r] = max_i |x[r*n + i]| for r < rows (NaNs ignored). */
 int slk_row_amax(const float* x, int rows, int n, float* amax, void* stream);
@@ -241,7 +280,8 @@ int slk_conv2_wgrad_x3s(const uint16_t* act16, const float* act_amax, const floa
                         const uint8_t* code, float* slabs, int B, void* stream);
 /* Which kernel slk_conv2_wgrad_x3s runs: always 2 = on the 2:4-sparse f16 MFMA (v_smfmac_f32_16x16x64_f16:
  * the max-pool routing leaves at most 2 nonzeros of dY in every 4 consecutive output pixels of a row starting at
- * a multiple of 4, so half the dense x3 products are never issued). 1 (the dense x3 kernel) and 0 (the round-4
+ * a multiple of 4, so half the dense x3 products are never issued; clause 4 above: a non-finite activation that meets
+ * only skipped zeros of dY does not reach its column). 1 (the dense x3 kernel) and 0 (the round-4
  * kernel) named forms that are no longer built. Measurement only (bench.py prices the executed products against
  * the matching peak). */
 int slk_conv2_wgrad_x3_form(void);

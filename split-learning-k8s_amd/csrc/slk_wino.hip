@@ -388,8 +388,11 @@ extern "C" int slk_conv2_fwd_pool(const float* act, const float* W2, const float
 // Routing lookup tables, built once per workgroup in LDS (float4 entries, code c = 0..4):
 //   dgrad  EXP[c] = (c==0, c==1, c==2, c==3): the 2x2 block of a window whose gradient sits at c;
 //   wgrad  ZT[c][16] = A[i][c>>1] * A[j][c&1] (A = [1 0; 1 1; 1 -1; 0 -1]): Z = A dY A^T of that block.
-// Code 4 (ReLU-blocked window) maps to zeros. A lookup + packed multiplies replaces per-element
-// compares and selects: on gfx950 every VALU instruction costs its issue cycles on top of the f32
+// Code 4 (ReLU-blocked window) maps to zeros. The dgrad's rows are bit masks applied with an AND, the wgrad drops a
+// blocked window's value with one select before its multiply: a multiply by a 0 entry would pass a non-finite
+// dpooled through the mask (NaN * 0 = NaN; include/slk.h "NaN and +-inf", clause 5). In the wgrad the zeros inside a
+// routed row are entries of Z = A dY A^T of the SAME output channel, whose every weight-gradient column the value
+// reaches anyway. A lookup replaces per-element compares and selects: on gfx950 every VALU instruction costs its issue cycles on top of the f32
 // MFMA stream (tools/ubench/fillers.hip), packed or not, so the count of instructions is what matters.
 __device__ __forceinline__ void build_luts(float* lut_exp, float* lut_z, int tid) {
     if (tid < 5 * 4) {
@@ -453,7 +456,7 @@ __global__ __launch_bounds__(WD_THREADS, 1) void conv2_dgrad_wino_kernel(
     float* __restrict__ gcut, int B) {
     __shared__ __attribute__((aligned(16))) float smem[2 * WD_BSTR + 2 * WD_XCH + 40];
     float* xch = smem + 2 * WD_BSTR;
-    float* lut = xch + 2 * WD_XCH;  // EXP table, 5 float4, then 5 zero float4 (out-of-range windows)
+    float* lut = xch + 2 * WD_XCH;  // EXP mask table, 5 float4, then 5 zero float4 (out-of-range windows)
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
@@ -462,7 +465,7 @@ __global__ __launch_bounds__(WD_THREADS, 1) void conv2_dgrad_wino_kernel(
 
     int b = blockIdx.x;
     if (b < B) wd_dma_sample(dpool, code, b, smem, wu, lane);
-    if (tid < 40) lut[tid] = (tid < 20 && (tid >> 2) == (tid & 3)) ? 1.f : 0.f;
+    if (tid < 40) lut[tid] = __uint_as_float((tid < 20 && (tid >> 2) == (tid & 3)) ? 0xFFFFFFFFu : 0u);  // bit masks
 
     // transformed flipped filters: lane (ci = 16(m ^ kh) + li, co = 32kh + 4s + lk); slot m = 0 is the
     // ci block this wave finishes, m = 1 the one it hands to its partner
@@ -547,13 +550,18 @@ __global__ __launch_bounds__(WD_THREADS, 1) void conv2_dgrad_wino_kernel(
 #pragma unroll
                 for (int w = 0; w < 4; ++w) E[w] = lutw[w][c[w]];
             };
+            // The table row is a BIT MASK per position (all ones at the routed one, zeros elsewhere; all zeros for code 4
+            // and for an out-of-range window) and the expansion an AND: a multiply by a 0/1 row would carry a
+            // non-finite dpooled into the positions the code excludes and through a blocked window (NaN * 0 = NaN;
+            // include/slk.h "NaN and +-inf", clause 5).
             auto expand = [&](const float (&v)[4], const float4 (&E)[4], f2 (&v01)[4], f2 (&v23)[4]) {
                 f2 Rlo[4], Rhi[4];
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
                     const float4 e = E[w];
-                    const f2 vv = {v[w], v[w]};
-                    const f2 r0 = vv * f2{e.x, e.y}, r1 = vv * f2{e.z, e.w};
+                    const uint32_t vb = __float_as_uint(v[w]);
+                    const f2 r0 = {__uint_as_float(vb & __float_as_uint(e.x)), __uint_as_float(vb & __float_as_uint(e.y))};
+                    const f2 r1 = {__uint_as_float(vb & __float_as_uint(e.z)), __uint_as_float(vb & __float_as_uint(e.w))};
                     const int wy = w >> 1;
                     if (w & 1) { Rhi[2 * wy] = r0; Rhi[2 * wy + 1] = r1; }
                     else { Rlo[2 * wy] = r0; Rlo[2 * wy + 1] = r1; }
@@ -873,12 +881,15 @@ __global__ __launch_bounds__(WW_THREADS, 1) void conv2_wgrad_wino_kernel(
                 for (int i = 0; i < 4; ++i) E[m][i] = zt[i];
             }
         };
-        auto xform = [&](const f2 (&lo)[2][4], const f2 (&hi)[2][4], const float (&v)[2], const float4 (&E)[2][4]) {
+        // as in the dgrad: a blocked window's value is dropped by a select, not by its all-zero table row (clause 5)
+        auto xform = [&](const f2 (&lo)[2][4], const f2 (&hi)[2][4], const float (&v)[2], const int (&c)[2],
+                         const float4 (&E)[2][4]) {
             pk_wino_in(lo[0], hi[0], v01[0], v23[0]);
             pk_wino_in(lo[1], hi[1], v01[1], v23[1]);
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
-                const f2 vv = {v[m], v[m]};
+                const float vs = c[m] < CODE_NONE ? v[m] : 0.f;
+                const f2 vv = {vs, vs};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float4 e = E[m][i];
@@ -892,7 +903,7 @@ __global__ __launch_bounds__(WW_THREADS, 1) void conv2_wgrad_wino_kernel(
         load(0, Rlo[0], Rhi[0], dv[0], cd[0]);
         load(1, Rlo[1], Rhi[1], dv[1], cd[1]);
         zload(cd[0], E);
-        xform(Rlo[0], Rhi[0], dv[0], E);
+        xform(Rlo[0], Rhi[0], dv[0], cd[0], E);
         const float* dma_dst = smem + (buf + WW_NBUF - 1 >= WW_NBUF ? buf - 1 : buf + WW_NBUF - 1) * WW_BSTR;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
@@ -914,7 +925,7 @@ __global__ __launch_bounds__(WW_THREADS, 1) void conv2_wgrad_wino_kernel(
                         mfma_acc(acc[m][n][4 * i + 3], z23[m][i].y, v23[n][i].y);
                     }
             __builtin_amdgcn_sched_barrier(0);
-            if (j < 5) xform(Rlo[(j + 1) & 1], Rhi[(j + 1) & 1], dv[(j + 1) & 1], E);
+            if (j < 5) xform(Rlo[(j + 1) & 1], Rhi[(j + 1) & 1], dv[(j + 1) & 1], cd[(j + 1) & 1], E);
         }
         buf = buf + 1 == WW_NBUF ? 0 : buf + 1;
     }

@@ -159,6 +159,22 @@ class GraphedTrainer:
         self.server.loss_log.note_step(self.global_step)
         self.global_step += 1
 
+    # ---- non-finite values
+    def check_finite(self) -> None:
+        """Raise FloatingPointError if any parameter, optimizer-state tensor (momentum, m, v) or averaged block of
+        either stage holds a NaN or an infinity, naming stage and tensor ("server.conv2.weight", "client.conv1.bias
+        (momentum)"). One host sync; nothing is launched inside the step. The convolution path writes +0 for a NaN
+        pre-activation (include/slk.h "NaN and +-inf", clause 2), so a NaN weight can stay in a model whose logged
+        loss is finite; call this next to check_labels() to notice it. A non-finite INPUT pixel that clause 2 erases
+        before it reaches a parameter is not detectable this way."""
+        from .recipe import _raise_nonfinite
+        names, flags = [], []
+        for stage, st in (("client", self.client), ("server", self.server)):
+            n, f = st._finite_flags()
+            names += [(stage, b, t) for b, t in n]
+            flags.append(f)
+        _raise_nonfinite(names, torch.cat(flags).tolist())
+
     # ---- gradient clipping (optim.ClipNorm)
     def grad_norms(self) -> Dict[str, tuple]:
         """{"client": (norm, coef), "server": (norm, coef)} of the last step: each stage's global L2 gradient

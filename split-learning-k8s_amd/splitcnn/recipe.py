@@ -95,6 +95,14 @@ def ema_update(stages):
         ops.ema_multi([(st.ema, st.params) for st in stages], cfg.value, stages[0].step_ctr, cfg.start, cfg.warmup)
 
 
+def _raise_nonfinite(names, ok) -> None:
+    """names: [(stage, block, tensor)], ok: [bool]. Raises FloatingPointError listing every entry that is not ok."""
+    bad = [f"{stage}.{tensor}" + ("" if block == "params" else f" ({block})")
+           for (stage, block, tensor), good in zip(names, ok) if not good]
+    if bad:
+        raise FloatingPointError("splitcnn: non-finite values (NaN or inf) in " + ", ".join(bad))
+
+
 class StageRecipe:
     """Optimizer state and step of a stage that keeps `params` / `grads` as flat blocks on `device`.
 
@@ -227,6 +235,35 @@ class StageRecipe:
             ema_update([self])
             with TIMER("tick") if self.TICK_TIMER else _UNTIMED:
                 ops.tick(self.step_ctr)
+
+    # ---- non-finite values (include/slk.h "NaN and +-inf")
+    def _finite_flags(self):
+        """([(block, tensor)], device bool [n]): for every tensor of TENSORS in the parameter block, every
+        optimizer-state block (STATE) and the averaged block (ema=), whether all its values are finite. Torch
+        reductions on the current stream, outside the step; no host sync."""
+        blocks = [("params", self.params)]
+        blocks += [("momentum" if k == "buf" else k, t) for k, t in zip(self.STATE, self._blocks())]
+        if self.ema is not None:
+            blocks.append(("ema", self.ema))
+        sd = self.model.state_dict()
+        names, flags = [], []
+        for bname, flat in blocks:
+            off = 0
+            for t in self.TENSORS:
+                k = sd[t].numel()
+                names.append((bname, t))
+                flags.append(torch.isfinite(flat[off:off + k]).all())
+                off += k
+        return names, torch.stack(flags)
+
+    def check_finite(self, stage: str = None) -> None:
+        """Raise FloatingPointError naming every tensor of this stage — parameters, optimizer state (momentum, m, v),
+        averaged block — that holds a NaN or an infinity. One host sync. The convolution path writes +0 for a NaN
+        pre-activation (clause 2 of the non-finite rule), so a NaN weight can sit in a model whose logged loss stays
+        finite: this is the supported way to notice it. It cannot see a non-finite INPUT that the rule erases before
+        it reaches a parameter."""
+        names, flags = self._finite_flags()
+        _raise_nonfinite([(stage or type(self).__name__, b, t) for b, t in names], flags.tolist())
 
     def _weights(self, shapes, ema=False):
         """Views of the parameter block, or of the averaged block (ema), in the tensors' own shapes."""
