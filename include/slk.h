@@ -90,6 +90,9 @@ const char* slk_build_id(void);
  * 7. Heads, optimizers, EMA, both codecs and the loaders keep the contracts stated at their declarations. The K5
  *    head's dropout is a select ((keep bit) ? d * keep_scale : 0, csrc/slk_wide_head.hip): a DROPPED NaN or inf feature
  *    is 0 (torch's Dropout multiplies by the mask and keeps a NaN), a kept one is an ordinary operand of clause 1.
+ *    The cut noise (slk_cut_noise, "Cut noise" below) has no special case: a NaN element makes its sample's s2, coef
+ *    and every clipped element NaN, an infinite s2 gives coef = 0 (then 0 x inf = NaN at an infinite element), and
+ *    without a clip a non-finite element stays its own; no other sample is touched.
  * The supported check is Python's GraphedTrainer.check_finite() (parameters, optimizer state, averaged blocks). */
 
 /* ---------------------------------------------------------------- client stage (ModelPartA) */
@@ -893,6 +896,52 @@ int slk_cut8_encode_sr(const void* x_bf16, int n, int fmt, void* rec, uint32_t s
                        void* stream);
 int slk_cut8_roundtrip_sr(const void* x_bf16, int n, int fmt, void* out_bf16, uint32_t seed, const int* step, int row0,
                           void* stream);
+/* Cut noise (csrc/slk_cut_noise.hip): an opt-in defence of the K5 cut against model inversion — a per-sample norm
+ * bound, then additive noise from a 1,024-entry table. An experiment's tool, not a certified mechanism: no epsilon
+ * is claimed. A sample is the 16,384 contiguous bf16 elements of one cut row, as in the FP8 records. All float
+ * arithmetic is float32 and EVERY operation is rounded on its own (fl(.) below): no fma contraction anywhere.
+ * Clip (only where max_norm is not NULL; max_norm is a device f32[1], so a captured graph follows it):
+ *   s2 = sum x_i^2 in one fixed order. Thread t of 256 holds elements [16 (256 j + t), +16), j = 0..3, and adds
+ *        fl(x_i * x_i) one at a time from 0, j ascending, then the element ascending. Inside each wave of 64 the xor
+ *        butterfly a = a + shfl_xor(a, o) runs for o = 32, 16, 8, 4, 2, 1; the four waves' sums w0..w3 (threads
+ *        64 w .. 64 w + 63) combine as (w0 + w1) + (w2 + w3).
+ *   norm = sqrt(s2);  coef = *max_norm / (norm + 1e-6f), replaced by 1 where it compares greater than 1
+ *        (slk_clip_coef's formulation); the square root and the division are correctly rounded.
+ *        *max_norm = inf gives coef = 1 for a finite norm. stats[row] = (norm, coef), f32 pairs, where stats is given.
+ *   c_i = fl(coef * x_i).      Without max_norm nothing is reduced, stats is not written and c_i = x_i exactly.
+ * Draw (only where scale is not NULL; scale is a device f32[1]). All uint32 arithmetic, lowbias32 as in the K5
+ * dropout mask; g = row0 + the sample's row in the launch, t = *step (a device int32[1] read as uint32 and never
+ * written; a captured graph follows it), i the element's index 0..16383:
+ *   base = lowbias32(g * 0x9E3779B1 + t * 0x85EBCA77 + seed * 0xC2B2AE3D + 3 * 0x27D4EB2F)    (cut8 uses 1 and 2)
+ *   r    = lowbias32(base + i * 0x9E3779B1);     r2 = lowbias32(r + 0x9E3779B9)
+ *   neg  = r >> 31;    k = (r >> 21) & 1023;     G = clz(r2), 32 for r2 = 0
+ *   a    = fl(fl(tail * (float)G) + table[k]);   n = fl(*scale * a), its sign bit flipped where neg
+ *   y_i  = bf16_rne(fl(c_i + n))
+ * so a slice of rows launched with its own row0 gives the rows of the whole launch. table is a device f32[1024]
+ * (16-byte aligned; its values are not validated), tail a by-value float. Without scale, y_i = bf16_rne(c_i) and
+ * table, tail, seed, step and row0 are not read.
+ * The two laws the Python side builds (splitcnn/privacy.py):
+ *   Laplace(b):   -ln U = G ln 2 + (-ln U'), G geometric, U' uniform on (1/2, 1), so tail = f32(ln 2), table[k] =
+ *                 f32(-log1p(-(k + 0.5) / 2048)), *scale = b: exact in distribution up to the 1,024 strata of U'; the
+ *                 magnitude ends at about 32 ln 2 b, a cut of probability 2^-32 per element.
+ *   Gaussian(s):  tail = 0, table[k] = the half-normal quantile at (k + 0.5) / 1024, *scale = s: 2,048 values, the
+ *                 support ends at 3.487 s and the table's variance is 0.99936.
+ * NaN and +-inf follow IEEE with no special case ("NaN and +-inf" clause 7): a NaN result is a quiet NaN of
+ * unspecified sign and payload.
+ * Backward (slk_cut_scale_rows): the noise is additive and the clip coefficient is treated as a CONSTANT (detached,
+ * as the FP8 codec is straight-through), so the client back-propagates out_i = bf16_rne(fl(coef_row * x_i)) with
+ * coef_row = stats[row][1] — a deviation from differentiating through the norm, which would add a term along x. A
+ * coef of 1 leaves every finite element's bits.
+ * One block of 256 threads per sample; the sample is read once and held in registers; the table is staged once per
+ * block in LDS; every output element and every stats pair is written by exactly one thread with ordinary vector
+ * stores, without atomics. out may equal x. n == 0 launches nothing and returns 0. Refused with
+ * hipErrorInvalidValue before any launch: n < 0, row0 < 0, a NULL x / out (or stats for slk_cut_scale_rows), x or
+ * out not 16-byte aligned, stats not 8-byte aligned, max_norm or scale not 4-byte aligned, and with scale a NULL or
+ * misaligned table (16 bytes) or step (4 bytes). stats may be NULL in slk_cut_noise (the pairs are then not kept). */
+int slk_cut_noise(const void* x_bf16, int n, const float* table, float tail, const float* scale,
+                  const float* max_norm, uint32_t seed, const int* step, int row0, void* out_bf16, float* stats,
+                  void* stream);
+int slk_cut_scale_rows(const void* x_bf16, int n, const float* stats, void* out_bf16, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -121,6 +121,9 @@ _SIGS = {
     "slk_cut8_record_bytes": [],
     "slk_cut8_encode_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
     "slk_cut8_roundtrip_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
+    # per-sample clip + table noise on the K5 cut (privacy.CutNoise)
+    "slk_cut_noise": [_P, _I, _P, _F, _P, _P, _U, _P, _I, _P, _P, _P],
+    "slk_cut_scale_rows": [_P, _I, _P, _P, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

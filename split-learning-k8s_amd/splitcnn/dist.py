@@ -865,9 +865,17 @@ class WideHub:
     client ticks in step_from_grads, the server in finish_step) and the part's first row in the concatenated batch,
     rank * B + k * b — the server's b0 — so the words are the fused step's. HIP kernels: the stage must be on a CUDA device. Every rank that decodes keeps `err_flag` (a malformed
     record decodes to NaNs and sets it); check_exchange() reads it. `exchange_bytes` counts what this rank sent and
-    received in the last step, `dense_bytes` what the dense exchange would have moved."""
+    received in the last step, `dense_bytes` what the dense exchange would have moved.
 
-    def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None, codec=None):
+    noise (privacy.CutNoise; client ranks only — the defence sits where the data is, and the server side is
+    unchanged): part k is clipped and noised (slk_cut_noise) into a hub buffer keyed by k, under the client's step_ctr
+    (not yet ticked) and row0 = rank * B + k * b, before the encode / isend; the received gradient part is scaled by
+    that part's coefficients (slk_cut_scale_rows, only with a clip) after the decode and before backward_grads. So
+    the hub step is wide.WideTrainer(cut_noise=...)'s at batch (N-1)*B, and the byte counts do not change. HIP
+    kernels: the stage must be on a CUDA device."""
+
+    def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None, codec=None,
+                 noise=None):
         _default_optimizer_only("WideHub", stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.server_rank = world - 1
@@ -882,6 +890,17 @@ class WideHub:
                 raise ValueError("WideHub(codec=...): the FP8 cut codec runs as HIP kernels on CUDA tensors; the stage "
                                  f"is on {device} — pass no codec (on BOTH sides) for CPU stages")
             self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.noise = None
+        if noise is not None:
+            from .privacy import check_cut_noise
+            self.noise = check_cut_noise(noise)
+            device = torch.device(getattr(stage, "device", "cpu"))
+            if device.type != "cuda":
+                raise ValueError("WideHub(noise=...): the cut noise runs as HIP kernels on CUDA tensors; the stage is "
+                                 f"on {device} — pass no noise for CPU stages")
+            if rank == self.server_rank:
+                raise ValueError("WideHub(noise=...): the cut noise runs on the client ranks; the server rank takes none")
+            self.noise.to(device)
         if groups is None:   # one group per direction, as for Hub (exchange_groups)
             groups = exchange_groups() if dist.is_initialized() else (None, None)
         self.groups = tuple(groups)
@@ -916,10 +935,12 @@ class WideHub:
                                "reserved bytes or an exponent out of range); its sample was decoded to NaNs")
 
     def client_step(self, x, y):
-        c, q = self.stage, self.codec
+        c, q, nz = self.stage, self.codec, self.noise
         B, m = x.shape[0], self.micro
         assert B % m == 0, "batch must be divisible by the micro-batch count"
         b = B // m
+        clipped = nz is not None and nz.clip_value is not None
+        stats = [self._buf(("cut_stats", k), (b, 2), torch.float32, x.device) if clipped else None for k in range(m)]
         dcut = self._buf("dcut", c.cut_shape(B), c.cut_dtype, x.device)
         fw, bw = self.groups
         f8, b8 = self._fp8("fwd"), self._fp8("bwd")
@@ -927,6 +948,9 @@ class WideHub:
         for k in range(m):
             sl = slice(k * b, (k + 1) * b)
             cut = c.forward(x[sl], tag=k)
+            if nz is not None:
+                cut = nz.apply(cut, self._buf(("cut_n", k), tuple(cut.shape), cut.dtype, x.device), step=c.step_ctr,
+                               row0=self.rank * B + k * b, stats=stats[k])
             if f8:
                 cut = q.encode(cut, q.records(("fwd", k), b, x.device), "fwd", step=c.step_ctr, row0=self.rank * B + k * b)
             sends.append(isend(cut, self.server_rank, fw))
@@ -938,6 +962,8 @@ class WideHub:
             recvs[k].wait()
             if b8:
                 q.decode(grecs[k], dcut[k * b:(k + 1) * b], self.err_flag, "bwd")
+            if clipped:
+                nz.scale_rows(dcut[k * b:(k + 1) * b], stats[k], dcut[k * b:(k + 1) * b])
             c.backward_grads(dcut[k * b:(k + 1) * b], tag=k, accumulate=k > 0)
         for w in sends:
             w.wait()

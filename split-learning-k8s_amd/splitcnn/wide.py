@@ -38,6 +38,7 @@ from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
 from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema
+from .privacy import CutNoise, check_cut_noise
 from .recipe import Seg, StageRecipe, _flatten_params
 
 P_DROP = 0.25
@@ -652,7 +653,18 @@ class WideTrainer(GraphedTrainer):
     cut under the client's step_ctr, the cut gradient under the server's, each read before its stage's tick (the
     gradient is rounded between the head and the server's Adam), so load_optimizer_state reproduces the bits and
     the step stays dist.WideHub(codec=...)'s. Evaluation and prediction round the cut to nearest whatever the
-    training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd)."""
+    training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd).
+
+    `cut_noise` (privacy.CutNoise) puts a noise defence on the cut, inside the captured step: the cut is clipped per
+    sample and noised (slk_cut_noise) into the server-stage buffer `cut_n` under the client's step_ctr with row0 = 0,
+    read before the client's tick — then the FP8 forward direction if there is a codec, then the head. Backward: the
+    head's dcut, the FP8 backward direction if any, then — only with a clip — slk_cut_scale_rows in place (the
+    coefficient held constant: straight through), then the client's backward. A replay follows the counter, so
+    load_optimizer_state reproduces the bits; CutNoise.set_scale / set_clip reach a captured graph, its kind, seed,
+    table and tail are by-value constants it keeps. evaluate / eval_batch / predict apply the clip and NO noise, on
+    the live and on the averaged weights: evaluation stays a pure function of the weights (noisy inference is the
+    user's own CutNoise.apply call). cut_stats() reads the last step's (norm, coef) per sample. cut_noise=None
+    launches nothing new."""
 
     input_shape = (3, 32, 32)
 
@@ -660,11 +672,15 @@ class WideTrainer(GraphedTrainer):
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
                  loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
-                 cut_codec: Optional[Fp8Cut] = None):
+                 cut_codec: Optional[Fp8Cut] = None, cut_noise: Optional[CutNoise] = None):
         check_clip(clip)
         check_ema(ema)
         self.cut_codec = check_cut_codec(cut_codec)
+        self.cut_noise = check_cut_noise(cut_noise)
         super().__init__(device, graph)
+        if self.cut_noise is not None:
+            self.cut_noise.to(self.device)
+        self._cut_stats_B = None
         self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
                                       schedule=self.client.schedule, clip=self.client.clip, loss=loss,
@@ -686,9 +702,46 @@ class WideTrainer(GraphedTrainer):
                 return q.roundtrip(t, out, direction, step=step)
             return q.roundtrip(t, out, direction)   # today's call, argument for argument
 
+    def _noised(self, cut, name, step=None):
+        """The cut the defence lets out: clip + noise of `cut` in the server stage's buffer `name`, the (norm, coef)
+        pairs in `name`_stats; cut itself without a defence. `step` is the stage counter the draws are keyed on
+        (row0 = 0: cut is the whole batch); without it — evaluation — only the clip runs (and nothing without one)."""
+        n = self.cut_noise
+        if n is None or (step is None and n.clip_value is None):
+            return cut
+        out = self.server._b(name, tuple(cut.shape), _BF)
+        stats = self.server._b(name + "_stats", (cut.shape[0], 2), _F32) if n.clip_value is not None else None
+        with TIMER("cut_noise"):
+            return n.apply(cut, out, step=step, stats=stats, noise=step is not None)
+
+    def _unclipped(self, dcut):
+        """The gradient of the clip with its coefficient held constant: dcut scaled in place by the forward's
+        per-sample coefficient; dcut itself without a clip."""
+        n = self.cut_noise
+        if n is None or n.clip_value is None:
+            return dcut
+        with TIMER("cut_scale_rows"):
+            return n.scale_rows(dcut, self.server._b("cut_n_stats", (dcut.shape[0], 2), _F32), dcut)
+
+    def cut_stats(self) -> torch.Tensor:
+        """f32 [B, 2] on the host: (norm, coef) of every sample of the last training step's cut — its L2 norm before
+        the clip and the coefficient applied (1.0: not clipped). One host sync. Needs cut_noise= with a clip
+        (CutNoise(clip=float("inf")) measures without clipping)."""
+        n = self.cut_noise
+        if n is None or n.clip_value is None:
+            raise RuntimeError("cut_stats: the trainer was built without cut_noise= or its CutNoise has clip=None")
+        if self._cut_stats_B is None:
+            raise RuntimeError("cut_stats: no training step has run yet")
+        return self.server._b("cut_n_stats", (self._cut_stats_B, 2), _F32).cpu()
+
+    def step(self, x, y):
+        self._cut_stats_B = int(x.shape[0])   # which of the per-batch-size stats buffers the last step wrote
+        super().step(x, y)
+
     def _eager(self, x, y):
         c, s, q = self.client, self.server, self.cut_codec
-        cut = self._wire(c.forward(x), "fwd", "cut_q", c.step_ctr)
+        cut = self._noised(c.forward(x), "cut_n", c.step_ctr)
+        cut = self._wire(cut, "fwd", "cut_q", c.step_ctr)
         if q is not None and q.format("bwd") is not None and q.rounding_of("bwd") == "stochastic":
             # step_request with the gradient rounded before the server's tick: its words are this step's
             dcut, loss_i, sf = s.forward_backward(cut, y, 1.0 / cut.shape[0])
@@ -697,7 +750,7 @@ class WideTrainer(GraphedTrainer):
             s.step_from_slabs(sf)
         else:
             dcut = self._wire(s.step_request(cut, y)[0], "bwd", None, s.step_ctr)
-        c.backward_step(dcut)
+        c.backward_step(self._unclipped(dcut))
 
     def _state(self):
         c, s = self.client, self.server
@@ -721,7 +774,8 @@ class WideTrainer(GraphedTrainer):
         ema = self._check_weights(weights)
         # the client forward under its own tag: the saved tensors of a training forward (tag "") survive
         self.eval_cut = self.client.forward(x, tag="eval", ema=ema)   # the last evaluation's cut (a stage buffer)
-        return self.server.evaluate(self._wire(self.eval_cut, "fwd", "eval_cut_q"), y, metrics=metrics, ema=ema)
+        cut = self._wire(self._noised(self.eval_cut, "eval_cut_n"), "fwd", "eval_cut_q")
+        return self.server.evaluate(cut, y, metrics=metrics, ema=ema)
 
     def predict(self, x, return_logits: bool = False, weights: str = "live"):
         """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
