@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports exactly what
-include/slk.h declares, argument validation works without a GPU, and the Python module contract
+include/slk.h declares with the argument types it declares, argument validation works without a GPU (four entries by
+hand, then every entry that takes a pointer, in a child process that sees no device), and the Python module contract
 (src/model_def.py:1-71) is preserved: names, state_dict keys/shapes, seeded init, get_model."""
 import os
 import re
@@ -37,6 +38,134 @@ def test_argument_validation_without_gpu():
     assert lib.slk_error_string(1) == b"invalid argument"
     with pytest.raises(_lib.SLKError, match="invalid argument"):
         _lib.call("slk_conv2_dgrad", None, None, None, None, 3, None)
+
+
+def test_ctypes_signatures_match_the_header_types():
+    """Every declaration of include/slk.h against _lib._SIGS position by position (a pointer is c_void_p, int c_int,
+    unsigned / uint32_t c_uint, int64_t c_int64, float c_float, double c_double) and its return type against
+    _RESTYPES: a c_float where the header says int would hand the kernel another register's contents."""
+    import ctypes
+    from abi_sweep import declarations, param_ctype
+    from splitcnn import _lib
+    decls = declarations()
+    assert [name for _, name, _ in decls] and sorted(name for _, name, _ in decls) == header_symbols()
+    assert len(decls) == len(set(name for _, name, _ in decls)) >= 116
+    returns = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+    bad = []
+    for ret, name, params in decls:
+        want = [param_ctype(t) for t, _ in params]
+        got = _lib._SIGS[name]
+        if len(got) != len(want):
+            bad.append(f"{name}: {len(got)} ctypes arguments, the header declares {len(want)}")
+            continue
+        bad += [f"{name}: argument {i} ({t} {n}) is bound as {g.__name__}, the header says {w.__name__}"
+                for i, ((t, n), g, w) in enumerate(zip(params, got, want)) if g is not w]
+        if _lib._RESTYPES.get(name, ctypes.c_int) is not returns[ret]:
+            bad.append(f"{name}: returns {ret}, bound as {_lib._RESTYPES.get(name, ctypes.c_int).__name__}")
+    assert not bad, "\n".join(bad)
+    assert set(_lib._RESTYPES) <= set(_lib._SIGS)
+
+
+# Pointers an entry accepts as NULL, each with the words of include/slk.h that say so (an entry defined as another
+# entry's variant is quoted at that definition). Everything else must be refused when it is NULL.
+OPTIONAL_POINTERS = {
+    "slk_xent_fwd_bwd": {"err_flag": "sets *err_flag (may be NULL)"},
+    "slk_fc_logits_xent": {"err_flag": "slk_fc_fwd + slk_xent_fwd_bwd in one launch"},
+    "slk_fc_xent": {"err_flag": "Fused server head: fc1 forward, cross-entropy forward+backward"},
+    "slk_fc_xent_amax": {"err_flag": "slk_fc_xent that also writes dp_amax[b]"},
+    "slk_xent_soft_fwd_bwd": {"err_flag": "it sets *err_flag (may be NULL)"},
+    "slk_fc_logits_xent_soft": {"err_flag": "it sets *err_flag (may be NULL)"},
+    "slk_fc_xent_soft": {"err_flag": "it sets *err_flag (may be NULL)",
+                         "dp_amax": "dp_amax may be NULL (then it is not written)"},
+    "slk_conv1_fwd_x3": {"act": "act when act != NULL", "relu_bits": "relu_bits (optional,"},
+    "slk_fc_eval": {"logits": "logits may be NULL (not stored)", "labels": "NULL (predict only)",
+                    "err_flag": "(may be NULL) and gives loss_i = NaN"},
+    "slk_eval_logits": {"labels": "labels / loss_i / err_flag as in slk_fc_eval",
+                        "err_flag": "labels / loss_i / err_flag as in slk_fc_eval"},
+    "slk_sgd_from_slabs": {"grad": "grad[i] = g (if grad != NULL)"},
+    "slk_sgd_multi_from_slabs": {"grads": "grads ? grads[s] : NULL", "loss_values": "loss_values != NULL, slk_loss_log("},
+    "slk_sgdm_from_slabs": {"grad": "grad[i] = g (if grad != NULL, before weight decay)"},
+    "slk_sgdm_multi_from_slabs": {"grads": "(the momentum form of", "loss_values": "loss_values != NULL, in ONE launch"},
+    "slk_reduce_sqnorm_multi": {"loss_values": "When loss_values != NULL one more block runs slk_loss_log"},
+    "slk_mnist_batch": {"err_flag": "sets *err_flag (if non-null) and reads image 0. Bit-identical"},
+    "slk_image_batch": {"err_flag": "sets *err_flag (if non-null) and reads image 0 with image 0's draws"},
+    "slk_image_batch_mix": {"err_flag": "behaves like an idx outside it (flag, then row 0 with row 0's draws)"},
+    "slk_image_batch_blend": {"cut_table": "either of which may be NULL (not both)",
+                              "lam_table": "either of which may be NULL (not both)",
+                              "err_flag": "The arguments are slk_image_batch_mix's"},
+    "slk_wide_conv1_fwd": {"a1bits": "a1bits (may be NULL)"},
+    "slk_wide_head_soft": {"err_flag": "the same malformed-target rule"},
+    "slk_adam_from_slabs": {"grad": "grad (if non-null) receives the reduced gradient. Replaces"},
+    "slk_adam_multi_from_slabs": {"grads": "grads may be NULL or hold NULL entries"},
+    "slk_adamw_from_slabs": {"grad": "grad (if non-null) receives the reduced gradient before weight decay"},
+    "slk_adamw_multi_from_slabs": {"grads": "slk_adamw_from_slabs over nseg (<= 4) segments in ONE launch"},
+    "slk_reduce_tnorm_multi": {"loss_values": "When loss_values != NULL pass 1 runs one more block"},
+    "slk_lamb_moments_multi": {"loss_values": "When loss_values != NULL pass 1 runs one more block"},
+    "slk_cut_noise": {"scale": "only where scale is not NULL", "max_norm": "only where max_norm is not NULL",
+                      "stats": "stats may be NULL in slk_cut_noise"},
+}
+# accepted as NULL today although the header does not say so at slk_wide_head (its soft twin's rule does)
+UNDOCUMENTED_OPTIONAL = {"slk_wide_head": {"err_flag"}}
+
+# What a count of 0 with null pointers returns today: these refuse it (1), every other entry launches nothing (0).
+ZERO_IS_REFUSED = {
+    "slk_row_amax", "slk_conv2_fwd_pool_x3", "slk_conv2_dgrad_x3", "slk_conv2_wgrad_x3", "slk_conv2_fwd_pool_x3s",
+    "slk_conv2_wgrad_x3s", "slk_mfma_probe", "slk_conv2_fwd_pool_x3sa", "slk_conv2_fwd_pool_x3i", "slk_loss_sum",
+    "slk_loss_log", "slk_sgdm_from_slabs", "slk_sgdm_multi_from_slabs", "slk_reduce_sqnorm_multi", "slk_sgdm_clip_multi",
+    "slk_mnist_batch", "slk_image_batch", "slk_image_batch_mix", "slk_image_batch_blend", "slk_cut_unpack_x3_parts",
+    "slk_conv2_dgrad_x3_pack_parts", "slk_wide_conv1_fwd", "slk_wide_relu_bits", "slk_wide_conv2_fwd",
+    "slk_wide_conv3_fwd", "slk_wide_head", "slk_wide_head_soft", "slk_wide_head_fwd", "slk_wide_head_bwd",
+    "slk_wide_conv3_wgrad", "slk_wide_conv3_dgrad", "slk_wide_conv2_wgrad", "slk_wide_conv2_dgrad",
+    "slk_wide_conv1_wgrad", "slk_adam_from_slabs", "slk_adam_multi_from_slabs", "slk_adamw_from_slabs",
+    "slk_adamw_multi_from_slabs", "slk_adamw_clip_multi", "slk_reduce_tnorm_multi", "slk_lars_multi",
+    "slk_lamb_moments_multi", "slk_lamb_multi", "slk_ema_multi", "slk_wide_shadows", "slk_wide_fc_shadow", "slk_tick"}
+
+
+def test_optional_pointers_are_documented():
+    src = " ".join(open(os.path.join(ROOT, "include", "slk.h")).read().replace("\n *", " ").split())
+    for entry, ptrs in OPTIONAL_POINTERS.items():
+        for name, words in ptrs.items():
+            assert " ".join(words.split()) in src, (entry, name)
+
+
+def test_every_entry_refuses_null_pointers_and_negative_counts():
+    """tests/abi_sweep.py in a fresh child process to which no device is visible (a missing check then fails at the
+    launch instead of running on null pointers): every entry that takes a pointer returns hipErrorInvalidValue (1)
+    with its counts at -1, with counts at 1 and all pointers null, and with counts at 1 and any one required pointer
+    null among dummies. With every pointer a dummy no entry refuses (so the single null is what was refused), a
+    documented optional pointer may be null, and a count of 0 returns what it returns today."""
+    import json
+    import subprocess
+    import sys
+    from abi_sweep import declarations, pointer_params
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "abi_sweep.py")], env=env, capture_output=True,
+                         text=True, timeout=300)
+    assert run.returncode == 0, f"the sweep ended with status {run.returncode}:\n{run.stderr[-2000:]}"
+    res = json.loads(run.stdout.strip().splitlines()[-1])
+    expected = {name: pointer_params(params) for _, name, params in declarations() if pointer_params(params)}
+    assert set(res) == set(expected) and len(res) >= 94
+    assert set(OPTIONAL_POINTERS) | set(UNDOCUMENTED_OPTIONAL) <= set(res) and ZERO_IS_REFUSED <= set(res)
+    bad = []
+    for entry, ptrs in expected.items():
+        r = res[entry]
+        optional = set(OPTIONAL_POINTERS.get(entry, ())) | UNDOCUMENTED_OPTIONAL.get(entry, set())
+        assert optional <= set(ptrs), entry
+        if r["minus"] != 1:
+            bad.append(f"{entry}: counts at -1 returned {r['minus']}")
+        if r["null"] != 1:
+            bad.append(f"{entry}: counts at 1 and null pointers returned {r['null']}")
+        if r["dummy"] in (0, 1):
+            bad.append(f"{entry}: dummy pointers returned {r['dummy']} (the arguments of the sweep are not legal)")
+        if r["zero"] != (1 if entry in ZERO_IS_REFUSED else 0):
+            bad.append(f"{entry}: a count of 0 returned {r['zero']}")
+        for name in ptrs:
+            got = r["-" + name]
+            if name in optional and got != r["dummy"]:
+                bad.append(f"{entry}: the optional {name} null returned {got}, all dummies {r['dummy']}")
+            if name not in optional and got != 1:
+                bad.append(f"{entry}: {name} null returned {got}")
+    assert not bad, "\n".join(bad)
 
 
 def test_slab_counts_are_functions_of_batch_only():
