@@ -411,7 +411,9 @@ int slk_sgd_multi_from_slabs(float* const* params, float* const* grads, const fl
  * read on the device: lr = lr_table[clamp(*step, 0, lr_len - 1)], where *step is the number of optimizer
  * steps this stage has completed (advance it with slk_tick after the launch). A constant rate is a table of
  * length 1, a torch.optim.lr_scheduler schedule a table of its per-step values (the last one holds past the
- * end); no host value is baked into a captured HIP graph. Per element, g = sum_s slabs[s*n+i] (the three
+ * end); no host value is baked into a captured HIP graph. Valid counter values are 0 <= *step <= 2^31 - 2: the
+ * Adam-type entries form t = *step + 1 as an int, so *step = 2^31 - 1 (INT_MAX) is outside the contract of every
+ * entry that takes `step`, and slk_tick must not be asked to advance a counter past 2^31 - 2. Per element, g = sum_s slabs[s*n+i] (the three
  * summation forms of slk_reduce_slabs); grad[i] = g (if grad != NULL, before weight decay); then
  *   g += weight_decay * p                                         (weight_decay != 0)
  *   buf = (*step == 0) ? g : momentum * buf + (1 - dampening) * g  (momentum != 0; buf may be NULL otherwise)
@@ -948,7 +950,9 @@ int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t
                      uint16_t* w3f, uint16_t* w3d, void* stream);
 /* wf8[j][(plane*64+pix)*8+k] = Wf[j][(plane*8+k)*64+pix]: the fc weight in the cut's C8 order. */
 int slk_wide_fc_shadow(const float* wf, float* wf8, void* stream);
-/* ++*counter on the device (the per-stage step counter a captured HIP graph advances). */
+/* ++*counter on the device (the per-stage step counter a captured HIP graph advances). A step counter stays in
+ * [0, 2^31 - 2] (see slk_sgdm_from_slabs): ticking one that already holds 2^31 - 2 leaves it at INT_MAX, which no
+ * optimizer entry accepts, and one more tick overflows the int. */
 int slk_tick(int* counter, void* stream);
 
 #ifdef __cplusplus

@@ -39,9 +39,11 @@ __device__ __forceinline__ void adam_moments(float t, float& m, float& v, float 
 // sqrt(v) / sqrt(1 - b2^t) + eps
 __device__ __forceinline__ float adam_denom(float v, float bc2s, float eps) { return sqrtf(v) / bc2s + eps; }
 
-// p = p - step_size * m / denom  [addcdiv_]
+// p = p - step_size * m / denom  [addcdiv_]: ONE fused multiply-add, asked for by name. Left to contraction, the
+// fourth segment slot of lamb_multi_kernel merged this line's tail with LAMB's p - fl(r u) into a shared v_sub_f32 and
+// rounded the product on its own, so an excluded bias there missed slk_adamw_from_slabs' bits.
 __device__ __forceinline__ float adam_step(float p, float m, float denom, float step_size) {
-    return p + (-step_size) * (m / denom);
+    return __builtin_fmaf(-step_size, m / denom, p);
 }
 
 // the Adam update of element i from its summed gradient t (shared by the reduction forms)

@@ -245,7 +245,9 @@ def test_adam_multi_bit_identical_to_separate_launches():
         st = WideClientStage(a, device=dev)
         st.fuse_adam = fuse
         stages.append(st)
-    # slab counts on both sides of the 64-slab order switch (the production conv1 set has 512 slabs)
+    # three reduction forms, not one switch: <= 16 slabs sum ascending (1024 columns per block), 17..64 as 4 strided
+    # partials (256 columns), > 64 as 16 strided partials (64 columns). These sets cover the last two (17; 65 and the
+    # production conv1 set's 512); the <= 16 form and every form's update are in tests/test_optim_exact_gpu.py.
     slabs = [torch.randn(n_s, n, device=dev, generator=g) * 1e-3 for n_s, n in ((512, 1792), (17, 73856), (65, 295168))]
     for _ in range(2):  # two steps: the second reads m, v and the step counter the first wrote
         for st in stages:
