@@ -92,7 +92,10 @@ const char* slk_build_id(void);
  *    is 0 (torch's Dropout multiplies by the mask and keeps a NaN), a kept one is an ordinary operand of clause 1.
  *    The cut noise (slk_cut_noise, "Cut noise" below) has no special case: a NaN element makes its sample's s2, coef
  *    and every clipped element NaN, an infinite s2 gives coef = 0 (then 0 x inf = NaN at an infinite element), and
- *    without a clip a non-finite element stays its own; no other sample is touched.
+ *    without a clip a non-finite element stays its own; no other sample is touched. The MX cut records ("MX cut
+ *    records" below) poison by BLOCK, not by sample: a non-finite element makes its 32-element block's scale byte 0xFF
+ *    and the block 32 NaNs on the other side, the sample's other 511 blocks are unchanged (the FP8 records poison the
+ *    whole sample); the head then poisons that sample's logits as for any NaN feature it keeps.
  * The supported check is Python's GraphedTrainer.check_finite() (parameters, optimizer state, averaged blocks). */
 
 /* ---------------------------------------------------------------- client stage (ModelPartA) */
@@ -898,6 +901,52 @@ int slk_cut8_encode_sr(const void* x_bf16, int n, int fmt, void* rec, uint32_t s
                        void* stream);
 int slk_cut8_roundtrip_sr(const void* x_bf16, int n, int fmt, void* out_bf16, uint32_t seed, const int* step, int row0,
                           void* stream);
+/* MX cut records (csrc/slk_cutmx.hip): an opt-in, lossy, block-scaled wire format of the K5 cut and of its gradient
+ * after the OCP Microscaling formats — one E8M0 power-of-two scale per 32 elements and narrow element codes — where
+ * the FP8 records above have one scale per sample. A sample is the 16,384 contiguous bf16 elements of one cut or
+ * cut-gradient row, as in the FP8 records; a block is 32 consecutive elements of the row as stored, 512 blocks a
+ * sample (the codec is elementwise in memory order, so the C8 layout does not matter).
+ * Element formats: fmt 0 = "e2m1" (OCP FP4: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; F_MAX = 6, m = 1, emin = 0; no
+ * NaN or inf code; the code is sign << 3 | exp << 1 | man), fmt 1 = "e4m3" (OCP e4m3fn, exactly the FP8 records'
+ * format 0: F_MAX = 448, m = 3, emin = -6).
+ * Per-block scale: a block with a non-finite element is poisoned: scale byte 0xFF (E8M0's NaN) and all-zero codes.
+ * Otherwise amax = max |x_i| over the block; e = 0 if amax == 0, else e is the smallest integer with
+ * amax * 2^-e <= F_MAX, clamped below at -100 (the FP8 records' clamp, for the same reason: no product ever depends
+ * on float32 subnormal handling). The scale byte is e + 127. Nothing saturates — a deliberate deviation from the
+ * OCP v1.0 suggestion e = floor(log2 amax) - emax_elem, which clips the values between F_MAX * 2^e and 2^(e+1) times
+ * the element format's top binade; the record is still a valid MX block, since any E8M0 scale is — and this keeps the
+ * FP8 records' error bound per block: |x - x^| <= max(|x| * 2^-(m+1), 2^e * 2^(emin-m-1)).
+ * Codes: each code is x_i * 2^-e (an exact float32 product) rounded to nearest even; a zero result keeps the sign of
+ * x_i (e2m1 has a -0 code, 0x8).
+ * Record: u8 [n, R], records contiguous, the base 16-byte aligned; R = 8,720 (e2m1) or 16,912 (e4m3), both multiples
+ * of 16, so a slice of samples is an aligned slice of bytes.
+ *   bytes 0..15     header: uint32 words, little endian: word 0 = 32 (the block length), word 1 = 0x10 + fmt,
+ *                   words 2 and 3 = 0. The format words are disjoint from the FP8 records' (0, 1), so each decoder
+ *                   reports the other's record as malformed.
+ *   bytes 16..527   512 scale bytes, one per block, in block order
+ *   bytes 528..     payload. e2m1: 8,192 bytes, element 2i in bits 0..3 of byte i, element 2i + 1 in bits 4..7.
+ *                   e4m3: 16,384 bytes, one per element.
+ * Decode: x^_i = value(code_i) * 2^e written as bf16 — exact (at most four significant bits, and e >= -100 keeps it
+ * a normal bf16) — with the FP8 records' one exception at the top of bf16's range: a finite code whose product is at
+ * or past 2^128 (amax = 255 * 2^120 rounds to 4 * 2^126 in e2m1, to 256 * 2^120 in e4m3) is written as the largest
+ * finite bf16 of its sign. decode(encode(.)) is idempotent in decoded bits and finite inputs stay finite. A poisoned
+ * block decodes to 32 NaNs (0x7FC0): a non-finite element poisons its block, not its sample. Malformed records: a
+ * wrong header word decodes the whole sample to NaNs and stores err_flag[0] = 1; a scale byte below 27 (e < -100)
+ * decodes that block to 32 NaNs and stores err_flag[0] = 1, the other blocks decode as usual (a plain store; nobody
+ * clears it). An e4m3 NaN code inside a received payload propagates as 0x7FC0.
+ * slk_cutmx_roundtrip is bitwise decode(encode(x)) in one launch with no record in memory; out may equal x.
+ * Order inside a training step (wide.WideTrainer(cut_codec=codec.MxCut(...))): the cut noise if any,
+ * slk_cutmx_roundtrip in the forward format, the head, slk_cutmx_roundtrip in the backward format in place, the
+ * clip's slk_cut_scale_rows if any, the client's backward.
+ * One workgroup of 256 threads per sample, a thread owning two whole blocks: each input byte is read once with
+ * 16-byte loads, every output byte is written by exactly one thread (the scale bytes of four lanes as one word),
+ * without atomics, LDS or barriers. cutmx::* in csrc/slk_cutmx.h is this rule in integer C++ that also compiles for
+ * the host. n == 0 launches nothing and returns 0; n < 0, fmt outside {0, 1}, a NULL pointer or a pointer that is
+ * not 16-byte aligned (err_flag: 4-byte) is refused with hipErrorInvalidValue before any launch. */
+int slk_cutmx_encode(const void* x_bf16, int n, int fmt, void* rec, void* stream);
+int slk_cutmx_decode(const void* rec, int n, int fmt, void* out_bf16, int* err_flag, void* stream);
+int slk_cutmx_roundtrip(const void* x_bf16, int n, int fmt, void* out_bf16, void* stream);
+int64_t slk_cutmx_record_bytes(int fmt); /* 8720 / 16912; -1 for another fmt */
 /* Cut noise (csrc/slk_cut_noise.hip): an opt-in defence of the K5 cut against model inversion — a per-sample norm
  * bound, then additive noise from a 1,024-entry table. An experiment's tool, not a certified mechanism: no epsilon
  * is claimed. A sample is the 16,384 contiguous bf16 elements of one cut row, as in the FP8 records. All float

@@ -121,6 +121,11 @@ _SIGS = {
     "slk_cut8_record_bytes": [],
     "slk_cut8_encode_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
     "slk_cut8_roundtrip_sr": [_P, _I, _I, _P, _U, _P, _I, _P],
+    # block-scaled MX records of the K5 cut and its gradient (codec.MxCut)
+    "slk_cutmx_encode": [_P, _I, _I, _P, _P],
+    "slk_cutmx_decode": [_P, _I, _I, _P, _P, _P],
+    "slk_cutmx_roundtrip": [_P, _I, _I, _P, _P],
+    "slk_cutmx_record_bytes": [_I],
     # per-sample clip + table noise on the K5 cut (privacy.CutNoise)
     "slk_cut_noise": [_P, _I, _P, _F, _P, _P, _U, _P, _I, _P, _P, _P],
     "slk_cut_scale_rows": [_P, _I, _P, _P, _P],
@@ -154,7 +159,8 @@ _SIGS = {
     "slk_tick": [_P, _P],
 }
 _RESTYPES = {"slk_error_string": ctypes.c_char_p, "slk_build_id": ctypes.c_char_p, "slk_conv2_act16_bytes": ctypes.c_int64,
-             "slk_relu_bits_bytes": ctypes.c_int64, "slk_cut8_record_bytes": ctypes.c_int64}
+             "slk_relu_bits_bytes": ctypes.c_int64, "slk_cut8_record_bytes": ctypes.c_int64,
+             "slk_cutmx_record_bytes": ctypes.c_int64}
 
 SYMBOLS = tuple(_SIGS)
 

@@ -20,7 +20,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(PKG_DIR)), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libslk.so")
 SOURCES = ["slk_client.hip", "slk_server.hip", "slk_optim.hip", "slk_data.hip", "slk_wide.hip",
            "slk_wide_head.hip", "slk_wino.hip", "slk_codec.hip", "slk_x3.hip", "slk_eval.hip", "slk_ema.hip",
-           "slk_cut8.hip", "slk_cut_noise.hip"]
+           "slk_cut8.hip", "slk_cut_noise.hip", "slk_cutmx.hip"]
 ARCH = "gfx950"
 # Per-source extra hipcc flags (none needed at present; tools/build_variant.sh passes -D defines).
 EXTRA_FLAGS: dict = {}

@@ -8,7 +8,8 @@ in activations.backward, src/client_part.py:132), so the positions left out neve
 Every weight, loss and gradient downstream is bit-identical to the dense exchange.
 
 The widened model's bf16 cut (K5, wide.py) has a codec of its own, Fp8Cut (csrc/slk_cut8.hip): opt-in and lossy, one
-power-of-two scale per sample and OCP FP8 codes, half the bytes in each direction.
+power-of-two scale per sample and OCP FP8 codes, half the bytes in each direction; and a block-scaled one, MxCut
+(csrc/slk_cutmx.hip): one E8M0 scale per 32 elements and OCP e2m1 / e4m3 codes, 0.27 / 0.52 of the bytes.
 """
 from __future__ import annotations
 
@@ -21,6 +22,9 @@ CUT8_SAMPLE = 16384      # bf16 elements of one K5 cut [256,8,8] or of one cut-g
 CUT8_RECORD = 16400      # bytes of one record: a 16-byte header and one fp8 code per element
 CUT8_FORMATS = {"e4m3": 0, "e5m2": 1}
 CUT8_ROUNDINGS = ("nearest", "stochastic")
+CUTMX_BLOCK = 32         # elements under one scale byte of an MX record
+CUTMX_FORMATS = {"e2m1": 0, "e4m3": 1}
+CUTMX_RECORD = {"e2m1": 8720, "e4m3": 16912}   # a 16-byte header, 512 scale bytes, 4- or 8-bit codes
 
 
 class CutCodec:
@@ -184,9 +188,15 @@ class Fp8Cut:
         if t.data_ptr() % 16:
             raise ValueError(f"{name}: the base address must be 16-byte aligned")
 
-    def records(self, key, n: int, device):
+    def record_bytes(self, direction: str) -> int:
+        """Bytes of one sample's record in "fwd" / "bwd": 16,400 in either format."""
+        self._fmt(direction)
+        return CUT8_RECORD
+
+    def records(self, key, n: int, device, direction=None):
         """The uint8 [n, 16400] record buffer of `key`. Keyed by shape too and never replaced, so a HIP graph
-        captured around the kernels at one size keeps valid pointers after another size has run (CutCodec._buf)."""
+        captured around the kernels at one size keeps valid pointers after another size has run (CutCodec._buf).
+        `direction` is accepted for MxCut's sake and ignored: both formats have one record width."""
         k = (key, int(n), str(torch.device(device)))
         t = self._bufs.get(k)
         if t is None:
@@ -243,8 +253,101 @@ class Fp8Cut:
         return out
 
 
+class MxCut:
+    """Opt-in lossy block-scaled exchange of the widened model's cut (csrc/slk_cutmx.hip; the rule is in
+    include/slk.h, "MX cut records"): one E8M0 power-of-two scale per 32 consecutive elements and OCP codes — "e2m1"
+    (FP4, 8,720 bytes a sample) or "e4m3" (16,912) against the bf16 cut's 32,768. `fwd` is the format of the cut, `bwd`
+    that of the cut gradient; either may be None, which leaves that direction dense bf16. The formats are constructor
+    constants passed to the kernels by value: a captured graph keeps them, and there is no setter. Rounding is to
+    nearest even only (rounding_of is always "nearest"; there is no rounding= parameter).
+
+    A sample is 16,384 contiguous bf16 elements: x / out are [n, ...] with 16,384 elements per row, records are uint8
+    [n, record_bytes(direction)]. The surface is Fp8Cut's: every method works on caller-visible buffers and launches on
+    the tensor's current stream; encode / roundtrip accept and ignore step= / row0= (the hub passes them to every
+    codec)."""
+
+    def __init__(self, fwd="e2m1", bwd="e4m3"):
+        for name, v in (("fwd", fwd), ("bwd", bwd)):
+            if v is not None and v not in CUTMX_FORMATS:
+                raise ValueError(f"MxCut: {name}={v!r}; expected one of {sorted(CUTMX_FORMATS)} or None")
+        if fwd is None and bwd is None:
+            raise ValueError("MxCut: fwd and bwd are both None — that is the dense exchange (pass no codec)")
+        self.fwd, self.bwd = fwd, bwd
+        self._bufs = {}
+
+    def __repr__(self):
+        return f"MxCut(fwd={self.fwd!r}, bwd={self.bwd!r})"
+
+    def rounding_of(self, direction: str) -> str:
+        """The rounding of "fwd" / "bwd": always "nearest"."""
+        self.format(direction)
+        return "nearest"
+
+    def nearest(self) -> "MxCut":
+        """This codec (what evaluation uses): it rounds to nearest already."""
+        return self
+
+    def format(self, direction: str):
+        """The format name of "fwd" / "bwd", or None where that direction stays dense."""
+        if direction not in ("fwd", "bwd"):
+            raise ValueError(f"MxCut: direction {direction!r}; expected 'fwd' or 'bwd'")
+        return self.fwd if direction == "fwd" else self.bwd
+
+    def _name(self, direction: str) -> str:
+        name = self.format(direction)
+        if name is None:
+            raise ValueError(f"MxCut: the {direction} direction is dense (built with {direction}=None)")
+        return name
+
+    def record_bytes(self, direction: str) -> int:
+        """Bytes of one sample's record in "fwd" / "bwd": 8,720 (e2m1) or 16,912 (e4m3)."""
+        return CUTMX_RECORD[self._name(direction)]
+
+    def _records(self, rec, n, direction, name="rec"):
+        _dev(rec, name, (n, self.record_bytes(direction)), torch.uint8)
+        Fp8Cut._aligned(rec, name)
+
+    def records(self, key, n: int, device, direction=None):
+        """The uint8 [n, record_bytes(direction)] record buffer of `key`; `direction` is required: the two directions
+        may have different record widths. Keyed by shape too and never replaced, so a HIP graph captured around the
+        kernels at one size keeps valid pointers after another size has run (CutCodec._buf)."""
+        if direction is None:
+            raise ValueError("MxCut.records: direction= is required ('fwd' or 'bwd')")
+        width = self.record_bytes(direction)
+        k = (key, int(n), width, str(torch.device(device)))
+        t = self._bufs.get(k)
+        if t is None:
+            t = torch.empty((int(n), width), dtype=torch.uint8, device=device)
+            self._bufs[k] = t
+        return t
+
+    def encode(self, x, rec, direction: str = "fwd", step=None, row0: int = 0):
+        """x (bf16 [n, ...]) -> rec (uint8 [n, record_bytes(direction)]) in `direction`'s format."""
+        fmt, n = CUTMX_FORMATS[self._name(direction)], Fp8Cut._rows(x, "x")
+        self._records(rec, n, direction)
+        _lib.call("slk_cutmx_encode", x.data_ptr(), n, fmt, rec.data_ptr(), _stream(x))
+        return rec
+
+    def decode(self, rec, out, err_flag, direction: str = "fwd"):
+        """rec -> out (bf16 [n, ...]); a malformed header decodes its sample to NaNs, a scale byte below 27 its block,
+        and either sets err_flag (int32 [1]); a poisoned block (scale byte 0xFF) decodes to 32 NaNs without the flag."""
+        fmt, n = CUTMX_FORMATS[self._name(direction)], Fp8Cut._rows(out, "out")
+        self._records(rec, n, direction)
+        _dev(err_flag, "err_flag", (1,), torch.int32)
+        _lib.call("slk_cutmx_decode", rec.data_ptr(), n, fmt, out.data_ptr(), err_flag.data_ptr(), _stream(out))
+        return out
+
+    def roundtrip(self, x, out, direction: str, step=None, row0: int = 0):
+        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x."""
+        fmt, n = CUTMX_FORMATS[self._name(direction)], Fp8Cut._rows(x, "x")
+        if Fp8Cut._rows(out, "out") != n:
+            raise ValueError(f"out: expected {n} samples like x, got {out.shape[0]}")
+        _lib.call("slk_cutmx_roundtrip", x.data_ptr(), n, fmt, out.data_ptr(), _stream(x))
+        return out
+
+
 def check_cut_codec(codec):
-    """A trainer's / hub's codec argument: an Fp8Cut or None."""
-    if codec is not None and not isinstance(codec, Fp8Cut):
-        raise TypeError(f"expected splitcnn.codec.Fp8Cut or None, got {type(codec).__name__}")
+    """A trainer's / hub's codec argument: an Fp8Cut, an MxCut or None."""
+    if codec is not None and not isinstance(codec, (Fp8Cut, MxCut)):
+        raise TypeError(f"expected splitcnn.codec.Fp8Cut, splitcnn.codec.MxCut or None, got {type(codec).__name__}")
     return codec

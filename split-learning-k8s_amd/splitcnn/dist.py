@@ -856,7 +856,9 @@ class WideHub:
     Stages: client.forward(x, tag) / backward_grads(dcut, tag, accumulate) / step_from_grads / grads /
     cut_shape / cut_dtype; server.accumulate(cut, labels, scale, b0, k, nparts, dcut) / finish_step.
 
-    codec (codec.Fp8Cut, opt-in and lossy; both sides must be built with the same formats): each part travels as
+    codec (codec.Fp8Cut or codec.MxCut, opt-in and lossy; both sides must be built with the same formats; an MxCut
+    travels as MX records of 8,720 / 16,912 B/sample, include/slk.h "MX cut records", always rounded to nearest, and
+    everything below holds for it with that record): each part travels as
     FP8 records (16,400 B/sample, include/slk.h "FP8 cut records") in every direction whose format is not None —
     the sender encodes the part into one uint8 tensor, the receiver decodes it where the dense tensor would have
     landed (the server into its `cuts` slice before accumulate; it encodes each `dcuts` slice before sending) — so
@@ -887,8 +889,8 @@ class WideHub:
             self.codec = check_cut_codec(codec)
             device = torch.device(getattr(stage, "device", "cpu"))
             if device.type != "cuda":
-                raise ValueError("WideHub(codec=...): the FP8 cut codec runs as HIP kernels on CUDA tensors; the stage "
-                                 f"is on {device} — pass no codec (on BOTH sides) for CPU stages")
+                raise ValueError(f"WideHub(codec=...): the {self._codec_name()} cut codec runs as HIP kernels on CUDA "
+                                 f"tensors; the stage is on {device} — pass no codec (on BOTH sides) for CPU stages")
             self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.noise = None
         if noise is not None:
@@ -918,19 +920,26 @@ class WideHub:
             self._bufs[key] = t
         return t
 
+    def _codec_name(self) -> str:
+        from .codec import MxCut
+        return "MX" if isinstance(self.codec, MxCut) else "FP8"
+
     def _fp8(self, direction) -> bool:
+        """Whether `direction` travels as records (FP8 or MX) instead of dense bf16."""
         return self.codec is not None and self.codec.format(direction) is not None
 
     def _count_bytes(self, n: int, dense_per_sample: int):
         """The last step's bytes on this rank's links for n samples: each direction's cut payload + the labels."""
-        from .codec import CUT8_RECORD
-        per = sum(CUT8_RECORD if self._fp8(d) else dense_per_sample for d in ("fwd", "bwd"))
+        per = sum(self.codec.record_bytes(d) if self._fp8(d) else dense_per_sample for d in ("fwd", "bwd"))
         self.exchange_bytes = n * per + n * 8
         self.dense_bytes = 2 * n * dense_per_sample + n * 8
 
     def check_exchange(self):
         """Raise if any record this rank decoded so far was malformed (one host sync)."""
         if self.err_flag is not None and int(self.err_flag.item()) != 0:
+            if self._codec_name() == "MX":
+                raise RuntimeError("dist.WideHub: a received MX cut record was malformed (a wrong header word, or a "
+                                   "scale byte below 27); its sample or block was decoded to NaNs")
             raise RuntimeError("dist.WideHub: a received FP8 cut record was malformed (wrong format word, nonzero "
                                "reserved bytes or an exponent out of range); its sample was decoded to NaNs")
 
@@ -952,11 +961,12 @@ class WideHub:
                 cut = nz.apply(cut, self._buf(("cut_n", k), tuple(cut.shape), cut.dtype, x.device), step=c.step_ctr,
                                row0=self.rank * B + k * b, stats=stats[k])
             if f8:
-                cut = q.encode(cut, q.records(("fwd", k), b, x.device), "fwd", step=c.step_ctr, row0=self.rank * B + k * b)
+                cut = q.encode(cut, q.records(("fwd", k), b, x.device, direction="fwd"), "fwd", step=c.step_ctr,
+                               row0=self.rank * B + k * b)
             sends.append(isend(cut, self.server_rank, fw))
             sends.append(isend(y[sl], self.server_rank, fw))
         for k in range(m):
-            grecs.append(q.records(("bwd", k), b, x.device) if b8 else dcut[k * b:(k + 1) * b])
+            grecs.append(q.records(("bwd", k), b, x.device, direction="bwd") if b8 else dcut[k * b:(k + 1) * b])
             recvs.append(irecv(grecs[k], self.server_rank, bw))
         for k in range(m):
             recvs[k].wait()
@@ -987,7 +997,7 @@ class WideHub:
         for c in range(nc):
             for k in range(m):
                 sl = slice(c * B + k * b, c * B + (k + 1) * b)
-                recs[c, k] = q.records(("fwd", c, k), b, device) if f8 else cuts[sl]
+                recs[c, k] = q.records(("fwd", c, k), b, device, direction="fwd") if f8 else cuts[sl]
                 reqs[c, k] = (irecv(recs[c, k], c, fw), irecv(labels[sl], c, fw))
         sends, part = [], 0
         for k in range(m):
@@ -999,8 +1009,8 @@ class WideHub:
                     q.decode(recs[c, k], cuts[sl], self.err_flag, "fwd")
                 b0 = c * B + k * b
                 s.accumulate(cuts[sl], labels[sl], 1.0 / G, b0, part, m * nc, dcut=dcuts[sl])
-                out = (q.encode(dcuts[sl], q.records(("bwd", c, k), b, device), "bwd", step=s.step_ctr, row0=b0)
-                       if b8 else dcuts[sl])
+                out = (q.encode(dcuts[sl], q.records(("bwd", c, k), b, device, direction="bwd"), "bwd", step=s.step_ctr,
+                                row0=b0) if b8 else dcuts[sl])
                 sends.append(isend(out, c, bw))
                 part += 1
         s.finish_step(m * nc, step=self.global_step)

@@ -24,7 +24,7 @@ there is no CPU path. Activations live in HBM in the C8 layout [B][C/8][H][W][8]
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Union
 
 import numpy as np
 import torch
@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
-from .codec import Fp8Cut, check_cut_codec
+from .codec import Fp8Cut, MxCut, check_cut_codec
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
@@ -653,7 +653,9 @@ class WideTrainer(GraphedTrainer):
     cut under the client's step_ctr, the cut gradient under the server's, each read before its stage's tick (the
     gradient is rounded between the head and the server's Adam), so load_optimizer_state reproduces the bits and
     the step stays dist.WideHub(codec=...)'s. Evaluation and prediction round the cut to nearest whatever the
-    training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd).
+    training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd). A codec.MxCut
+    in the same place runs the block-scaled exchange (include/slk.h, "MX cut records") the same way: two
+    slk_cutmx_roundtrip launches at the same two places, always to nearest, evaluation and prediction included.
 
     `cut_noise` (privacy.CutNoise) puts a noise defence on the cut, inside the captured step: the cut is clipped per
     sample and noised (slk_cut_noise) into the server-stage buffer `cut_n` under the client's step_ctr with row0 = 0,
@@ -672,7 +674,7 @@ class WideTrainer(GraphedTrainer):
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
                  loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
-                 cut_codec: Optional[Fp8Cut] = None, cut_noise: Optional[CutNoise] = None):
+                 cut_codec: Union[Fp8Cut, MxCut, None] = None, cut_noise: Optional[CutNoise] = None):
         check_clip(clip)
         check_ema(ema)
         self.cut_codec = check_cut_codec(cut_codec)
@@ -697,7 +699,7 @@ class WideTrainer(GraphedTrainer):
         if step is None:
             q = q.nearest()
         out = self.server._b(name, tuple(t.shape), _BF) if name is not None else t
-        with TIMER("cut8_roundtrip"):
+        with TIMER("cutmx_roundtrip" if isinstance(q, MxCut) else "cut8_roundtrip"):
             if q.rounding_of(direction) == "stochastic":
                 return q.roundtrip(t, out, direction, step=step)
             return q.roundtrip(t, out, direction)   # today's call, argument for argument
