@@ -66,7 +66,8 @@ def encode_relu_bits(mask):
     return w.to(torch.int32).reshape(B, 676).contiguous()
 
 
-def _exact_case(gpu, B, seed, narrow=False, small_grad=False):
+def _exact_case(gpu, B, seed, narrow=False, small_grad=False, relu_p=0.25):
+    """relu_p: the density of the ReLU bits (the last draw, so every other operand is the same at any value)."""
     g = torch.Generator().manual_seed(seed)
     if narrow:
         act = _sparse(g, (B, 32, 26, 26), 0.15, 1, 3)
@@ -76,7 +77,7 @@ def _exact_case(gpu, B, seed, narrow=False, small_grad=False):
     dp = _ints(g, (B, 64, 12, 12), -3, 3) if small_grad else _ints(g, (B, 64, 12, 12), -15, 15)
     code = torch.randint(0, 5, (B, 64, 12, 12), generator=g).to(torch.uint8)
     x = _sparse(g, (B, 1, 28, 28), 0.25, -1, 1)
-    relu = torch.rand((B, 32, 26, 26), generator=g) < 0.25
+    relu = torch.rand((B, 32, 26, 26), generator=g) < relu_p
     c = dict(act=act, W2=W2, b2=b2, dp=dp, code=code, x=x, relu=relu)
     c = {k: v.to(gpu).contiguous() for k, v in c.items()}
     for k in ("act", "W2", "b2", "dp", "x"):         # integers of at most 11 significant bits: exact f16 values

@@ -23,7 +23,8 @@ Mixed exponents (weight gradient): sample b's act is multiplied by 2^ka[b], its 
 and kd = (1, 0, 2) by b mod 3: three values of each in a batch, a total spread of 4 binades, and neighbouring
 samples always differ in both. A K share of either kernel holds 2 to 4 units of 3 (or 6) a sample at B = 130, so at
 most two samples: every share that spans two samples mixes two scales of each operand (three distinct values cannot
-meet in one share at this batch). This is the only exact check of the dY compensation.
+meet in one share at this batch; tests/test_steady_exact_gpu.py runs the same variant at B = 171 to 342, where three
+do). These two files hold the only exact checks of the dY compensation.
 
 Images: real-valued operands (randn-based ReLU outputs at per-sample magnitudes from 1e-3 to 1e3, SyntheticMNIST
 through conv1) with planted elements in every sample - exact ties both ways, an l that is subnormal in f16, an
@@ -139,7 +140,8 @@ def relu_density(B):
     return min(0.25, 8.0 / (676 * B))
 
 
-def dgrad_case(cls, B, seed, dev):
+def dgrad_case(cls, B, seed, dev, special=False):
+    """special: sample 1 is blocked everywhere and sample 2 has a single routed window (drawn operands unchanged)."""
     g = torch.Generator().manual_seed(seed)
     d_shape, w_shape = (B, 64, 12, 12), (64, 32, 3, 3)
     if cls == "dp14":
@@ -151,6 +153,9 @@ def dgrad_case(cls, B, seed, dev):
     else:
         dp, W2 = gen_both(g, d_shape, 0.3, True), gen_both(g, w_shape, 0.3, True)
     code = torch.randint(0, 5, d_shape, generator=g).to(torch.uint8)
+    if special:
+        code[1:3] = 4
+        code[2, 17, 5, 7] = 2
     x = gen_small(g, (B, 1, 28, 28), 0.25, [1], True)
     relu = torch.rand((B, 32, 26, 26), generator=g) < relu_density(B)
     cut = torch.randn((B, 32, 26, 26), generator=g).clamp_min(0.0)            # its zero pattern is the codec mask
@@ -210,12 +215,18 @@ def test_x3_dgrad_lo_exact(gpu, cls, B):
 KA, KD = (0, 2, 1), (1, 0, 2)
 
 
-def wgrad_case(cls, B, seed, dev):
-    g = torch.Generator().manual_seed(seed)
-    a_shape, d_shape = (B, 32, 26, 26), (B, 64, 12, 12)
+def wgrad_densities(cls, B):
     pa, pd = (0.15, 0.3) if B <= 5 else (0.05, 0.05)
     if B > 5 and cls in ("dp14", "mixed_dp"):
         pd = 0.02          # db2 adds 14-bit values themselves: 0.05 x 2^kd reaches 2^24.5 granules at B = 130
+    return pa, pd
+
+
+def wgrad_case(cls, B, seed, dev, densities=None):
+    """densities: (act, dpooled) nonzero probabilities; default wgrad_densities(cls, B)."""
+    g = torch.Generator().manual_seed(seed)
+    a_shape, d_shape = (B, 32, 26, 26), (B, 64, 12, 12)
+    pa, pd = wgrad_densities(cls, B) if densities is None else densities
     if cls in ("act14", "mixed_act"):
         act, dp = gen14(g, a_shape, pa, False), gen_small(g, d_shape, pd, [1], True)
     elif cls in ("dp14", "mixed_dp"):
