@@ -993,6 +993,53 @@ int slk_cut_noise(const void* x_bf16, int n, const float* table, float tail, con
                   const float* max_norm, uint32_t seed, const int* step, int row0, void* out_bf16, float* stats,
                   void* stream);
 int slk_cut_scale_rows(const void* x_bf16, int n, const float* stats, void* out_bf16, void* stream);
+/* Distance correlation (csrc/slk_dcor.hip): how much of the raw input the cut still carries, as one number — the
+ * sample distance correlation of Szekely, Rizzo and Bakirov 2007 between x and z, the quantity NoPeek reports: 0 for
+ * independent samples, 1 where z is a similarity transform of x. A metric only: there is no gradient.
+ * Inputs: x float32 [n, dx] and z bf16 [n, dz], contiguous, one sample per row, 16-byte aligned, dx and dz
+ * multiples of 64. The K5 case is dx = 3072 (the image) and dz = 16,384 (the cut as stored: its C8 layout permutes
+ * the row, which leaves Euclidean distances alone).
+ * Distances: a_ij = |x_i - x_j| and b_ij = |z_i - z_j| from Gram blocks, in float32:
+ *   s_i  = sum_k x_ik^2, summed in float64 and rounded once to float32 (a pre-pass; likewise for z)
+ *   g_ij = sum_k x_ik x_jk on the matrix cores, float32 accumulation: x enters v_mfma_f32_32x32x2_f32 as stored, z
+ *          enters v_mfma_f32_32x32x16_bf16 as stored; an accumulator chain runs over 16 chunks of 128 bytes per
+ *          row (512 floats / 1024 bf16) and the chains are added up in float32, in K order
+ *   d2   = fl(fl(s_i + s_j) - 2 g_ij), set to 0 where d2 <= fl(tau * fl(s_i + s_j)) (the resolution rule; it also
+ *          clamps a negative d2), d = sqrt(d2); d_ii = 0 exactly.
+ * The resolution rule is a stated deviation from the textbook statistic: a float32 Gram matrix cannot resolve a
+ * squared distance below its own accumulation error, and without the rule a batch of identical rows would give a
+ * ratio of two rounding noises instead of 0. tau is one constant per operand, slk_dcor_tau(which) in units of 2^-24
+ * (which = 0: x, 1: z; -1 for another), derived as the worst case of this K order, charged as ONE chain (splitting
+ * it only shortens the path of a product to the result): with u = 2^-24, a chain of K float32 accumulations errs by at most K u sum_k |x_ik x_jk| <= K u (s_i + s_j) / 2 to first order (the bf16 MFMA
+ * adds 16 exact products per instruction in an order the hardware does not state: every product is charged one
+ * rounding per product that follows it, the same K); 2 g carries twice that; s_i and s_j add u / 2 each relative,
+ * the sum and the difference one rounding each, and the second-order terms stay below 16 u at K = 16,384. So
+ * |d2 - true| <= (K + 19) u (s_i + s_j), and tau = (K + 128) u with the K of the K5 operands: 3200 * 2^-24 for x and
+ * 16512 * 2^-24 for z. Longer rows are accepted, but the constant is then no longer their worst case.
+ * Statistic (the biased, V-statistic form, as in NoPeek), with ra_i = sum_j a_ij, Ta = sum_i ra_i, Sab = sum_ij a_ij b_ij:
+ *   dCov2(x, z) = Sab / n^2 - 2 sum_i ra_i rb_i / n^3 + Ta Tb / n^4        (dVar: the same with b = a)
+ *   dCor = sqrt(max(dCov2, 0) / sqrt(dVar_x dVar_z)), 0 where the product of the variances is <= 0
+ * Every sum of distances is float64 from the float32 distance on (the products a b, a a, b b are exact in float64):
+ * inside a pair tile in registers, across the tiles and in the closed form on the device, in one fixed order and
+ * without atomics, so the same inputs give the same bits on every run. (A float32 tile partial would carry 2^-25 of
+ * itself, which does not average out over a few tiles the way the per-pair errors do over n^2 pairs.)
+ * out4 = (dcor, dcov2, dvar_x, dvar_z) as float32. A NaN or +-inf anywhere in x or z makes all four NaN: the finish
+ * adds 0 * (sum_i s_x[i] + s_z[i]) to each output, and a non-finite element makes its row's s NaN or inf (so does a
+ * row whose square norm overflows float32).
+ * Kernels: the square norms (one block per row); the pair tiles — one block of 256 threads per 128 x 128 tile with
+ * tj >= ti, T (T + 1) / 2 blocks for T = ceil(n / 128), both K loops over the same accumulators (x first, turned into
+ * a_ij in registers, then z), operands staged through double-buffered LDS, a diagonal tile staging its rows once, an
+ * off-diagonal tile counting twice in the three sums and feeding the row sums on both sides; rows at or past n are
+ * read from row n - 1 and masked by a select —; the finish (one block). Every workspace slot that is read has
+ * exactly one writer.
+ * slk_dcor_workspace_bytes(n) is the size of the workspace slk_dcor needs (-1 for n < 0); its contents before the
+ * call do not matter. n == 0 launches nothing and returns 0; n == 1 writes four zeros and reads neither x nor z
+ * (one sample has no pairs, so dx and dz are not looked at). Refused with hipErrorInvalidValue before any launch:
+ * a negative n, dx or dz; a NULL x, z_bf16, workspace or out4; any of the four not 16-byte aligned; for n >= 2 a dx
+ * or dz that is 0 or not a multiple of 64, and an n with more than 2^31 - 1 tiles. */
+int slk_dcor_tau(int which);
+int64_t slk_dcor_workspace_bytes(int n);
+int slk_dcor(const float* x, int dx, const void* z_bf16, int dz, int n, void* workspace, float* out4, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -1035,3 +1035,18 @@ def wide_head_soft(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale,
               _dev(slabs, "slabs"), _dev(work, "work"),
               _err_ptr(err_flag), int(b0), B, _stream(cut))
     return dcut, loss_i, slabs
+
+
+# ------------------------------------------------------------------------------------ distance correlation
+def dcor_workspace_bytes(n: int) -> int:
+    """Bytes of the workspace slk_dcor needs for n samples."""
+    return _lib.query("slk_dcor_workspace_bytes", int(n))
+
+
+def dcor(x, z, workspace, out):
+    """out (f32 [4]) = (dcor, dcov2, dvar_x, dvar_z) of x (f32 [n, dx]) and z (bf16 [n, dz]) — slk_dcor; every
+    buffer is the caller's (privacy.distance_correlation checks and caches them)."""
+    n, dx, dz = int(x.shape[0]), int(x.shape[1]), int(z.shape[1])
+    _lib.call("slk_dcor", _dev(x, "x", (n, dx)), dx, _dev(z, "z", (n, dz), torch.bfloat16), dz, n,
+              _dev(workspace, "workspace", dtype=torch.uint8), _dev(out, "out", (4,)), _stream(x))
+    return out

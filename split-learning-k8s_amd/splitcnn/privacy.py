@@ -15,7 +15,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _dev, _stream
 
 NOISE_SAMPLE = 16384        # bf16 elements of one K5 cut [256,8,8] or of one cut-gradient row
@@ -240,3 +240,91 @@ def check_cut_noise(noise):
     if noise is not None and not isinstance(noise, CutNoise):
         raise TypeError(f"expected splitcnn.privacy.CutNoise or None, got {type(noise).__name__}")
     return noise
+
+
+# ------------------------------------------------------------------------------------ what a defence buys
+class DistanceCorrelation:
+    """The four numbers of one distance_correlation call: dcor, dcov2, dvar_x, dvar_z (Python floats). They are read
+    back from the device on first access, with one host sync (like WideTrainer.cut_stats); `values` is the f32 [4]
+    device tensor itself, in that order, for a caller that stays on the device (inside a graph capture)."""
+
+    _FIELDS = ("dcor", "dcov2", "dvar_x", "dvar_z")
+
+    def __init__(self, values: torch.Tensor):
+        self.values = values
+        self._host = None
+
+    def __getattr__(self, name):
+        if name in DistanceCorrelation._FIELDS:
+            if self._host is None:
+                self._host = tuple(float(v) for v in self.values.cpu())
+            return self._host[DistanceCorrelation._FIELDS.index(name)]
+        raise AttributeError(name)
+
+    def __repr__(self):
+        return "DistanceCorrelation(" + ", ".join(f"{k}={getattr(self, k):.6g}" for k in self._FIELDS) + ")"
+
+
+_DCOR_WORKSPACES: dict = {}
+
+
+def dcor_tau(which: str) -> float:
+    """The resolution constant of an operand ("x" or "z"): a squared distance at or below tau * (s_i + s_j) counts as
+    0 (include/slk.h, "Distance correlation")."""
+    return _lib.query("slk_dcor_tau", {"x": 0, "z": 1}[which]) * 2.0 ** -24
+
+
+def _dcor_width(t, name, dtype) -> int:
+    """Elements per sample of t, after the rules that need no device: dtype, [n, ...], a multiple of 64."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() < 2:
+        raise ValueError(f"{name}: expected [n, ...] with at least 2 dimensions, got {tuple(t.shape)}")
+    d = int(np.prod(t.shape[1:]))
+    if d == 0 or d % 64:
+        raise ValueError(f"{name}: {d} elements per sample; expected a positive multiple of 64")
+    return d
+
+
+def _dcor_rows(t, name, d):
+    """t as [n, d] once it is on a device, contiguous and 16-byte aligned."""
+    _dev(t, name, dtype=t.dtype)
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name}: the base address must be 16-byte aligned")
+    return t.view(t.shape[0], d)
+
+
+def distance_correlation(x, z, out=None) -> DistanceCorrelation:
+    """The sample distance correlation between the raw inputs x (float32 [n, ...]) and the cut z (bf16 [n, ...]), both
+    flattened per sample to a multiple of 64 elements: slk_dcor, the biased (V-statistic) form that NoPeek reports,
+    with Gram-based float32 distances and the resolution rule of include/slk.h. 0 means independent, 1 a similarity
+    transform. A metric only — nothing here is differentiable.
+
+    Three launches on x's current stream, no host sync (the result object syncs on first access) and no allocation
+    once the workspace for this (device, n) exists, so a call can be captured in a HIP graph: pass out= (f32 [4]) then
+    and read result.values after a replay. For a noisy cut, apply your own CutNoise first and pass its output."""
+    dx, dz = _dcor_width(x, "x", torch.float32), _dcor_width(z, "z", torch.bfloat16)
+    x2, z2 = _dcor_rows(x, "x", dx), _dcor_rows(z, "z", dz)
+    n = int(x2.shape[0])
+    if int(z2.shape[0]) != n:
+        raise ValueError(f"z: expected {n} samples like x, got {z2.shape[0]}")
+    if z.device != x.device:
+        raise ValueError(f"z: on {z.device}, x is on {x.device}")
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=x.device)
+    else:
+        _dev(out, "out", (4,), torch.float32)
+        if out.device != x.device:
+            raise ValueError(f"out: on {out.device}, x is on {x.device}")
+        if out.data_ptr() % 16:
+            raise ValueError("out: the base address must be 16-byte aligned")
+    if n == 0:
+        raise ValueError("distance_correlation: an empty batch has no statistic")
+    key = (x.device, n)
+    ws = _DCOR_WORKSPACES.get(key)
+    if ws is None:
+        ws = _DCOR_WORKSPACES[key] = torch.empty(ops.dcor_workspace_bytes(n), dtype=torch.uint8, device=x.device)
+    ops.dcor(x2, z2, ws, out)
+    return DistanceCorrelation(out)

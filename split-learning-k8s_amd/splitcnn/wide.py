@@ -38,7 +38,7 @@ from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
 from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema
-from .privacy import CutNoise, check_cut_noise
+from .privacy import CutNoise, check_cut_noise, distance_correlation
 from .recipe import Seg, StageRecipe, _flatten_params
 
 P_DROP = 0.25
@@ -778,6 +778,18 @@ class WideTrainer(GraphedTrainer):
         self.eval_cut = self.client.forward(x, tag="eval", ema=ema)   # the last evaluation's cut (a stage buffer)
         cut = self._wire(self._noised(self.eval_cut, "eval_cut_n"), "fwd", "eval_cut_q")
         return self.server.evaluate(cut, y, metrics=metrics, ema=ema)
+
+    def cut_leakage(self, x, weights: str = "live"):
+        """privacy.distance_correlation between the batch x and the cut a server would receive for it: the client
+        forward as in evaluation, the clip of cut_noise= WITHOUT noise and the codec's nearest rounding if one is set.
+        It touches no training state. For a noisy cut, run your own CutNoise.apply on eval_cut and call
+        privacy.distance_correlation yourself. weights="ema": on the averaged weights."""
+        ema = self._check_weights(weights)
+        if tuple(x.shape[1:]) != self.input_shape:
+            raise ValueError(f"cut_leakage: expected x [B,{','.join(map(str, self.input_shape))}], got {tuple(x.shape)}")
+        self.eval_cut = self.client.forward(x, tag="eval", ema=ema)
+        cut = self._wire(self._noised(self.eval_cut, "eval_cut_n"), "fwd", "eval_cut_q")
+        return distance_correlation(x, cut)
 
     def predict(self, x, return_logits: bool = False, weights: str = "live"):
         """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
