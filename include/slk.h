@@ -995,7 +995,7 @@ int slk_cut_noise(const void* x_bf16, int n, const float* table, float tail, con
 int slk_cut_scale_rows(const void* x_bf16, int n, const float* stats, void* out_bf16, void* stream);
 /* Distance correlation (csrc/slk_dcor.hip): how much of the raw input the cut still carries, as one number — the
  * sample distance correlation of Szekely, Rizzo and Bakirov 2007 between x and z, the quantity NoPeek reports: 0 for
- * independent samples, 1 where z is a similarity transform of x. A metric only: there is no gradient.
+ * independent samples, 1 where z is a similarity transform of x. The metric alone; its gradient is slk_dcor_grad below.
  * Inputs: x float32 [n, dx] and z bf16 [n, dz], contiguous, one sample per row, 16-byte aligned, dx and dz
  * multiples of 64. The K5 case is dx = 3072 (the image) and dz = 16,384 (the cut as stored: its C8 layout permutes
  * the row, which leaves Euclidean distances alone).
@@ -1040,6 +1040,44 @@ int slk_cut_scale_rows(const void* x_bf16, int n, const float* stats, void* out_
 int slk_dcor_tau(int which);
 int64_t slk_dcor_workspace_bytes(int n);
 int slk_dcor(const float* x, int dx, const void* z_bf16, int dz, int n, void* workspace, float* out4, void* stream);
+/* Distance correlation gradient (csrc/slk_dcor.hip): the NoPeek term of Vepakomma et al. on the cut,
+ *   out = dcut + alpha * d dCor^2(x, z) / d z      (squared = 1; squared = 0 differentiates dCor itself),
+ * client-local: x, z, dcut and out are the client's own buffers, z [n, dz] bf16 the raw cut, dcut / out bf16 of z's
+ * shape (out may be dcut). With the notation above, R^2 = C / sqrt(Vx Vz) (C = dCov2, Vx, Vz the variances),
+ *   Abar_ij = a_ij - ra_i / n - ra_j / n + Ta / n^2  (Bbar likewise),  C = sum Abar b / n^2,  Vz = sum Bbar b / n^2,
+ *   u_ij = (Abar_ij - (C / Vz) Bbar_ij) / b_ij  where b_ij > 0, else 0 (the diagonal and unresolved pairs),
+ *   d R^2 / d z_i = c1 sum_j u_ij (z_i - z_j),  c1 = 2 / (n^2 sqrt(Vx Vz)),
+ * and the gradient of R is that times 1 / (2 R). The rule inherits the metric's three deviations: the biased
+ * (V-statistic) form, float32 Gram-based distances, and the resolution rule (a pair it sets to 0 carries no weight).
+ * Where the metric's closed form clamps (Vx Vz <= 0 or C <= 0) the term is exactly 0 and out holds dcut's bits.
+ * Launches, on one stream, without atomics, host syncs or allocation; the same inputs give the same bits:
+ *   1-3  slk_dcor's three, out4 written as slk_dcor writes it; the tile kernel's second instantiation also stores its
+ *        float32 a and b tiles (upper triangle of 128 x 128 tiles, in the kernel's own register order).
+ *   4    coefficients, one block, float64: ra_i / n, rb_i / n, Ta / n^2, Tb / n^2, C / Vz from the finish kernel's sums
+ *        in its order, and f = *alpha * c1 (times 1 / (2 R) for squared = 0), 0 where the form clamps, plus the
+ *        metric's poison term 0 * sum_i (s_x[i] + s_z[i]): NaN for any NaN or +-inf in x or z. f is then rounded once
+ *        to float32. alpha is a device f32[1] read at run time, so a captured graph follows it.
+ *   5    weights, one block per stored tile: u_ij = (Abar - (C / Vz) Bbar) / b in float64 from the float32 distances,
+ *        Abar = fl(fl(fl(a - ra_i / n) - ra_j / n) + Ta / n^2), rounded ONCE to bf16, written as the tile and its
+ *        transpose into the row-major bf16 U[Np][Np], Np = 128 ceil(n / 128); rows and columns at or past n are zeros.
+ *        The row sums ru_i = sum_j U[i][j] are sums of the STORED bf16 values in float64: inside a tile over its
+ *        columns ascending, across the tiles of a row ascending, then rounded once to float32. So the result is
+ *        exactly sum_j u^_ij (z_i - z_j) for the rounded weights u^: bf16 perturbs each weight relatively and adds no
+ *        cancellation error.
+ *   6    product and epilogue: acc_ik = sum_j U[i][j] z_jk on v_mfma_f32_32x32x16_bf16, one float32 accumulator chain
+ *        over j ascending in chunks of 16 (the order inside an instruction is the hardware's), then
+ *          out_ik = bf16_rne(fmaf(f, fmaf(ru_i, (float)z_ik, -acc_ik), (float)dcut_ik)),
+ *        and dcut_ik's own bits where f == 0. Rows at or past n are not written; a non-finite input makes every
+ *        output element NaN through f.
+ * Workspace: slk_dcor_grad_workspace_bytes(n) (-1 for n < 0), contents before the call do not matter. It holds the one
+ * n x n matrix of this feature, U (2 Np^2 bytes: 32 MiB at n = 4096), and the two float32 tile stores (2 x 64 KiB per
+ * tile: 66 MiB at n = 4096). n == 0 launches nothing and returns 0; n == 1 copies dcut to out (dz elements) and
+ * writes four zeros. Refused with hipErrorInvalidValue before any launch: a negative n, dx or dz; squared outside
+ * {0, 1}; a NULL x, z_bf16, dcut_bf16, alpha, workspace, out_bf16 or out4; any of them not 16-byte aligned (alpha: 4);
+ * for n >= 2 a dx or dz that is 0 or not a multiple of 64, and n above 128 * 65535. */
+int64_t slk_dcor_grad_workspace_bytes(int n);
+int slk_dcor_grad(const float* x, int dx, const void* z_bf16, int dz, int n, const void* dcut_bf16, const float* alpha,
+                  int squared, void* workspace, void* out_bf16, float* out4, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

@@ -133,6 +133,9 @@ _SIGS = {
     "slk_dcor_tau": [_I],
     "slk_dcor_workspace_bytes": [_I],
     "slk_dcor": [_P, _I, _P, _I, _I, _P, _P, _P],
+    # its gradient on the cut (privacy.DcorLoss)
+    "slk_dcor_grad_workspace_bytes": [_I],
+    "slk_dcor_grad": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)
@@ -164,7 +167,8 @@ _SIGS = {
 }
 _RESTYPES = {"slk_error_string": ctypes.c_char_p, "slk_build_id": ctypes.c_char_p, "slk_conv2_act16_bytes": ctypes.c_int64,
              "slk_relu_bits_bytes": ctypes.c_int64, "slk_cut8_record_bytes": ctypes.c_int64,
-             "slk_cutmx_record_bytes": ctypes.c_int64, "slk_dcor_workspace_bytes": ctypes.c_int64}
+             "slk_cutmx_record_bytes": ctypes.c_int64, "slk_dcor_workspace_bytes": ctypes.c_int64,
+             "slk_dcor_grad_workspace_bytes": ctypes.c_int64}
 
 SYMBOLS = tuple(_SIGS)
 

@@ -1050,3 +1050,20 @@ def dcor(x, z, workspace, out):
     _lib.call("slk_dcor", _dev(x, "x", (n, dx)), dx, _dev(z, "z", (n, dz), torch.bfloat16), dz, n,
               _dev(workspace, "workspace", dtype=torch.uint8), _dev(out, "out", (4,)), _stream(x))
     return out
+
+
+def dcor_grad_workspace_bytes(n: int) -> int:
+    """Bytes of the workspace slk_dcor_grad needs for n samples."""
+    return _lib.query("slk_dcor_grad_workspace_bytes", int(n))
+
+
+def dcor_grad(x, z, dcut, alpha, squared, workspace, out, out4):
+    """out (bf16 [n, dz]) = dcut + alpha * d dCor^2(x, z) / d z (dCor itself with squared=False) and out4 = slk_dcor's
+    four values — slk_dcor_grad; alpha is a device f32 [1], every buffer is the caller's (privacy.DcorLoss checks and
+    caches them). out may be dcut."""
+    n, dx, dz = int(x.shape[0]), int(x.shape[1]), int(z.shape[1])
+    _lib.call("slk_dcor_grad", _dev(x, "x", (n, dx)), dx, _dev(z, "z", (n, dz), torch.bfloat16), dz, n,
+              _dev(dcut, "dcut", (n, dz), torch.bfloat16), _dev(alpha, "alpha", (1,)), int(bool(squared)),
+              _dev(workspace, "workspace", dtype=torch.uint8), _dev(out, "out", (n, dz), torch.bfloat16),
+              _dev(out4, "out4", (4,)), _stream(x))
+    return out

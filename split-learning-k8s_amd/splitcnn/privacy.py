@@ -300,7 +300,7 @@ def distance_correlation(x, z, out=None) -> DistanceCorrelation:
     """The sample distance correlation between the raw inputs x (float32 [n, ...]) and the cut z (bf16 [n, ...]), both
     flattened per sample to a multiple of 64 elements: slk_dcor, the biased (V-statistic) form that NoPeek reports,
     with Gram-based float32 distances and the resolution rule of include/slk.h. 0 means independent, 1 a similarity
-    transform. A metric only — nothing here is differentiable.
+    transform. The metric alone: DcorLoss below adds its gradient to a cut gradient.
 
     Three launches on x's current stream, no host sync (the result object syncs on first access) and no allocation
     once the workspace for this (device, n) exists, so a call can be captured in a HIP graph: pass out= (f32 [4]) then
@@ -328,3 +328,90 @@ def distance_correlation(x, z, out=None) -> DistanceCorrelation:
         ws = _DCOR_WORKSPACES[key] = torch.empty(ops.dcor_workspace_bytes(n), dtype=torch.uint8, device=x.device)
     ops.dcor(x2, z2, ws, out)
     return DistanceCorrelation(out)
+
+
+# ------------------------------------------------------------------------------------ training against leakage
+_DCOR_GRAD_WORKSPACES: dict = {}   # (device, n) -> slk_dcor_grad's workspace, like _DCOR_WORKSPACES
+
+
+class DcorLoss:
+    """The NoPeek term (Vepakomma et al.) on the K5 cut, as a config of one entry, slk_dcor_grad: the client trains on
+    task loss + alpha * dCor^2(x, cut) by adding alpha * d dCor^2 / d cut to the cut gradient it back-propagates. The
+    term is client-local (x and the raw cut never leave the client) and inherits the metric's rule (include/slk.h,
+    "Distance correlation gradient"). squared=False differentiates dCor itself.
+
+    `alpha` lives in a device f32[1] the kernel reads, so a captured HIP graph follows `set_alpha` without being
+    recaptured; `squared` is passed by value: a captured graph keeps it, and there is no setter."""
+
+    def __init__(self, alpha: float, squared: bool = True, device="cuda"):
+        self.alpha = self._checked_alpha(alpha)
+        if not isinstance(squared, bool):
+            raise ValueError(f"DcorLoss: squared={squared!r}; expected a bool")
+        self.squared = squared
+        self.alpha_value = torch.full((1,), self.alpha, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _checked_alpha(alpha) -> float:
+        if not _number(alpha) or not 0.0 <= alpha < math.inf:   # NaN fails this too
+            raise ValueError(f"DcorLoss: alpha={alpha!r}; expected a finite number >= 0")
+        return float(alpha)
+
+    def to(self, device) -> "DcorLoss":
+        """Move the scalar (a no-op on its own device); captured graphs hold its address, so move a DcorLoss before
+        the first step only."""
+        if self.alpha_value.device != torch.device(device):
+            self.alpha_value = self.alpha_value.to(device)
+        return self
+
+    def set_alpha(self, alpha: float) -> None:
+        """Overwrite the weight in place: an asynchronous device write on the current stream, so the next launch —
+        eager or a replay of an already captured graph — runs at `alpha`."""
+        self.alpha = self._checked_alpha(alpha)
+        self.alpha_value.fill_(self.alpha)
+
+    def __repr__(self):
+        return f"DcorLoss(alpha={self.alpha}, squared={self.squared})"
+
+    def add_grad(self, x, cut, dcut, out=None, stats=None):
+        """out = dcut + alpha * d dCor^2(x, cut) / d cut; out=None writes dcut in place. x is float32 [n, ...], cut and
+        dcut bf16 [n, ...] of one shape, flattened per sample to multiples of 64 elements. `stats` (f32 [4]) receives
+        the metric's four values (DistanceCorrelation(stats) reads them). Six launches on x's current stream, no host
+        sync, and no allocation once the workspace for this (device, n) exists. Returns out."""
+        dx, dz = _dcor_width(x, "x", torch.float32), _dcor_width(cut, "cut", torch.bfloat16)
+        x2, z2 = _dcor_rows(x, "x", dx), _dcor_rows(cut, "cut", dz)
+        n = int(x2.shape[0])
+        if n == 0:
+            raise ValueError("DcorLoss.add_grad: an empty batch has no statistic")
+        out = dcut if out is None else out
+        rows = [z2]
+        for t, name in ((dcut, "dcut"), (out, "out")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+                raise TypeError(f"{name}: expected a {torch.bfloat16} torch.Tensor")
+            if tuple(t.shape) != tuple(cut.shape):
+                raise ValueError(f"{name}: expected {tuple(cut.shape)} like cut, got {tuple(t.shape)}")
+            rows.append(_dcor_rows(t, name, dz))
+        if int(z2.shape[0]) != n:
+            raise ValueError(f"cut: expected {n} samples like x, got {z2.shape[0]}")
+        if stats is None:
+            stats = torch.empty(4, dtype=torch.float32, device=x.device)
+        else:
+            _dev(stats, "stats", (4,), torch.float32)
+            if stats.data_ptr() % 16:
+                raise ValueError("stats: the base address must be 16-byte aligned")
+        for t, name in ((cut, "cut"), (dcut, "dcut"), (out, "out"), (stats, "stats"), (self.alpha_value, "alpha")):
+            if t.device != x.device:
+                raise ValueError(f"{name}: on {t.device}, x is on {x.device}")
+        key = (x.device, n)
+        ws = _DCOR_GRAD_WORKSPACES.get(key)
+        if ws is None:
+            ws = _DCOR_GRAD_WORKSPACES[key] = torch.empty(ops.dcor_grad_workspace_bytes(n), dtype=torch.uint8,
+                                                          device=x.device)
+        ops.dcor_grad(x2, z2, rows[1], self.alpha_value, self.squared, ws, rows[2], stats)
+        return out
+
+
+def check_dcor_loss(loss):
+    """A trainer's leak_loss argument: a DcorLoss or None."""
+    if loss is not None and not isinstance(loss, DcorLoss):
+        raise TypeError(f"expected splitcnn.privacy.DcorLoss or None, got {type(loss).__name__}")
+    return loss

@@ -38,7 +38,8 @@ from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
 from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema
-from .privacy import CutNoise, check_cut_noise, distance_correlation
+from .privacy import (CutNoise, DcorLoss, DistanceCorrelation, check_cut_noise, check_dcor_loss,
+                      distance_correlation)
 from .recipe import Seg, StageRecipe, _flatten_params
 
 P_DROP = 0.25
@@ -666,7 +667,15 @@ class WideTrainer(GraphedTrainer):
     table and tail are by-value constants it keeps. evaluate / eval_batch / predict apply the clip and NO noise, on
     the live and on the averaged weights: evaluation stays a pure function of the weights (noisy inference is the
     user's own CutNoise.apply call). cut_stats() reads the last step's (norm, coef) per sample. cut_noise=None
-    launches nothing new."""
+    launches nothing new.
+
+    `leak_loss` (privacy.DcorLoss) trains the client against leakage, NoPeek's way: its loss is the task loss +
+    alpha * dCor^2(x, cut). The term is client-local: after the clip's backward the client adds
+    alpha * d dCor^2(x, raw cut) / d cut to the cut gradient in place (slk_dcor_grad; the raw cut is the client's
+    forward output, before the clip, the noise and any codec) and back-propagates the sum, inside the captured step.
+    DcorLoss.set_alpha reaches a captured graph; `squared` is a by-value constant it keeps. leak_stats() reads the
+    last step's distance correlation of (x, raw cut). The logged loss stays the task loss. leak_loss=None launches
+    nothing new."""
 
     input_shape = (3, 32, 32)
 
@@ -674,7 +683,8 @@ class WideTrainer(GraphedTrainer):
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
                  loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
-                 cut_codec: Union[Fp8Cut, MxCut, None] = None, cut_noise: Optional[CutNoise] = None):
+                 cut_codec: Union[Fp8Cut, MxCut, None] = None, cut_noise: Optional[CutNoise] = None,
+                 leak_loss: Optional[DcorLoss] = None):
         check_clip(clip)
         check_ema(ema)
         self.cut_codec = check_cut_codec(cut_codec)
@@ -683,6 +693,10 @@ class WideTrainer(GraphedTrainer):
         if self.cut_noise is not None:
             self.cut_noise.to(self.device)
         self._cut_stats_B = None
+        self.leak_loss = check_dcor_loss(leak_loss)
+        if self.leak_loss is not None:
+            self.leak_loss.to(self.device)
+            self._leak_stats = torch.zeros(4, dtype=_F32, device=self.device)
         self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
                                       schedule=self.client.schedule, clip=self.client.clip, loss=loss,
@@ -736,13 +750,30 @@ class WideTrainer(GraphedTrainer):
             raise RuntimeError("cut_stats: no training step has run yet")
         return self.server._b("cut_n_stats", (self._cut_stats_B, 2), _F32).cpu()
 
+    def _leak(self, x, raw_cut, dcut):
+        """dcut plus the leakage term of (x, the client's raw cut), in place; dcut itself without leak_loss."""
+        if self.leak_loss is None:
+            return dcut
+        with TIMER("dcor_grad"):
+            return self.leak_loss.add_grad(x, raw_cut, dcut, stats=self._leak_stats)
+
+    def leak_stats(self) -> DistanceCorrelation:
+        """The distance correlation between the last training step's batch and its raw cut, as the step's own
+        slk_dcor_grad measured it (before that step's update). One host sync. Needs leak_loss=."""
+        if self.leak_loss is None:
+            raise RuntimeError("leak_stats: the trainer was built without leak_loss= (privacy.DcorLoss)")
+        if self._cut_stats_B is None:
+            raise RuntimeError("leak_stats: no training step has run yet")
+        return DistanceCorrelation(self._leak_stats.clone())
+
     def step(self, x, y):
         self._cut_stats_B = int(x.shape[0])   # which of the per-batch-size stats buffers the last step wrote
         super().step(x, y)
 
     def _eager(self, x, y):
         c, s, q = self.client, self.server, self.cut_codec
-        cut = self._noised(c.forward(x), "cut_n", c.step_ctr)
+        raw = c.forward(x)
+        cut = self._noised(raw, "cut_n", c.step_ctr)
         cut = self._wire(cut, "fwd", "cut_q", c.step_ctr)
         if q is not None and q.format("bwd") is not None and q.rounding_of("bwd") == "stochastic":
             # step_request with the gradient rounded before the server's tick: its words are this step's
@@ -752,7 +783,7 @@ class WideTrainer(GraphedTrainer):
             s.step_from_slabs(sf)
         else:
             dcut = self._wire(s.step_request(cut, y)[0], "bwd", None, s.step_ctr)
-        c.backward_step(self._unclipped(dcut))
+        c.backward_step(self._leak(x, raw, self._unclipped(dcut)))
 
     def _state(self):
         c, s = self.client, self.server
