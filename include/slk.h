@@ -95,7 +95,9 @@ const char* slk_build_id(void);
  *    without a clip a non-finite element stays its own; no other sample is touched. The MX cut records ("MX cut
  *    records" below) poison by BLOCK, not by sample: a non-finite element makes its 32-element block's scale byte 0xFF
  *    and the block 32 NaNs on the other side, the sample's other 511 blocks are unchanged (the FP8 records poison the
- *    whole sample); the head then poisons that sample's logits as for any NaN feature it keeps.
+ *    whole sample); the head then poisons that sample's logits as for any NaN feature it keeps. The top-k cut records
+ *    ("Top-k cut records" below) poison by sample like the FP8 records: one non-finite element makes the whole sample
+ *    16,384 NaNs on the other side, and no other sample is touched.
  * The supported check is Python's GraphedTrainer.check_finite() (parameters, optimizer state, averaged blocks). */
 
 /* ---------------------------------------------------------------- client stage (ModelPartA) */
@@ -947,6 +949,49 @@ int slk_cutmx_encode(const void* x_bf16, int n, int fmt, void* rec, void* stream
 int slk_cutmx_decode(const void* rec, int n, int fmt, void* out_bf16, int* err_flag, void* stream);
 int slk_cutmx_roundtrip(const void* x_bf16, int n, int fmt, void* out_bf16, void* stream);
 int64_t slk_cutmx_record_bytes(int fmt); /* 8720 / 16912; -1 for another fmt */
+/* Top-k cut records (csrc/slk_cuttopk.hip): an opt-in, lossy, sparsified wire format of the K5 cut and of its
+ * gradient — the k largest-magnitude elements of a sample, bit for bit, and a bit map of their positions — where the
+ * FP8 and MX records keep every element and narrow it. A sample is the 16,384 contiguous bf16 elements of one cut or
+ * cut-gradient row as stored, as in the FP8 and MX records. The key of element i is mag_i = bits_i & 0x7FFF.
+ * Selection: k is a multiple of 8 with 8 <= k <= 8192. Order the elements by (mag descending, index ascending) and
+ * keep the first k. The sign plays no part in the order: +x and -x tie, and the lower index wins. Zeros take part like
+ * any value: a sample with fewer than k nonzeros fills up with its lowest-index zeros, and a kept -0 keeps its sign.
+ * Exactly k elements are always kept.
+ * Poison: a sample with a non-finite element (mag >= 0x7F80) is poisoned, as the FP8 records poison a sample.
+ * Record: u8 [n, R], records contiguous, the base 16-byte aligned; R = 16 + 2048 + 2 k, a multiple of 16, so a slice
+ * of samples is an aligned slice of bytes (k = 1024: 4,112 bytes; k = 2048: 6,160; the dense row is 32,768).
+ *   bytes 0..15      header: uint32 words, little endian: word 0 = k, word 1 = 0x20 (disjoint from the FP8 records'
+ *                    0 / 1 and the MX records' 0x10 / 0x11, so each decoder reports the others' records as
+ *                    malformed), word 2 = 1 for a poisoned sample and 0 otherwise, word 3 = 0.
+ *   bytes 16..2063   the bit map: element i is bit i & 31 of little-endian uint32 word i >> 5 (bit i & 7 of byte
+ *                    i >> 3); a set bit is a kept element.
+ *   bytes 2064..     the k kept values as raw bf16 bits, in ascending element index.
+ * A poisoned record has an all-zero bit map and all-zero value bytes.
+ * Decode: a kept element returns bit for bit; every other element is +0 (0x0000). A poisoned record decodes to
+ * 16,384 x 0x7FC0 without touching err_flag, and its payload is not looked at. A malformed record decodes its sample
+ * to 16,384 x 0x7FC0 and stores err_flag[0] = 1 (a plain store; nobody clears it); the other samples of the launch
+ * decode as usual. Malformed is any of: word 0 != the k passed to the call; word 1 != 0x20; word 2 > 1; word 3 != 0;
+ * in an unpoisoned record, a bit map whose population count is not k (checked before anything is written).
+ * slk_cuttopk_roundtrip is bitwise decode(encode(x)) in one launch with no record in memory; out may equal x.
+ * decode(encode(.)) is idempotent: a roundtripped sample selects the same k positions again (what was dropped is
+ * now +0 and loses every tie it lost before).
+ * Order inside a training step (wide.WideTrainer(cut_codec=codec.TopKCut(...))): the cut noise if any,
+ * slk_cuttopk_roundtrip with the forward k, the head, slk_cuttopk_roundtrip with the backward k in place, the clip's
+ * slk_cut_scale_rows if any, the client's backward: straight through, the backward is not masked by the forward's
+ * selection.
+ * One workgroup of 256 threads per sample; a wave owns 4,096 contiguous elements and reads and writes them as
+ * 16-byte pieces, 1 KiB contiguous per instruction. The selection is an exact two-level radix select on the key
+ * (mag >> 7 in 256 bins, then mag & 127 in 128 bins over the crossing bin) with one histogram per wave in LDS —
+ * integer LDS adds, whose sum does not depend on their order — and ties are ranked in index order by wave prefix sums.
+ * Every output byte is written by exactly one thread, without global atomics or scratch: the result is a function of
+ * the sample alone, bit-reproducible from run to run.
+ * n == 0 launches nothing and returns 0. Refused before any launch: n < 0, k < 0, a NULL pointer or a pointer that is
+ * not 16-byte aligned (err_flag: 4-byte) with hipErrorInvalidValue; with well-formed pointers, a k that is not a
+ * multiple of 8 in [8, 8192] with hipErrorInvalidConfiguration (9). */
+int slk_cuttopk_encode(const void* x_bf16, int n, int k, void* rec, void* stream);
+int slk_cuttopk_decode(const void* rec, int n, int k, void* out_bf16, int* err_flag, void* stream);
+int slk_cuttopk_roundtrip(const void* x_bf16, int n, int k, void* out_bf16, void* stream);
+int64_t slk_cuttopk_record_bytes(int k); /* 2064 + 2 k; -1 for a k the rule refuses */
 /* Cut noise (csrc/slk_cut_noise.hip): an opt-in defence of the K5 cut against model inversion — a per-sample norm
  * bound, then additive noise from a 1,024-entry table. An experiment's tool, not a certified mechanism: no epsilon
  * is claimed. A sample is the 16,384 contiguous bf16 elements of one cut row, as in the FP8 records. All float

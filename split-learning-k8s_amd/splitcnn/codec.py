@@ -9,7 +9,9 @@ Every weight, loss and gradient downstream is bit-identical to the dense exchang
 
 The widened model's bf16 cut (K5, wide.py) has a codec of its own, Fp8Cut (csrc/slk_cut8.hip): opt-in and lossy, one
 power-of-two scale per sample and OCP FP8 codes, half the bytes in each direction; and a block-scaled one, MxCut
-(csrc/slk_cutmx.hip): one E8M0 scale per 32 elements and OCP e2m1 / e4m3 codes, 0.27 / 0.52 of the bytes.
+(csrc/slk_cutmx.hip): one E8M0 scale per 32 elements and OCP e2m1 / e4m3 codes, 0.27 / 0.52 of the bytes; and a
+sparsifying one, TopKCut (csrc/slk_cuttopk.hip): the k largest-magnitude elements of a sample bit for bit and a bit
+map of their positions, 0.125 of the bytes at k = 1024.
 """
 from __future__ import annotations
 
@@ -25,6 +27,8 @@ CUT8_ROUNDINGS = ("nearest", "stochastic")
 CUTMX_BLOCK = 32         # elements under one scale byte of an MX record
 CUTMX_FORMATS = {"e2m1": 0, "e4m3": 1}
 CUTMX_RECORD = {"e2m1": 8720, "e4m3": 16912}   # a 16-byte header, 512 scale bytes, 4- or 8-bit codes
+CUTTOPK_K = (8, 8192)    # the k of a top-k record: a multiple of 8 in this range
+CUTTOPK_HEAD = 2064      # a 16-byte header and a 2,048-byte bit map; then k bf16 values
 
 
 class CutCodec:
@@ -346,8 +350,106 @@ class MxCut:
         return out
 
 
+class TopKCut:
+    """Opt-in lossy top-k sparsification of the widened model's cut (csrc/slk_cuttopk.hip; the rule is in
+    include/slk.h, "Top-k cut records"): the k largest-magnitude elements of a sample travel bit for bit, in index
+    order, behind a bit map of their positions — 2,064 + 2 k bytes a sample (k = 1024: 4,112; k = 2048: 6,160) against
+    the bf16 cut's 32,768 — and every other element is +0 on the other side. Ties go to the lower index, the sign plays
+    no part, and exactly k elements are always kept. `fwd` is the k of the cut, `bwd` that of the cut gradient; either
+    may be None, which leaves that direction dense bf16. k is a constructor constant passed to the kernels by value: a
+    captured graph keeps it, and there is no setter. Nothing is rounded (rounding_of is always "nearest").
+
+    A sample is 16,384 contiguous bf16 elements: x / out are [n, ...] with 16,384 elements per row, records are uint8
+    [n, record_bytes(direction)]. The surface is MxCut's: every method works on caller-visible buffers and launches on
+    the tensor's current stream; encode / roundtrip accept and ignore step= / row0=."""
+
+    def __init__(self, fwd=2048, bwd=None):
+        for name, v in (("fwd", fwd), ("bwd", bwd)):
+            if v is None:
+                continue
+            lo, hi = CUTTOPK_K
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi or v % 8:
+                raise ValueError(f"TopKCut: {name}={v!r}; expected k, a multiple of 8 with {lo} <= k <= {hi}, or None")
+        if fwd is None and bwd is None:
+            raise ValueError("TopKCut: fwd and bwd are both None — that is the dense exchange (pass no codec)")
+        self.fwd, self.bwd = fwd, bwd
+        self._bufs = {}
+
+    def __repr__(self):
+        return f"TopKCut(fwd={self.fwd!r}, bwd={self.bwd!r})"
+
+    def rounding_of(self, direction: str) -> str:
+        """The rounding of "fwd" / "bwd": always "nearest" (kept values are not rounded at all)."""
+        self.format(direction)
+        return "nearest"
+
+    def nearest(self) -> "TopKCut":
+        """This codec (what evaluation uses): it has no random part."""
+        return self
+
+    def format(self, direction: str):
+        """The k of "fwd" / "bwd", or None where that direction stays dense."""
+        if direction not in ("fwd", "bwd"):
+            raise ValueError(f"TopKCut: direction {direction!r}; expected 'fwd' or 'bwd'")
+        return self.fwd if direction == "fwd" else self.bwd
+
+    def _k(self, direction: str) -> int:
+        k = self.format(direction)
+        if k is None:
+            raise ValueError(f"TopKCut: the {direction} direction is dense (built with {direction}=None)")
+        return k
+
+    def record_bytes(self, direction: str) -> int:
+        """Bytes of one sample's record in "fwd" / "bwd": 2,064 + 2 k."""
+        return CUTTOPK_HEAD + 2 * self._k(direction)
+
+    def _records(self, rec, n, direction, name="rec"):
+        _dev(rec, name, (n, self.record_bytes(direction)), torch.uint8)
+        Fp8Cut._aligned(rec, name)
+
+    def records(self, key, n: int, device, direction=None):
+        """The uint8 [n, record_bytes(direction)] record buffer of `key`; `direction` is required: the two directions
+        may have different record widths. Keyed by shape too and never replaced, so a HIP graph captured around the
+        kernels at one size keeps valid pointers after another size has run (CutCodec._buf)."""
+        if direction is None:
+            raise ValueError("TopKCut.records: direction= is required ('fwd' or 'bwd')")
+        width = self.record_bytes(direction)
+        k = (key, int(n), width, str(torch.device(device)))
+        t = self._bufs.get(k)
+        if t is None:
+            t = torch.empty((int(n), width), dtype=torch.uint8, device=device)
+            self._bufs[k] = t
+        return t
+
+    def encode(self, x, rec, direction: str = "fwd", step=None, row0: int = 0):
+        """x (bf16 [n, ...]) -> rec (uint8 [n, record_bytes(direction)]) with `direction`'s k."""
+        k, n = self._k(direction), Fp8Cut._rows(x, "x")
+        self._records(rec, n, direction)
+        _lib.call("slk_cuttopk_encode", x.data_ptr(), n, k, rec.data_ptr(), _stream(x))
+        return rec
+
+    def decode(self, rec, out, err_flag, direction: str = "fwd"):
+        """rec -> out (bf16 [n, ...]); a malformed record (a wrong header word, another k, a bit map that does not
+        hold k bits) decodes its sample to NaNs and sets err_flag (int32 [1]); a poisoned record (its sample had a
+        non-finite element) decodes to NaNs without the flag."""
+        k, n = self._k(direction), Fp8Cut._rows(out, "out")
+        self._records(rec, n, direction)
+        _dev(err_flag, "err_flag", (1,), torch.int32)
+        _lib.call("slk_cuttopk_decode", rec.data_ptr(), n, k, out.data_ptr(), err_flag.data_ptr(), _stream(out))
+        return out
+
+    def roundtrip(self, x, out, direction: str, step=None, row0: int = 0):
+        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x."""
+        k, n = self._k(direction), Fp8Cut._rows(x, "x")
+        if Fp8Cut._rows(out, "out") != n:
+            raise ValueError(f"out: expected {n} samples like x, got {out.shape[0]}")
+        _lib.call("slk_cuttopk_roundtrip", x.data_ptr(), n, k, out.data_ptr(), _stream(x))
+        return out
+
+
 def check_cut_codec(codec):
-    """A trainer's / hub's codec argument: an Fp8Cut, an MxCut or None."""
-    if codec is not None and not isinstance(codec, (Fp8Cut, MxCut)):
-        raise TypeError(f"expected splitcnn.codec.Fp8Cut, splitcnn.codec.MxCut or None, got {type(codec).__name__}")
+    """A trainer's / hub's codec argument: an Fp8Cut, an MxCut, a TopKCut or None."""
+    if codec is not None and not isinstance(codec, (Fp8Cut, MxCut, TopKCut)):
+        raise TypeError("expected splitcnn.codec.Fp8Cut, splitcnn.codec.MxCut, splitcnn.codec.TopKCut or None, got "
+                        f"{type(codec).__name__}")
     return codec

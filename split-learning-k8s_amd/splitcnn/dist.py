@@ -885,8 +885,11 @@ class WideHub:
         self.client_group = client_group
         self.codec = self.err_flag = None
         if codec is not None:
-            from .codec import check_cut_codec
-            self.codec = check_cut_codec(codec)
+            from .codec import TopKCut, check_cut_codec
+            if isinstance(check_cut_codec(codec), TopKCut):
+                raise ValueError("WideHub(codec=...): the top-k cut codec has no hub form yet (it runs in "
+                                 "wide.WideTrainer(cut_codec=...) only)")
+            self.codec = codec
             device = torch.device(getattr(stage, "device", "cpu"))
             if device.type != "cuda":
                 raise ValueError(f"WideHub(codec=...): the {self._codec_name()} cut codec runs as HIP kernels on CUDA "

@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
-from .codec import Fp8Cut, MxCut, check_cut_codec
+from .codec import Fp8Cut, MxCut, TopKCut, check_cut_codec
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
@@ -657,6 +657,9 @@ class WideTrainer(GraphedTrainer):
     training rounding is: they stay a pure function of the weights, bitwise those of Fp8Cut(fwd, bwd). A codec.MxCut
     in the same place runs the block-scaled exchange (include/slk.h, "MX cut records") the same way: two
     slk_cutmx_roundtrip launches at the same two places, always to nearest, evaluation and prediction included.
+    A codec.TopKCut runs the top-k sparsification (include/slk.h, "Top-k cut records") there: slk_cuttopk_roundtrip
+    with the direction's k. The backward is straight through: the client back-propagates the server's whole dcut,
+    sparsified by its own k if bwd is set, not masked by the forward's selection.
 
     `cut_noise` (privacy.CutNoise) puts a noise defence on the cut, inside the captured step: the cut is clipped per
     sample and noised (slk_cut_noise) into the server-stage buffer `cut_n` under the client's step_ctr with row0 = 0,
@@ -683,7 +686,7 @@ class WideTrainer(GraphedTrainer):
                  device="cuda", graph: bool = True, seed: int = 0, optim: Optional[Adam] = None,
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
                  loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
-                 cut_codec: Union[Fp8Cut, MxCut, None] = None, cut_noise: Optional[CutNoise] = None,
+                 cut_codec: Union[Fp8Cut, MxCut, TopKCut, None] = None, cut_noise: Optional[CutNoise] = None,
                  leak_loss: Optional[DcorLoss] = None):
         check_clip(clip)
         check_ema(ema)
@@ -713,7 +716,8 @@ class WideTrainer(GraphedTrainer):
         if step is None:
             q = q.nearest()
         out = self.server._b(name, tuple(t.shape), _BF) if name is not None else t
-        with TIMER("cutmx_roundtrip" if isinstance(q, MxCut) else "cut8_roundtrip"):
+        with TIMER("cuttopk_roundtrip" if isinstance(q, TopKCut) else
+                   "cutmx_roundtrip" if isinstance(q, MxCut) else "cut8_roundtrip"):
             if q.rounding_of(direction) == "stochastic":
                 return q.roundtrip(t, out, direction, step=step)
             return q.roundtrip(t, out, direction)   # today's call, argument for argument
