@@ -949,6 +949,33 @@ int slk_cutmx_encode(const void* x_bf16, int n, int fmt, void* rec, void* stream
 int slk_cutmx_decode(const void* rec, int n, int fmt, void* out_bf16, int* err_flag, void* stream);
 int slk_cutmx_roundtrip(const void* x_bf16, int n, int fmt, void* out_bf16, void* stream);
 int64_t slk_cutmx_record_bytes(int fmt); /* 8720 / 16912; -1 for another fmt */
+/* The head on MX cut records (csrc/slk_wide_head_mx.hip): slk_wide_head reading the cut as MX records and writing the
+ * cut gradient as MX records (fmt_out 0 / 1: u8 [B, R(fmt_out)]) or as dense bf16 rows (fmt_out -1: bf16 [B, 16384]),
+ * in the head's two launches, with no bf16 cut in memory. rec_in is u8 [B, R(fmt_in)], fmt_in 0 / 1.
+ * The rule: every output is bit for bit what these three launches write, cut and dcut being bf16 [B, 16384]
+ * temporaries:
+ *   slk_cutmx_decode(rec_in, B, fmt_in, cut, rec_err);
+ *   slk_wide_head(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale, grad_scale, logits, loss_i, dlogits,
+ *                 dcut, slabs, work, label_err, b0, B);
+ *   slk_cutmx_encode(dcut, B, fmt_out, dcut_out), or a plain copy of dcut for fmt_out -1.
+ * That covers logits, loss_i, dlogits, the slk_wide_head_nslab(B) slabs, dcut_out with its headers and scale bytes,
+ * label_err (set as slk_wide_head sets err_flag) and rec_err (set as the decoder sets err_flag: a plain store of 1,
+ * nobody clears it), and with them every corner of "MX cut records": a poisoned block is 32 NaNs to the head, a scale
+ * byte below 27 makes its block NaN and a wrong header word its whole sample, both storing rec_err[0] = 1; an e4m3 NaN
+ * code propagates; a finite code whose product reaches 2^128 is the largest finite bf16 of its sign; a block of dcut
+ * with a non-finite element leaves poisoned (scale byte 0xFF, zero codes), and a zero code keeps its sign. The
+ * arithmetic order is slk_wide_head's (csrc/slk_wide_head.h holds the shared expressions), which is what makes the
+ * equality bitwise: the decode is exact, so both paths feed the same float32 values into the same operations.
+ * work = slk_wide_head_mx_work(B) floats, 16-byte aligned: the step's dropout bits and one verdict byte per sample
+ * (its header, checked once in the first launch and read by the second). Every output byte has one writer; the only
+ * atomic is the label flag's. B == 0 launches nothing and returns 0; B < 0, b0 < 0, fmt_in outside {0, 1}, fmt_out
+ * outside {-1, 0, 1}, a NULL pointer (every pointer is required, both flags included), rec_in, dcut_out or work not
+ * 16-byte aligned, or a flag not 4-byte aligned is refused with hipErrorInvalidValue before any launch. */
+int slk_wide_head_mx(const void* rec_in, int fmt_in, const float* wf8, const float* bf, const int64_t* labels,
+                     const int* step, uint32_t seed, uint32_t keep_threshold, float keep_scale, float grad_scale,
+                     float* logits, float* loss_i, float* dlogits, void* dcut_out, int fmt_out, float* slabs,
+                     float* work, int* label_err, int* rec_err, int b0, int B, void* stream);
+int slk_wide_head_mx_work(int B);
 /* Top-k cut records (csrc/slk_cuttopk.hip): an opt-in, lossy, sparsified wire format of the K5 cut and of its
  * gradient — the k largest-magnitude elements of a sample, bit for bit, and a bit map of their positions — where the
  * FP8 and MX records keep every element and narrow it. A sample is the 16,384 contiguous bf16 elements of one cut or

@@ -126,6 +126,9 @@ _SIGS = {
     "slk_cutmx_decode": [_P, _I, _I, _P, _P, _P],
     "slk_cutmx_roundtrip": [_P, _I, _I, _P, _P],
     "slk_cutmx_record_bytes": [_I],
+    # the K5 head reading and writing those records (ops.wide_head_mx)
+    "slk_wide_head_mx": [_P, _I, _P, _P, _P, _P, _U, _U, _F, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P],
+    "slk_wide_head_mx_work": [_I],
     # top-k sparsified records of the K5 cut and its gradient (codec.TopKCut)
     "slk_cuttopk_encode": [_P, _I, _I, _P, _P],
     "slk_cuttopk_decode": [_P, _I, _I, _P, _P, _P],

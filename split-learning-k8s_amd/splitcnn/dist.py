@@ -874,10 +874,18 @@ class WideHub:
     (not yet ticked) and row0 = rank * B + k * b, before the encode / isend; the received gradient part is scaled by
     that part's coefficients (slk_cut_scale_rows, only with a clip) after the decode and before backward_grads. So
     the hub step is wide.WideTrainer(cut_noise=...)'s at batch (N-1)*B, and the byte counts do not change. HIP
-    kernels: the stage must be on a CUDA device."""
+    kernels: the stage must be on a CUDA device.
+
+    native_head (opt-in; needs an MxCut whose forward format is set): the server rank hands every received part's
+    records to the stage's accumulate_records (slk_wide_head_mx, csrc/slk_wide_head_mx.hip), which reads them and writes
+    the part's cut gradient as records in the backward format — dense bf16 where that direction is dense — so the
+    server launches no decode and no encode and keeps no bf16 cut. The step is bitwise the native_head=False step;
+    exchange_bytes and check_exchange() (fed by the head's record flag) are unchanged. Client ranks accept the flag
+    and ignore it. With MxCut(bwd=None) the head writes dense rows and was measured 8 % SLOWER than decode + head
+    (README "The server head on MX records"): that combination buys the missing cut buffer only, not time."""
 
     def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None, codec=None,
-                 noise=None):
+                 noise=None, native_head: bool = False):
         _default_optimizer_only("WideHub", stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.server_rank = world - 1
@@ -895,6 +903,17 @@ class WideHub:
                 raise ValueError(f"WideHub(codec=...): the {self._codec_name()} cut codec runs as HIP kernels on CUDA "
                                  f"tensors; the stage is on {device} — pass no codec (on BOTH sides) for CPU stages")
             self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.native_head = bool(native_head)
+        if self.native_head:
+            from .codec import MxCut
+            if not isinstance(self.codec, MxCut):
+                raise ValueError("WideHub(native_head=True): the head reads MX cut records; pass codec=codec.MxCut(...)"
+                                 + (f" (got {type(self.codec).__name__})" if self.codec is not None else " (no codec)"))
+            if self.codec.fwd is None:
+                raise ValueError("WideHub(native_head=True): the forward direction is dense (MxCut(fwd=None)); the head "
+                                 "has no records to read")
+            if rank == self.server_rank:   # (a stage built with loss= was refused above, whatever the flag)
+                self.err_flag = stage.records_err_flag()   # what check_exchange() reads
         self.noise = None
         if noise is not None:
             from .privacy import check_cut_noise
@@ -991,11 +1010,12 @@ class WideHub:
         s, q = self.stage, self.codec
         m, nc = self.micro, self.nclients
         b, G = B // m, nc * B
-        cuts = self._buf("cuts", cut_shape(G), cut_dtype, device)
-        dcuts = self._buf("dcuts", cut_shape(G), cut_dtype, device)
-        labels = self._buf("labels", (G,), torch.int64, device)
         fw, bw = self.groups
         f8, b8 = self._fp8("fwd"), self._fp8("bwd")
+        native = self.native_head   # the head reads and writes the records: no dense cut, no dense gradient if b8
+        cuts = None if native else self._buf("cuts", cut_shape(G), cut_dtype, device)
+        dcuts = None if native and b8 else self._buf("dcuts", cut_shape(G), cut_dtype, device)
+        labels = self._buf("labels", (G,), torch.int64, device)
         reqs, recs = {}, {}
         for c in range(nc):
             for k in range(m):
@@ -1008,9 +1028,15 @@ class WideHub:
                 sl = slice(c * B + k * b, c * B + (k + 1) * b)
                 for r in reqs[c, k]:
                     r.wait()
+                b0 = c * B + k * b
+                if native:   # records in, records (or dense rows) out: no decode, no encode
+                    out = q.records(("bwd", c, k), b, device, direction="bwd") if b8 else dcuts[sl]
+                    s.accumulate_records(recs[c, k], q.fwd, labels[sl], 1.0 / G, b0, part, m * nc, out, q.bwd)
+                    sends.append(isend(out, c, bw))
+                    part += 1
+                    continue
                 if f8:
                     q.decode(recs[c, k], cuts[sl], self.err_flag, "fwd")
-                b0 = c * B + k * b
                 s.accumulate(cuts[sl], labels[sl], 1.0 / G, b0, part, m * nc, dcut=dcuts[sl])
                 out = (q.encode(dcuts[sl], q.records(("bwd", c, k), b, device, direction="bwd"), "bwd", step=s.step_ctr,
                                 row0=b0) if b8 else dcuts[sl])
@@ -1019,7 +1045,8 @@ class WideHub:
         s.finish_step(m * nc, step=self.global_step)
         for w in sends:
             w.wait()
-        self._count_bytes(G, cuts[0].numel() * cuts.element_size() if G else 0)
+        row = cuts if cuts is not None else torch.empty(cut_shape(G), dtype=cut_dtype, device="meta")
+        self._count_bytes(G, row[0].numel() * row.element_size() if G else 0)
         self.global_step += 1
 
 

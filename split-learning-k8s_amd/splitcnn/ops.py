@@ -1037,6 +1037,44 @@ def wide_head_soft(cut, wf8, bf, labels, step, seed, keep_threshold, keep_scale,
     return dcut, loss_i, slabs
 
 
+# ------------------------------------------------------------------------------------ widened head, MX records
+def wide_head_mx_work(B: int) -> int:
+    """Floats of the `work` buffer slk_wide_head_mx needs for B samples (dropout bits + one verdict byte a sample)."""
+    return _lib.query("slk_wide_head_mx_work", int(B))
+
+
+def wide_head_mx(rec, fmt_in, wf8, bf, labels, step, seed, keep_threshold, keep_scale, grad_scale, logits, loss_i,
+                 dlogits, out, fmt_out, slabs, work, label_err, rec_err, b0=0):
+    """slk_wide_head on MX cut records (slk_wide_head_mx): rec is uint8 [B, R(fmt_in)] (fmt 0 = e2m1, 1 = e4m3), `out`
+    receives the cut gradient as uint8 [B, R(fmt_out)] records, or as dense bf16 [B, ...] rows of 16,384 elements for
+    fmt_out = -1. Bitwise slk_cutmx_decode + slk_wide_head + slk_cutmx_encode; every buffer is the caller's, and both
+    flags (label_err, rec_err: int32 [1]) are required. Returns (out, loss_i, slabs)."""
+    B = int(rec.shape[0])
+    if fmt_in not in (0, 1) or fmt_out not in (-1, 0, 1):
+        raise ValueError(f"wide_head_mx: fmt_in={fmt_in!r} (expected 0 or 1), fmt_out={fmt_out!r} (expected -1, 0 or 1)")
+    width = lambda f: _lib.query("slk_cutmx_record_bytes", f)
+    if fmt_out < 0:
+        pout = _dev(out, "out", dtype=torch.bfloat16)
+        if out.dim() < 1 or out.shape[0] != B or out.numel() != B * 16384:
+            raise ValueError(f"out: expected {B} rows of 16384 elements, got {tuple(out.shape)}")
+    else:
+        pout = _dev(out, "out", (B, width(fmt_out)), torch.uint8)
+    for t, name in ((rec, "rec"), (out, "out"), (work, "work")):
+        if isinstance(t, torch.Tensor) and t.data_ptr() % 16:
+            raise ValueError(f"{name}: must be 16-byte aligned")
+    if work.numel() < wide_head_mx_work(B):
+        raise ValueError(f"work: expected at least {wide_head_mx_work(B)} floats, got {work.numel()}")
+    _lib.call("slk_wide_head_mx", _dev(rec, "rec", (B, width(fmt_in)), torch.uint8), int(fmt_in),
+              _dev(wf8, "wf8", (163840,)), _dev(bf, "fc.bias", (10,)), _labels(labels, B),
+              _dev(step, "step", (1,), torch.int32), int(seed) & 0xFFFFFFFF, int(keep_threshold) & 0xFFFFFFFF,
+              float(keep_scale), float(grad_scale), _dev(logits, "logits", (B, 10)), _dev(loss_i, "loss_i", (B,)),
+              _dev(dlogits, "dlogits", (B, 10)), pout, int(fmt_out),
+              _dev(slabs, "slabs", (_lib.query("slk_wide_head_nslab", B), 163850)), _dev(work, "work"),
+              _dev(label_err, "label_err", (1,), torch.int32), _dev(rec_err, "rec_err", (1,), torch.int32), int(b0), B,
+              _stream(rec))
+    return out, loss_i, slabs
+
+
 # ------------------------------------------------------------------------------------ distance correlation
 def dcor_workspace_bytes(n: int) -> int:
     """Bytes of the workspace slk_dcor needs for n samples."""

@@ -510,6 +510,7 @@ class WideServerStage(_AdamRecipe):
         self.wf8_ema = torch.empty_like(self.wf8) if self.ema is not None else None
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.eval_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)  # evaluate()'s own flag
+        self._rec_err_flag = None   # forward_backward_records' flag for malformed records (records_err_flag())
         self.eval_logits = None   # the logits of the last evaluate() (a stage buffer)
         self.loss_log = loss_log if loss_log is not None else LossLog(self.device)
         self._buf = _Buffers()
@@ -616,6 +617,50 @@ class WideServerStage(_AdamRecipe):
             ops.reduce_slabs(sf, out=self.grads, accumulate=k > 0)
         ops.loss_sum(loss_i, grad_scale, out=self._b("loss_parts", (nparts,), _F32)[k:k + 1])
         return dcut
+
+    # --- the same two calls on MX cut records (slk_wide_head_mx): no bf16 cut, no decode / encode launches
+    def records_err_flag(self):
+        """The int32 [1] flag forward_backward_records sets for a malformed record (made on first use)."""
+        if self._rec_err_flag is None:
+            self._rec_err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._rec_err_flag
+
+    def forward_backward_records(self, rec, fmt_in, labels, grad_scale, out, fmt_out, b0: int = 0):
+        """forward_backward reading the cut as MX records `rec` (uint8 [B, R], format name fmt_in: "e2m1" / "e4m3") and
+        writing the cut gradient into `out`: records of format fmt_out, or dense bf16 [B, 128, 8, 8, 8]-shaped rows
+        for fmt_out=None. Bitwise MxCut.decode -> forward_backward -> MxCut.encode, with the same stage buffers;
+        a malformed record sets records_err_flag(). Returns (out, loss_i, sf)."""
+        if self.loss is not None:
+            raise ValueError("WideServerStage: the head on MX records has no soft-target form (the stage was built "
+                             "with loss=)")
+        from .codec import CUTMX_FORMATS
+        for name, v, ok in (("fmt_in", fmt_in, CUTMX_FORMATS), ("fmt_out", fmt_out, (*CUTMX_FORMATS, None))):
+            if v not in ok:
+                raise ValueError(f"WideServerStage: {name}={v!r}; expected one of {sorted(CUTMX_FORMATS)}"
+                                 + (" or None" if name == "fmt_out" else ""))
+        B = rec.shape[0]
+        _dev(labels, "labels", (B,), torch.int64)
+        logits = self._b("logits", (B, 10), _F32)
+        loss_i = self._b("loss_i", (B,), _F32)
+        dlogits = self._b("dlogits", (B, 10), _F32)
+        sf = self._b("sf", (_q("slk_wide_head_nslab", B), SERVER_NPARAM), _F32)
+        work = self._b("work_mx", (ops.wide_head_mx_work(B),), _F32)
+        with TIMER("wide_head_mx"):
+            ops.wide_head_mx(rec, CUTMX_FORMATS[fmt_in], self.wf8, self.params[163840:], labels, self.step_ctr,
+                             self.seed, KEEP_THRESHOLD, KEEP_SCALE, grad_scale, logits, loss_i, dlogits, out,
+                             -1 if fmt_out is None else CUTMX_FORMATS[fmt_out], sf, work, self.err_flag,
+                             self.records_err_flag(), b0=b0)
+        self._logits, self._dlogits = logits, dlogits
+        return out, loss_i, sf
+
+    def accumulate_records(self, rec, fmt_in, labels, grad_scale: float, b0: int, k: int, nparts: int, out, fmt_out):
+        """accumulate on MX records (forward_backward_records): the fc gradient adds into self.grads, the part's loss
+        sum lands in loss part k of nparts. Returns `out`."""
+        out, loss_i, sf = self.forward_backward_records(rec, fmt_in, labels, grad_scale, out, fmt_out, b0=b0)
+        with TIMER("reduce_slabs"):
+            ops.reduce_slabs(sf, out=self.grads, accumulate=k > 0)
+        ops.loss_sum(loss_i, grad_scale, out=self._b("loss_parts", (nparts,), _F32)[k:k + 1])
+        return out
 
     def finish_step(self, nparts: int, step=None):
         """Adam from the accumulated gradient, loss logged (sum of the parts), step counter ticked."""
