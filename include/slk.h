@@ -1150,6 +1150,52 @@ int slk_dcor(const float* x, int dx, const void* z_bf16, int dz, int n, void* wo
 int64_t slk_dcor_grad_workspace_bytes(int n);
 int slk_dcor_grad(const float* x, int dx, const void* z_bf16, int dz, int n, const void* dcut_bf16, const float* alpha,
                   int squared, void* workspace, void* out_bf16, float* out4, void* stream);
+/* DP-SGD on the K5 client (csrc/slk_dpsgd.hip): Abadi et al. 2016 for the client's weights — clip every sample's
+ * gradient to an L2 norm of at most C, sum, add N(0, sigma^2 C^2). The client's backward is linear in the cut gradient,
+ * so the clipped per-sample gradient of every client parameter is the ordinary backward of coef_b * dcut_b
+ * (slk_cut_scale_rows with the stats below, then the existing kernels). What these entries add is the per-sample norm,
+ * the coefficient and the noise. Order inside a training step (wide.WideTrainer(dp=privacy.DPSGD(...))): the two dgrads
+ * on the unscaled dcut, slk_wide_grad_sqnorm, slk_dp_coef, slk_cut_scale_rows into a stage buffer, the whole backward on
+ * that scaled dcut, slk_dp_noise into one extra slab row per layer, the optimizer launch.
+ * slk_wide_grad_sqnorm: work[b][0..5] = the six partials of
+ *   sumsq_b = sum over conv1, conv2, conv3 of (sum dW_b^2 + sum db_b^2),
+ * dW3_b the weight gradient of (p2_b, dcut_b routed by code3_b), dW2_b of (a1_b, dp2_b routed by code2_b), dW1_b of
+ * (bf16(x_b), da1m_b), db the routed gradient's pixel sum: the operands of slk_wide_conv{3,2,1}_wgrad for sample b
+ * alone, dp2 and da1m as slk_wide_conv3_dgrad / slk_wide_conv2_dgrad stored them for the same dcut. A code outside 0..3
+ * routes nowhere. bf16 operands, v_mfma_f32_16x16x32_bf16 with float32 accumulation: an element of dW_b is one
+ * accumulator chain over the sample's pixels ascending in steps of 32 (row-major; the order inside an instruction is the
+ * hardware's) and is never stored. Partial 0 is conv1 (64 x 28: column 27 is db1), partial 1 conv2, partials 2..5 conv3's
+ * blocks (co half, ci half) = 00, 01, 10, 11; db rides in the blocks of ci half 0. Inside a block every lane adds
+ * fl(v * v) of its accumulator elements one at a time from 0 — M tile ascending, then tap (conv1: column tile), then the
+ * instruction's four registers, then its db elements — each operation rounded on its own; the xor butterfly
+ * a = a + shfl_xor(a, o) runs for o = 32, 16, 8, 4, 2, 1 inside each wave and thread 0 adds the waves' sums in ascending
+ * wave order. No atomics: a partial is a fixed function of its own sample, so a NaN in one row of dcut stays in that
+ * row. layers selects what runs (bit 0 conv1, bit 1 conv2, bit 2 conv3; 7 = all; the partials of a layer left out are
+ * not written). work = slk_wide_grad_sqnorm_work(B) = 6 B floats.
+ * slk_dp_coef: s = the sample's six partials added in ascending order in float64 and rounded once to float32;
+ *   norm = fl(unit * sqrtf(s));  coef = fl(*max_norm / fl(norm + 1e-6f)) where that compares less than 1, else 1,
+ * so a NaN norm gives 1, an infinite one 0 and a zero one 1 (Opacus' and optim.ClipNorm's formula as a compare).
+ * unit is by value: 1 / grad_scale, i.e. B for the mean loss, so the norm is that of the per-sample loss's gradient.
+ * max_norm (C) is a device f32[1]. stats[b] = (norm, coef), f32 pairs in slk_cut_scale_rows' layout.
+ * slk_dp_noise: out[i] = fl(std * z(seed, *step, i0 + i)), i < n, with std = fl(fl(*sigma * *max_norm) * grad_scale)
+ * and exactly 0 where *sigma == 0. All uint32 arithmetic, j = i0 + i the index in the client's flat parameter block
+ * (a draw does not depend on slab shapes, and a slice launched with its own i0 gives the slice of the whole launch):
+ *   h0 = lowbias32(j * 0x9E3779B1 + step * 0x85EBCA77 + seed * 0xC2B2AE3D);   h1 = lowbias32(h0 + 0x9E3779B9)
+ *   u1 = ((h0 >> 9) + 0.5) * 2^-23;   u2 = (h1 >> 8) * 2^-24          (both exact in float32)
+ *   z  = fl(sqrtf(fl(-2 * logf(u1))) * cospif(fl(2 * u2)))
+ * Box-Muller's cosine branch on a counter-based hash: the support ends at sqrt(48 ln 2) = 5.77, u1 has 23 bits and
+ * u2 24, and lowbias32 is not a cryptographic generator. sigma and max_norm are device f32[1], step a device int32[1]
+ * read as uint32 and never written, so a captured graph follows all three.
+ * B == 0 / n == 0 launches nothing and returns 0. Refused with hipErrorInvalidValue before any launch: a negative count,
+ * layers outside 0..7, i0 < 0 or i0 + n > 2^32, a NULL pointer, a bf16 tensor not 16-byte aligned, a code tensor or
+ * stats not 8-byte aligned, any other pointer not 4-byte aligned. */
+int slk_wide_grad_sqnorm_work(int B);
+int slk_wide_grad_sqnorm(const float* x, const uint16_t* da1m, const uint16_t* a1, const uint16_t* dp2,
+                         const uint8_t* code2, const uint16_t* p2, const uint16_t* dcut, const uint8_t* code3,
+                         float* work, int layers, int B, void* stream);
+int slk_dp_coef(const float* work, int n, float unit, const float* max_norm, float* stats, void* stream);
+int slk_dp_noise(float* out, int n, int64_t i0, const float* sigma, const float* max_norm, float grad_scale,
+                 unsigned seed, const int* step, void* stream);
 /* Rebuild the bf16 weight shadows from the f32 masters: w1b [64][32] (W1 rows, k >= 27 zero) and the
  * MFMA layouts of W2 [128,64,3,3] and W3 [256,128,3,3]. */
 int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t* w1b, uint16_t* w2f, uint16_t* w2d,

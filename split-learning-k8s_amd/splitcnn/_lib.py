@@ -144,6 +144,11 @@ _SIGS = {
     # its gradient on the cut (privacy.DcorLoss)
     "slk_dcor_grad_workspace_bytes": [_I],
     "slk_dcor_grad": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P],
+    # DP-SGD on the K5 client (privacy.DPSGD): per-sample gradient norms, clip coefficients, the noise row
+    "slk_wide_grad_sqnorm_work": [_I],
+    "slk_wide_grad_sqnorm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "slk_dp_coef": [_P, _I, _F, _P, _P, _P],
+    "slk_dp_noise": [_P, _I, _L, _P, _P, _F, _U, _P, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

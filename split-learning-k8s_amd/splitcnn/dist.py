@@ -109,6 +109,9 @@ def _default_optimizer_only(who: str, *stages) -> None:
         if getattr(st, "ema", None) is not None:
             raise ValueError(f"dist.{who}: {type(st).__name__} carries an averaged copy of its parameters (optim.EMA); "
                              "the multi-GPU classes do not launch its update — build the stage without ema=")
+        if getattr(st, "dp", None) is not None:
+            raise ValueError(f"dist.{who}: {type(st).__name__} carries DP-SGD (privacy.DPSGD); the multi-GPU classes "
+                             "average gradients across clients and do not account for it — build the stage without dp=")
         if any(getattr(st, a, None) is not None for a in ("optim", "schedule", "clip")):
             raise ValueError(f"dist.{who}: {type(st).__name__} carries an optimizer config / learning-rate schedule "
                              "/ gradient clipping (splitcnn.optim); the multi-GPU classes take only the default "

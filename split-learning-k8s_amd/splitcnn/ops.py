@@ -1105,3 +1105,44 @@ def dcor_grad(x, z, dcut, alpha, squared, workspace, out, out4):
               _dev(workspace, "workspace", dtype=torch.uint8), _dev(out, "out", (n, dz), torch.bfloat16),
               _dev(out4, "out4", (4,)), _stream(x))
     return out
+
+
+# ------------------------------------------------------------------------------------ DP-SGD on the K5 client
+def wide_grad_sqnorm_work(B: int) -> int:
+    """Floats of the work buffer slk_wide_grad_sqnorm fills for B samples (six partials a sample)."""
+    return _lib.query("slk_wide_grad_sqnorm_work", int(B))
+
+
+def wide_grad_sqnorm(x, da1m, a1, dp2, code2, p2, dcut, code3, work=None, layers: int = 7):
+    """work (f32 [B, 6]) = the partials of every sample's squared client-gradient norm — slk_wide_grad_sqnorm on the
+    tensors the unscaled backward reads and leaves (C8 bf16 activations and gradients, uint8 routing codes). `layers`
+    (bit 0 conv1, 1 conv2, 2 conv3) leaves the other layers' partials unwritten."""
+    B = int(x.shape[0])
+    bf, u8 = torch.bfloat16, torch.uint8
+    work = _out(work, (B, 6), x, name="work")
+    _lib.call("slk_wide_grad_sqnorm", _dev(x, "x", (B, 3, 32, 32)), _dev(da1m, "da1m", (B, 8, 32, 32, 8), bf),
+              _dev(a1, "a1", (B, 8, 32, 32, 8), bf), _dev(dp2, "dp2", (B, 16, 16, 16, 8), bf),
+              _dev(code2, "code2", (B, 16, 16, 16, 8), u8), _dev(p2, "p2", (B, 16, 16, 16, 8), bf),
+              _dev(dcut, "dcut", (B, 32, 8, 8, 8), bf), _dev(code3, "code3", (B, 32, 8, 8, 8), u8), work.data_ptr(),
+              int(layers), B, _stream(x))
+    return work
+
+
+def dp_coef(work, unit, max_norm, stats=None):
+    """stats (f32 [n, 2]) = (norm, coef) of every sample from its partials — slk_dp_coef; `unit` by value, max_norm a
+    device f32 [1]."""
+    n = int(work.shape[0])
+    stats = _out(stats, (n, 2), work, name="stats")
+    _lib.call("slk_dp_coef", _dev(work, "work", (n, 6)), n, float(unit), _dev(max_norm, "max_norm", (1,)),
+              stats.data_ptr(), _stream(work))
+    return stats
+
+
+def dp_noise(out, i0, sigma, max_norm, grad_scale, seed, step):
+    """out (f32 [n]) = sigma * C * grad_scale * z(seed, step, i0 + i) — slk_dp_noise; sigma, max_norm device f32 [1],
+    step a device int32 [1], i0 the index of out[0] in the client's flat parameter block."""
+    n = int(out.numel())
+    _lib.call("slk_dp_noise", _dev(out, "out", (n,)), n, int(i0), _dev(sigma, "sigma", (1,)),
+              _dev(max_norm, "max_norm", (1,)), float(grad_scale), int(seed), _dev(step, "step", (1,), torch.int32),
+              _stream(out))
+    return out

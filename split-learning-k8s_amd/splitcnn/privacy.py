@@ -242,6 +242,123 @@ def check_cut_noise(noise):
     return noise
 
 
+# ------------------------------------------------------------------------------------ DP-SGD on the client's weights
+DP_ORDERS = tuple(range(2, 257))   # the integer Renyi orders the accountant minimises over
+
+
+class DPSGD:
+    """DP-SGD (Abadi et al. 2016) on the K5 client's weights, as a config of WideClientStage / WideTrainer(dp=...):
+    every sample's client gradient is clipped to an L2 norm of at most `max_grad_norm` (C), the clipped gradients are
+    summed and N(0, (noise_multiplier * C)^2) is added to the sum (include/slk.h, "DP-SGD on the K5 client").
+
+    C and sigma live in device f32[1] scalars the kernels read, so a captured HIP graph follows `set_max_grad_norm` /
+    `set_noise_multiplier` without being recaptured. `seed` is passed by value: a captured graph keeps it. A stage
+    built with noise_multiplier == 0 has no noise row at all (a later set_noise_multiplier raises); max_grad_norm=inf
+    clips nothing but still measures the norms.
+
+    The stage takes the cut gradient of the MEAN loss over its batch (grad_scale = 1 / B, what WideTrainer and
+    WideServerStage.step_request hand it): norms are reported as B x the measured ones and the noise is scaled by 1 / B.
+    A dcut at any other scale is clipped and noised at the wrong sensitivity, without an error.
+
+    Deviations: the clipped gradient is the backward of bf16(coef_b * dcut_b), so the sensitivity bound holds up to
+    bf16 rounding; the norm is measured on the unscaled pass; the Gaussian's support ends at 5.77 sigma; only the
+    client stage is covered (the server is the other party, with its own optimizer)."""
+
+    def __init__(self, max_grad_norm: float, noise_multiplier: float, seed: int = 0, device="cuda"):
+        self.max_grad_norm = self._checked_norm(max_grad_norm)
+        self.noise_multiplier = self._checked_sigma(noise_multiplier)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"DPSGD: seed={seed!r}; expected an integer in [0, 2^32)")
+        self.seed = int(seed)
+        self.noisy = self.noise_multiplier > 0.0
+        self.norm_value = torch.full((1,), self.max_grad_norm, dtype=torch.float32, device=device)
+        self.sigma_value = torch.full((1,), self.noise_multiplier, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _checked_norm(c) -> float:
+        if not _number(c) or not c > 0.0:   # NaN fails this too
+            raise ValueError(f"DPSGD: max_grad_norm={c!r}; expected a number > 0 (inf clips nothing)")
+        return float(c)
+
+    @staticmethod
+    def _checked_sigma(s) -> float:
+        if not _number(s) or not 0.0 <= s < math.inf:   # NaN fails this too
+            raise ValueError(f"DPSGD: noise_multiplier={s!r}; expected a finite number >= 0")
+        return float(s)
+
+    def to(self, device) -> "DPSGD":
+        """Move the scalars (a no-op on their own device); captured graphs hold their addresses, so move a DPSGD
+        before the first step only."""
+        if self.norm_value.device != torch.device(device):
+            self.norm_value, self.sigma_value = self.norm_value.to(device), self.sigma_value.to(device)
+        return self
+
+    def set_max_grad_norm(self, c: float) -> None:
+        """Overwrite C in place: an asynchronous device write on the current stream, so the next launch — eager or a
+        replay of an already captured graph — clips at `c`."""
+        self.max_grad_norm = self._checked_norm(c)
+        self.norm_value.fill_(self.max_grad_norm)
+
+    def set_noise_multiplier(self, sigma: float) -> None:
+        """Overwrite sigma in place, like set_max_grad_norm. A DPSGD built with noise_multiplier == 0 has no noise
+        row to retarget."""
+        if not self.noisy:
+            raise RuntimeError("DPSGD: built with noise_multiplier == 0 — there is no noise launch to retarget; "
+                               "build one with noise_multiplier > 0")
+        self.noise_multiplier = self._checked_sigma(sigma)
+        self.sigma_value.fill_(self.noise_multiplier)
+
+    def __repr__(self):
+        return (f"DPSGD(max_grad_norm={self.max_grad_norm}, noise_multiplier={self.noise_multiplier}, "
+                f"seed={self.seed})")
+
+    def noise_draws(self, idx, step: int) -> np.ndarray:
+        """The host twin of slk_dp_noise's unit draws z for the flat parameter indices `idx` at counter value `step`,
+        in float64 on the kernel's own integers (the kernel evaluates the same expression in float32)."""
+        j = np.asarray(idx, dtype=np.uint64) & _M32
+        key = ((int(step) & _M32) * 0x85EBCA77 + self.seed * 0xC2B2AE3D) & _M32
+        h0 = _hash32((j * 0x9E3779B1 + key) & _M32)
+        h1 = _hash32((h0 + 0x9E3779B9) & _M32)
+        u1 = ((h0 >> 9).astype(np.float64) + 0.5) * 2.0 ** -23
+        u2 = (h1 >> 8).astype(np.float64) * 2.0 ** -24
+        return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+    def epsilon(self, steps: int, sample_rate: float, delta: float) -> float:
+        """epsilon of (epsilon, delta)-DP after `steps` steps at this noise multiplier: the Renyi-DP accountant of the
+        subsampled Gaussian mechanism over the integer orders DP_ORDERS (Mironov, Talwar, Zhang 2019, the binomial
+        expansion), composed over the steps and converted as eps = min_a (steps * rdp(a) + log(1 / delta) / (a - 1)).
+        It ASSUMES Poisson sampling at `sample_rate` while the loaders here shuffle and cut fixed-size batches (Opacus
+        carries the same caveat), and it knows nothing of the bf16 rounding of the clipped gradient or of the noise's
+        finite support. Infinite for noise_multiplier == 0."""
+        if not 0.0 < sample_rate <= 1.0 or not 0.0 < delta < 1.0 or steps < 0:
+            raise ValueError("epsilon: expected steps >= 0, 0 < sample_rate <= 1 and 0 < delta < 1")
+        return rdp_epsilon(self.noise_multiplier, steps, sample_rate, delta)
+
+
+def subsampled_gaussian_rdp(sigma: float, q: float, alpha: int) -> float:
+    """Renyi divergence of order alpha (an integer >= 2) of one step of the Poisson-subsampled Gaussian mechanism:
+    log(sum_i C(alpha, i) (1 - q)^(alpha - i) q^i exp((i^2 - i) / (2 sigma^2))) / (alpha - 1), in log space."""
+    i = np.arange(alpha + 1, dtype=np.float64)
+    logc = np.array([math.lgamma(alpha + 1) - math.lgamma(k + 1) - math.lgamma(alpha - k + 1) for k in range(alpha + 1)])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rest = np.where(alpha - i > 0, (alpha - i) * np.log1p(-q), 0.0)
+    terms = logc + rest + i * math.log(q) + (i * i - i) / (2.0 * sigma * sigma)
+    return float(np.logaddexp.reduce(terms)) / (alpha - 1)
+
+
+def rdp_epsilon(sigma: float, steps: int, sample_rate: float, delta: float, orders=DP_ORDERS) -> float:
+    if sigma <= 0.0:
+        return math.inf
+    return min(steps * subsampled_gaussian_rdp(sigma, sample_rate, a) + math.log(1.0 / delta) / (a - 1) for a in orders)
+
+
+def check_dpsgd(dp):
+    """A stage's / trainer's dp argument: a DPSGD or None."""
+    if dp is not None and not isinstance(dp, DPSGD):
+        raise TypeError(f"expected splitcnn.privacy.DPSGD or None, got {type(dp).__name__}")
+    return dp
+
+
 # ------------------------------------------------------------------------------------ what a defence buys
 class DistanceCorrelation:
     """The four numbers of one distance_correlation call: dcor, dcov2, dvar_x, dvar_z (Python floats). They are read

@@ -37,9 +37,9 @@ from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
 from .ops import _dev, _stream
-from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema
-from .privacy import (CutNoise, DcorLoss, DistanceCorrelation, check_cut_noise, check_dcor_loss,
-                      distance_correlation)
+from .optim import EMA, Adam, ClipNorm, LRSchedule, check_clip, check_ema, is_layerwise
+from .privacy import (DPSGD, CutNoise, DcorLoss, DistanceCorrelation, check_cut_noise, check_dcor_loss,
+                      check_dpsgd, distance_correlation)
 from .recipe import Seg, StageRecipe, _flatten_params
 
 P_DROP = 0.25
@@ -378,7 +378,9 @@ class _AdamRecipe(StageRecipe):
 
 class WideClientStage(_AdamRecipe):
     """Client half: forward(x) -> cut (bf16 C8); backward_step(dcut) = activations.backward(grads) +
-    Adam (client_part.py:114,132-133 for the widened model)."""
+    Adam (client_part.py:114,132-133 for the widened model). With dp= (privacy.DPSGD) the backward clips every sample's
+    gradient and appends the noise rows; it takes dcut as the gradient of the MEAN loss over the batch (grad_scale =
+    1 / B): at any other scale the clip and the noise sit at the wrong sensitivity, and nothing can detect it."""
 
     OFF = {"W1": 0, "b1": 1728, "W2": 1792, "b2": 75520, "W3": 75648, "b3": 370560}
     PAIRS = ((0, 1792, 1728), (1792, 75648, 73728), (75648, CLIENT_NPARAM, 294912))
@@ -386,8 +388,18 @@ class WideClientStage(_AdamRecipe):
 
     def __init__(self, model: Optional[WideModelPartA] = None, device="cuda", lr=LR, betas=(BETA1, BETA2),
                  eps=EPS, optim: Optional[Adam] = None, schedule: Optional[LRSchedule] = None,
-                 clip: Optional[ClipNorm] = None, ema: Optional[EMA] = None):
+                 clip: Optional[ClipNorm] = None, ema: Optional[EMA] = None, dp: Optional[DPSGD] = None):
         self.device = torch.device(device)
+        # dp=privacy.DPSGD: backward_slabs clips every sample's gradient and appends the noise row (_dp_backward)
+        self.dp, self._dp_B = check_dpsgd(dp), None
+        if dp is not None:
+            if clip is not None:
+                raise ValueError("WideClientStage: dp= is not combined with clip= (the global-norm clip would rescale "
+                                 "the noised sum and with it the noise multiplier)")
+            if is_layerwise(optim):
+                raise ValueError(f"WideClientStage: dp= is not combined with {type(optim).__name__} (a trust ratio "
+                                 "computed from the private gradient's norm is not accounted for)")
+            dp.to(self.device)
         self.model = (model if model is not None else WideModelPartA()).to(self.device)
         m = self.model
         self.params, self.grads = _flatten_params([m.conv1.weight, m.conv1.bias, m.conv2.weight, m.conv2.bias,
@@ -441,14 +453,60 @@ class WideClientStage(_AdamRecipe):
         return cut
 
     def backward_slabs(self, dcut: torch.Tensor, tag=""):
-        """Client backward into three slab sets (conv1, conv2, conv3); returns them."""
+        """Client backward into three slab sets (conv1, conv2, conv3); returns them. With dp= the sets are those of
+        the clipped per-sample gradients, each with one more row of noise behind it where sigma > 0 (_dp_backward)."""
         B = self._saved[tag][0].shape[0]
         self._x, self._a1, self._p2, self._code2, self._code3 = self._saved[tag][:5]
         scratch = client_backward_scratch(B, self._b)
+        if self.dp is not None:
+            return self._dp_backward(dcut, self._saved[tag], scratch)
         s1, s2, s3 = (self._b(n, shp, _F32) for n, shp in zip(("s1", "s2", "s3"), client_backward_slab_shapes(B)))
         client_backward_kernels(dcut, self._saved[tag], self.sh["w2d"], self.sh["w3d"], scratch, s1, s2, s3)
         self._dp2, self._da1m = scratch
         return s1, s2, s3
+
+    def _dp_backward(self, dcut, saved, scratch):
+        """DP-SGD's backward (include/slk.h, "DP-SGD on the K5 client") for the mean loss (grad_scale = 1 / B): the
+        two dgrads on the unscaled dcut, every sample's gradient norm and coefficient (dp_stats), dcut scaled per row
+        into a stage buffer, the whole backward on it, then the noise row of each slab set under this stage's
+        step_ctr (read before its tick). No host sync."""
+        dp = self.dp
+        x, a1, p2, code2, code3, a1bits = saved
+        dp2, da1m = scratch
+        B = x.shape[0]
+        s = _stream(dp2)
+        _dev(dcut, "dcut", (B,) + CUT_SHAPE, _BF)
+        _k("wide_conv3_dgrad", dcut.data_ptr(), code3.data_ptr(), self.sh["w3d"].data_ptr(), dp2.data_ptr(), B, s)
+        _k("wide_conv2_dgrad", dp2.data_ptr(), code2.data_ptr(), self.sh["w2d"].data_ptr(), a1bits.data_ptr(),
+           da1m.data_ptr(), B, s)
+        with TIMER("wide_grad_sqnorm"):
+            work = ops.wide_grad_sqnorm(x, da1m, a1, dp2, code2, p2, dcut, code3, work=self._b("dp_work", (B, 6), _F32))
+        stats = self._b("dp_stats", (B, 2), _F32)
+        with TIMER("dp_coef"):
+            ops.dp_coef(work, float(B), dp.norm_value, stats)
+        scaled = self._b("dcut_dp", (B,) + CUT_SHAPE, _BF)
+        _k("cut_scale_rows", dcut.data_ptr(), B, stats.data_ptr(), scaled.data_ptr(), s)
+        extra = 1 if dp.noisy else 0
+        sets = [self._b(n, (ns + extra, w), _F32) for n, (ns, w) in zip(("s1_dp", "s2_dp", "s3_dp"),
+                                                                     client_backward_slab_shapes(B))]
+        client_backward_kernels(scaled, saved, self.sh["w2d"], self.sh["w3d"], scratch, *(t[:t.shape[0] - extra]
+                                                                                           for t in sets))
+        if extra:
+            for (lo, _, _), t in zip(self.PAIRS, sets):
+                with TIMER("dp_noise"):
+                    ops.dp_noise(t[-1], lo, dp.sigma_value, dp.norm_value, 1.0 / B, dp.seed, self.step_ctr)
+        self._dp2, self._da1m = scratch
+        self._dp_B = B
+        return tuple(sets)
+
+    def dp_stats(self) -> torch.Tensor:
+        """f32 [B, 2] on the host: (norm, coef) of every sample of the last backward — the L2 norm of its own client
+        gradient (of the per-sample loss) and the coefficient applied (1.0: not clipped). One host sync. Needs dp=."""
+        if self.dp is None:
+            raise RuntimeError("dp_stats: the stage was built without dp= (privacy.DPSGD)")
+        if self._dp_B is None:
+            raise RuntimeError("dp_stats: no training step has run yet")
+        return self._b("dp_stats", (self._dp_B, 2), _F32).cpu()
 
     def _slab_segments(self, s1, s2, s3):
         """The three slab sets, [conv1 | conv2 | conv3], as (lo, hi, slabs) slices: the stage's PAIRS."""
@@ -474,6 +532,9 @@ class WideClientStage(_AdamRecipe):
     def backward_grads(self, dcut: torch.Tensor, tag="", accumulate: bool = False):
         """activations.backward(grads) into the flat gradient block (fixed-order slab reduction);
         accumulate=True adds (micro-batches of one step)."""
+        if accumulate and self.dp is not None:
+            raise ValueError("WideClientStage: backward_grads(accumulate=True) is not combined with dp= (every "
+                             "micro-batch would add its own noise row at its own 1 / B)")
         for lo, hi, sl in self._slab_segments(*self.backward_slabs(dcut, tag)):
             with TIMER("reduce_slabs"):
                 ops.reduce_slabs(sl, out=self.grads[lo:hi], accumulate=accumulate)
@@ -723,7 +784,17 @@ class WideTrainer(GraphedTrainer):
     forward output, before the clip, the noise and any codec) and back-propagates the sum, inside the captured step.
     DcorLoss.set_alpha reaches a captured graph; `squared` is a by-value constant it keeps. leak_stats() reads the
     last step's distance correlation of (x, raw cut). The logged loss stays the task loss. leak_loss=None launches
-    nothing new."""
+    nothing new.
+
+    `dp` (privacy.DPSGD) runs DP-SGD on the client's weights, inside the captured step with no host sync: the client's
+    backward measures every sample's own gradient norm (slk_wide_grad_sqnorm, slk_dp_coef), scales the cut gradient
+    per row (slk_cut_scale_rows), back-propagates it as before and appends one row of N(0, (sigma C / B)^2) noise
+    (slk_dp_noise) to each layer's slab set, keyed on the client's step_ctr read before its tick, so
+    load_optimizer_state reproduces the bits; the optimizer launch is unchanged. DPSGD.set_max_grad_norm /
+    set_noise_multiplier reach a captured graph; the seed is a by-value constant it keeps. It combines with optim=,
+    schedule=, ema=, loss=, cut_codec= and cut_noise=, which all act before the client's backward, and raises
+    ValueError with leak_loss=, clip= and a LAMB config. dp_stats() reads the last step's (norm, coef) per sample. The
+    server stage is not covered. dp=None launches nothing new."""
 
     input_shape = (3, 32, 32)
 
@@ -732,9 +803,12 @@ class WideTrainer(GraphedTrainer):
                  schedule: Optional[LRSchedule] = None, clip: Optional[ClipNorm] = None,
                  loss: Optional[SoftCrossEntropy] = None, ema: Optional[EMA] = None,
                  cut_codec: Union[Fp8Cut, MxCut, TopKCut, None] = None, cut_noise: Optional[CutNoise] = None,
-                 leak_loss: Optional[DcorLoss] = None):
+                 leak_loss: Optional[DcorLoss] = None, dp: Optional[DPSGD] = None):
         check_clip(clip)
         check_ema(ema)
+        if check_dpsgd(dp) is not None and leak_loss is not None:
+            raise ValueError("WideTrainer: dp= is not combined with leak_loss= (the distance-correlation term couples "
+                             "the samples of a batch, so no per-sample gradient and no per-sample sensitivity exist)")
         self.cut_codec = check_cut_codec(cut_codec)
         self.cut_noise = check_cut_noise(cut_noise)
         super().__init__(device, graph)
@@ -745,7 +819,7 @@ class WideTrainer(GraphedTrainer):
         if self.leak_loss is not None:
             self.leak_loss.to(self.device)
             self._leak_stats = torch.zeros(4, dtype=_F32, device=self.device)
-        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema)
+        self.client = WideClientStage(client, self.device, optim=optim, schedule=schedule, clip=clip, ema=ema, dp=dp)
         self.server = WideServerStage(server, self.device, seed=seed, optim=self.client.optim,
                                       schedule=self.client.schedule, clip=self.client.clip, loss=loss,
                                       ema=self.client.ema_cfg)
@@ -814,6 +888,13 @@ class WideTrainer(GraphedTrainer):
         if self._cut_stats_B is None:
             raise RuntimeError("leak_stats: no training step has run yet")
         return DistanceCorrelation(self._leak_stats.clone())
+
+    def dp_stats(self) -> torch.Tensor:
+        """f32 [B, 2] on the host: (norm, coef) of every sample of the last training step — the L2 norm of the sample's
+        own client gradient and the clip coefficient applied (WideClientStage.dp_stats). One host sync. Needs dp=."""
+        if self.client.dp is not None and self._cut_stats_B is not None:
+            self.client._dp_B = self._cut_stats_B   # a replayed graph wrote the buffers of its own batch size
+        return self.client.dp_stats()
 
     def step(self, x, y):
         self._cut_stats_B = int(x.shape[0])   # which of the per-batch-size stats buffers the last step wrote
