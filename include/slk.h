@@ -1202,6 +1202,58 @@ int slk_wide_shadows(const float* W1, const float* W2, const float* W3, uint16_t
                      uint16_t* w3f, uint16_t* w3d, void* stream);
 /* wf8[j][(plane*64+pix)*8+k] = Wf[j][(plane*8+k)*64+pix]: the fc weight in the cut's C8 order. */
 int slk_wide_fc_shadow(const float* wf, float* wf8, void* stream);
+/* ---------------------------------------------------------------- The n-class head
+ * The K5 server head for nc classes, 2 <= nc <= 128 (CIFAR-100): Dropout(0.25) -> flatten -> Linear(16384, nc) ->
+ * CrossEntropyLoss, forward and backward, as three bf16 GEMMs on v_mfma_f32_16x16x32_bf16 (csrc/slk_wide_headn.hip).
+ * The 10-class entries above are unchanged; this family is what wide.WideServerStage launches at any other class
+ * count. A reference reproduces it from this rule alone (tests/headn_ref.py does):
+ *   Weights   wq_jf = bf16(Wf_jf), round to nearest even: a shadow rebuilt after every optimizer step
+ *             (slk_wide_fcn_shadow). DEVIATION from the 10-class head, which reads Wf in float32. The buffer is
+ *             2 x 128 x 16384 bf16 (8 MiB, 16-byte aligned): wq[j][(plane*64+pix)*8+k] = bf16(Wf[j][(plane*8+k)*64+pix])
+ *             (the cut's C8 order, rows nc..127 zero) followed by its transpose [16384][128], which the cut gradient reads.
+ *   Dropout   m_f = keep bit of (seed, *step, b0 + b, torch feature index f): slk_wide_head's hash, unchanged, so a step
+ *             draws the same mask at any class count. keep_threshold 0 keeps every element.
+ *   Logits    z_j = fl(keep_scale * S_j) + bf_j,  S_j = sum_f m_f c_f wq_jf. The products are exact and are added in
+ *             float32 on the MFMA. keep_scale multiplies the finished sum ONCE, not every element (the 10-class head
+ *             scales the elements): the A operand stays the cut's own bf16 bits. Order of the sum: 8 slices of 2048
+ *             consecutive C8 elements; inside a slice 64 K steps of 32 elements in ascending order, each one
+ *             v_mfma_f32_16x16x32_bf16 onto the running accumulator; then the 8 slice sums added in ascending order.
+ *   Loss      m = max_j z_j; se = sum_j expf(z_j - m) over ascending j from 0; lse = m + logf(se); loss_i = lse - z_y;
+ *             dlogits_j = fl(fl(expf(z_j - lse) - [j == y]) * grad_scale), float32 [B][nc]: slk_wide_head's expressions
+ *             over nc classes. A label outside [0, nc) sets *err_flag and makes that row's loss_i and dlogits NaN.
+ *   Backward  both backward GEMMs read dlq = bf16(dlogits) (the stored dlogits stays float32). DEVIATION of the size
+ *             of the bf16 dcut it produces.
+ *   dcut_f    = m_f ? bf16(fl(keep_scale * sum_j dlq_j wq_jf)) : +0, j ascending in 4 K steps of 32 classes.
+ *   dWf_jf    = fl(keep_scale * sum_b dlq_bj m_bf c_bf),  dbf_j = sum_b dlq_bj, per slab: slab s sums samples
+ *             256 s .. 256 s + 255 in ascending K steps of 32. A slab is [nc * 16384 | nc] float32 in torch's parameter
+ *             order, so slk_reduce_slabs and slk_adam*_from_slabs take the set as it is; slk_wide_headn_nslab(B) =
+ *             ceil(B / 256) (16 at B = 4096).
+ * work: slk_wide_headn_work(B) floats, 16-byte aligned; the forward leaves the slice sums there, the backward its bf16
+ * dlogits (neither reads what the other wrote: slk_wide_headn_bwd re-derives the mask from the hash and takes dlogits
+ * as an argument, so it can run on operands of the caller's choosing). cut, dcut: bf16 C8 [B][16384], 16-byte aligned.
+ * slk_wide_headn_fwd has two forms. Training: labels, loss_i, dlogits and err_flag all given. Logits only (predict,
+ * evaluate, the module's forward): those four all NULL, nothing but logits [B][nc] is written. Any other mix is refused.
+ * slk_eval_logits_n / slk_eval_accumulate_n follow slk_eval_logits / slk_eval_accumulate word for word over nc
+ * classes (first maximum on ties, NaN as the maximum, float64 loss sum in the same fixed order; at nc = 10 the same
+ * bits): logits f32 [B][nc]; acc holds 4 + nc * nc words, acc[4 + nc * label + pred] the confusion counts. In
+ * slk_eval_logits_n labels, loss_i and err_flag are given together or all NULL (predict only).
+ * Refused with hipErrorInvalidValue before any launch: nc < 1 or nc > 128, a negative count, a NULL or misaligned
+ * pointer. B == 0 (nc == 0 for the shadow) launches nothing and returns 0. nc = 1, a head with one constant class
+ * (loss 0), is served too: the Python layer is what holds the class count to 2..128. */
+int slk_wide_fcn_shadow(const float* wf, int nc, uint16_t* wq, void* stream);
+int slk_wide_headn_fwd(const uint16_t* cut, const uint16_t* wq, const float* bf, int nc, const int64_t* labels,
+                       const int* step, unsigned seed, unsigned keep_threshold, float keep_scale, float grad_scale,
+                       float* logits, float* loss_i, float* dlogits, float* work, int* err_flag, int b0, int B,
+                       void* stream);
+int slk_wide_headn_bwd(const uint16_t* cut, const uint16_t* wq, const float* dlogits, int nc, const int* step,
+                       unsigned seed, unsigned keep_threshold, float keep_scale, uint16_t* dcut, float* slabs,
+                       float* work, int b0, int B, void* stream);
+int slk_wide_headn_nslab(int B);
+int slk_wide_headn_work(int B);
+int slk_eval_logits_n(const float* logits, int nc, const int64_t* labels, int B, float* loss_i, int64_t* pred,
+                      int* err_flag, void* stream);
+int slk_eval_accumulate_n(const float* loss_i, const int64_t* pred, const int64_t* labels, int nc, int B, int64_t* acc,
+                          void* stream);
 /* ++*counter on the device (the per-stage step counter a captured HIP graph advances). A step counter stays in
  * [0, 2^31 - 2] (see slk_sgdm_from_slabs): ticking one that already holds 2^31 - 2 leaves it at INT_MAX, which no
  * optimizer entry accepts, and one more tick overflows the int. */

@@ -149,6 +149,14 @@ _SIGS = {
     "slk_wide_grad_sqnorm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "slk_dp_coef": [_P, _I, _F, _P, _P, _P],
     "slk_dp_noise": [_P, _I, _L, _P, _P, _F, _U, _P, _P],
+    # the K5 head for 2..128 classes (wide.WideServerStage at num_classes != 10) and its evaluation kernels
+    "slk_wide_fcn_shadow": [_P, _I, _P, _P],
+    "slk_wide_headn_fwd": [_P, _P, _P, _I, _P, _P, _U, _U, _F, _F, _P, _P, _P, _P, _P, _I, _I, _P],
+    "slk_wide_headn_bwd": [_P, _P, _P, _I, _P, _U, _U, _F, _P, _P, _P, _I, _I, _P],
+    "slk_wide_headn_nslab": [_I],
+    "slk_wide_headn_work": [_I],
+    "slk_eval_logits_n": [_P, _I, _P, _I, _P, _P, _P, _P],
+    "slk_eval_accumulate_n": [_P, _P, _P, _I, _I, _P, _P],
     "slk_mnist_batch": [_P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P],
     "slk_image_batch": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _U, _U, _P, _P, _P, _P],
     # widened split CNN (BASELINE config 5)

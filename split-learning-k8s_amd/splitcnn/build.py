@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libslk.so")
 SOURCES = ["slk_client.hip", "slk_server.hip", "slk_optim.hip", "slk_data.hip", "slk_wide.hip",
            "slk_wide_head.hip", "slk_wino.hip", "slk_codec.hip", "slk_x3.hip", "slk_eval.hip", "slk_ema.hip",
            "slk_cut8.hip", "slk_cut_noise.hip", "slk_cutmx.hip", "slk_dcor.hip", "slk_cuttopk.hip",
-           "slk_wide_head_mx.hip", "slk_dpsgd.hip"]
+           "slk_wide_head_mx.hip", "slk_dpsgd.hip", "slk_wide_headn.hip"]
 ARCH = "gfx950"
 # Per-source extra hipcc flags (tools/build_variant.sh passes -D defines). slk_dcor.hip keeps the compiler from
 # pairing its float32 epilogue into packed-fp32 instructions; slk_cuttopk.hip (integer code) is built the same way.

@@ -31,13 +31,13 @@ _PY_FILES = {True: [f"data_batch_{i}" for i in range(1, 6)], False: ["test_batch
 
 
 # ------------------------------------------------------------------------------------ file formats
-def _check(images: np.ndarray, labels: np.ndarray, where: str):
+def _check(images: np.ndarray, labels: np.ndarray, where: str, num_classes: int = 10):
     if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (3, 32, 32):
         raise ValueError(f"{where}: images: expected u8 [N,3,32,32], got {images.dtype} {images.shape}")
     if labels.shape != (images.shape[0],):
         raise ValueError(f"{where}: labels: expected [{images.shape[0]}], got {labels.shape}")
-    if labels.size and (int(labels.max()) > 9 or int(labels.min()) < 0):
-        raise ValueError(f"{where}: labels must be in [0, 10)")
+    if labels.size and (int(labels.max()) > num_classes - 1 or int(labels.min()) < 0):
+        raise ValueError(f"{where}: labels must be in [0, {num_classes})")
 
 
 def read_cifar_bin(path: str):
@@ -127,6 +127,86 @@ class CifarBin:
         parts = [read(p) for p in paths]
         self.images = np.concatenate([p[0] for p in parts])
         self.labels = np.concatenate([p[1] for p in parts])
+
+    def __len__(self):
+        return int(self.images.shape[0])
+
+
+# ------------------------------------------------------------------------------------ CIFAR-100
+RECORD100 = 2 + 3 * 32 * 32   # binary version: the coarse label byte, the fine label byte, then the image
+_KINDS100 = {"fine": (1, 100, "fine_labels"), "coarse": (0, 20, "coarse_labels")}   # record byte, classes, pickle key
+
+
+def _kind100(labels: str):
+    if labels not in _KINDS100:
+        raise ValueError(f"labels={labels!r}; expected 'fine' (100 classes) or 'coarse' (20 superclasses)")
+    return _KINDS100[labels]
+
+
+def read_cifar100_bin(path: str, labels: str = "fine"):
+    """(images u8 [N,3,32,32], labels u8 [N]) of train.bin / test.bin of the CIFAR-100 binary version."""
+    col, ncls, _ = _kind100(labels)
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) % RECORD100:
+        raise ValueError(f"{path}: {len(raw)} bytes is not a multiple of the {RECORD100}-byte record")
+    rec = np.frombuffer(raw, dtype=np.uint8).reshape(-1, RECORD100)
+    images, lab = rec[:, 2:].reshape(-1, 3, 32, 32).copy(), rec[:, col].copy()
+    _check(images, lab, path, ncls)
+    return images, lab
+
+
+def write_cifar100_bin(path: str, images: np.ndarray, fine: np.ndarray, coarse: np.ndarray) -> None:
+    """Write u8 images [N,3,32,32] with their fine (< 100) and coarse (< 20) labels as one file of the CIFAR-100
+    binary version — for fixtures and tests."""
+    images = np.ascontiguousarray(images, dtype=np.uint8)
+    fine, coarse = np.ascontiguousarray(fine, dtype=np.uint8), np.ascontiguousarray(coarse, dtype=np.uint8)
+    _check(images, fine, path, 100)
+    _check(images, coarse, path, 20)
+    rec = np.concatenate([coarse[:, None], fine[:, None], images.reshape(len(images), -1)], axis=1)
+    with open(path, "wb") as f:
+        f.write(rec.tobytes())
+
+
+def read_cifar100_py(path: str, labels: str = "fine"):
+    """(images, labels) of the python version's `train` / `test` file (a pickled dict with 'data' u8 [N,3072],
+    'fine_labels' and 'coarse_labels'), through the allow-listed unpickler."""
+    _, ncls, key = _kind100(labels)
+    with open(path, "rb") as f:
+        d = _ArrayUnpickler(io.BytesIO(f.read()), encoding="latin1").load()
+    if not isinstance(d, dict):
+        raise ValueError(f"{path}: expected a pickled dict, got {type(d).__name__}")
+    d = {(k.decode("latin1") if isinstance(k, bytes) else k): v for k, v in d.items()}
+    if "data" not in d or key not in d:
+        raise ValueError(f"{path}: no 'data' / '{key}' entries")
+    data, lab = np.asarray(d["data"]), np.asarray(d[key])
+    if data.dtype != np.uint8 or data.ndim != 2 or data.shape[1] != 3072:
+        raise ValueError(f"{path}: data: expected u8 [N,3072], got {data.dtype} {data.shape}")
+    if lab.ndim != 1 or lab.dtype.kind not in "iu":
+        raise ValueError(f"{path}: {key}: expected integers [N], got {lab.dtype} {lab.shape}")
+    images = np.ascontiguousarray(data.reshape(-1, 3, 32, 32))
+    _check(images, lab, path, ncls)
+    return images, lab.astype(np.uint8)
+
+
+class Cifar100Bin:
+    """The CIFAR-100 split at `root`: the binary version (train.bin / test.bin under root or root/cifar-100-binary) or,
+    failing that, the python version (root/cifar-100-python/train, test). labels="fine" gives the 100 classes,
+    "coarse" the 20 superclasses; num_classes says which. images u8 [N,3,32,32], labels u8 [N]: CifarLoader takes it
+    as it takes CifarBin."""
+
+    def __init__(self, root: str, train: bool = True, labels: str = "fine"):
+        self.num_classes = _kind100(labels)[1]
+        name = "train" if train else "test"
+        for path, read in ((os.path.join(root, name + ".bin"), read_cifar100_bin),
+                           (os.path.join(root, "cifar-100-binary", name + ".bin"), read_cifar100_bin),
+                           (os.path.join(root, "cifar-100-python", name), read_cifar100_py)):
+            if os.path.exists(path):
+                break
+        else:
+            raise FileNotFoundError(f"{name}.bin not found under {root} (or its cifar-100-binary), nor {name} under "
+                                    "its cifar-100-python")
+        self.images, self.labels = read(path, labels)
 
     def __len__(self):
         return int(self.images.shape[0])

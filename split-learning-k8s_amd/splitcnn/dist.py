@@ -48,6 +48,16 @@ IMG_BYTES = 2 * 2 * 32 * 26 * 26
 CUT_ELEMS = 32 * 26 * 26
 
 
+def _ten_classes(who, *stages):
+    """The multi-GPU paths are limited to 10 classes: a stage of an n-class model (wide.WideServerStage at
+    num_classes != 10) is refused here, before anything is allocated or exchanged."""
+    for st in stages:
+        nc = getattr(st, "nc", 10)
+        if nc != 10:
+            raise ValueError(f"splitcnn.dist.{who}: limited to 10 classes, the stage's model has {nc} "
+                             "(train it on one GPU with wide.WideTrainer)")
+
+
 class _Staged:
     """A gloo point-to-point op on a device tensor, staged through host memory. Gloo moves only host
     buffers (the CPU protocol tests and the 1-GPU multi-rank rehearsal use it); RCCL ("nccl") moves
@@ -153,6 +163,7 @@ class Replicated:
 
     def __init__(self, client, server, group=None, device=None, fused: Optional[bool] = None,
                  graph: bool = False, overlap: Optional[bool] = None):
+        _ten_classes("Replicated", client, server)
         _default_optimizer_only("Replicated", client, server)
         self.client, self.server = client, server
         self.fused = _fused_pair(client, server) if fused is None else fused
@@ -313,6 +324,7 @@ class Hub:
     def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, compress=True,
                  server_rank: Optional[int] = None, client_ranks=None, graph: bool = True, groups=None,
                  ship_amax: bool = True, images: bool = False, fuse_codec: bool = True):
+        _ten_classes("Hub", stage)
         _default_optimizer_only(type(self).__name__, stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.fuse_codec = bool(fuse_codec)
@@ -736,6 +748,7 @@ class Pipeline(Hub):
     def __init__(self, stage, role: str, peer: int, micro: int = 4, compress=True, graph: bool = True,
                  groups=None, ship_amax: bool = True, images: bool = False, fuse_codec: bool = True):
         assert role in ("client", "server")
+        _ten_classes("Pipeline", stage)
         _default_optimizer_only("Pipeline", stage)
         me = dist.get_rank()
         super().__init__(stage, me, dist.get_world_size(), None, micro, compress,
@@ -756,6 +769,7 @@ class FedAvg:
     The aggregated client loss is logged for `step` like server_part.py:84 (mlflow.log_metric)."""
 
     def __init__(self, client, server, group=None, device=None):
+        _ten_classes("FedAvg", client, server)
         _default_optimizer_only("FedAvg", client, server)
         self.client, self.server = client, server
         _pair_amax(client, server)
@@ -805,6 +819,7 @@ class UShaped:
     client -> server, pooled and cut_grad server -> client; labels never leave the client."""
 
     def __init__(self, stage, role: str, peer: int, group=None):
+        _ten_classes("UShaped", stage)
         assert role in ("client", "server")
         _default_optimizer_only("UShaped", stage, getattr(stage, "conv", None))   # UClientStage.conv: a ClientStage
         self.stage, self.role, self.peer, self.group = stage, role, peer, group
@@ -889,6 +904,7 @@ class WideHub:
 
     def __init__(self, stage, rank: int, world: int, client_group=None, micro: int = 1, groups=None, codec=None,
                  noise=None, native_head: bool = False):
+        _ten_classes("WideHub", stage)
         _default_optimizer_only("WideHub", stage)
         self.stage, self.rank, self.world = stage, rank, world
         self.server_rank = world - 1

@@ -303,7 +303,7 @@ class GraphedTrainer:
         self._check_weights(weights)
         if metrics is None:
             if self._eval_metrics is None:
-                self._eval_metrics = EvalMetrics(self.device)
+                self._eval_metrics = EvalMetrics(self.device, getattr(self.server, "nc", 10))
             metrics = self._eval_metrics.reset()
         for x, y in batches:
             self.eval_batch(x, y, metrics, weights)

@@ -20,7 +20,7 @@ NCLS = 10
 
 @dataclass
 class EvalResult:
-    """Decoded metrics of an evaluation. confusion[label, pred]; loss = mean over the samples with a valid
+    """Decoded metrics of an evaluation. confusion[label, pred] (num_classes x num_classes); loss = mean over the samples with a valid
     label; per_class_accuracy[c] = confusion[c, c] / samples of class c (NaN for a class never seen)."""
     n: int
     correct: int
@@ -31,14 +31,15 @@ class EvalResult:
     per_class_accuracy: np.ndarray
 
     @classmethod
-    def from_raw(cls, raw) -> "EvalResult":
-        """Decode a raw accumulator (int64 [104], the layout of slk_eval_accumulate): a pure host function."""
+    def from_raw(cls, raw, num_classes: int = NCLS) -> "EvalResult":
+        """Decode a raw accumulator (int64 [4 + num_classes^2], the layout of slk_eval_accumulate / _n): a pure host
+        function."""
         a = np.ascontiguousarray(np.asarray(raw, dtype=np.int64).reshape(-1))
-        if a.size != ops.EVAL_ACC_WORDS:
-            raise ValueError(f"accumulator: expected {ops.EVAL_ACC_WORDS} int64 words, got {a.size}")
+        if a.size != 4 + num_classes * num_classes:
+            raise ValueError(f"accumulator: expected {4 + num_classes * num_classes} int64 words, got {a.size}")
         n, correct, bad = int(a[0]), int(a[1]), int(a[2])
         loss_sum = float(a[3:4].view(np.float64)[0])
-        confusion = a[4:].reshape(NCLS, NCLS).copy()
+        confusion = a[4:].reshape(num_classes, num_classes).copy()
         valid = n - bad
         rows = confusion.sum(axis=1)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -49,9 +50,9 @@ class EvalResult:
                    confusion=confusion, per_class_accuracy=per_class)
 
     def check(self) -> "EvalResult":
-        """Raise if any evaluated label was outside [0, 10) (torch raises IndexError there)."""
+        """Raise if any evaluated label was outside [0, num_classes) (torch raises IndexError there)."""
         if self.bad_labels > 0:
-            raise IndexError("splitcnn: a label was out of range [0, 10)")
+            raise IndexError(f"splitcnn: a label was out of range [0, {self.confusion.shape[0]})")
         return self
 
 
@@ -59,22 +60,27 @@ class EvalMetrics:
     """The device-side metric accumulator: reset(), update(loss_i, pred, labels) per batch (one launch, no
     sync), result() -> EvalResult (one device-to-host copy)."""
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", num_classes: int = NCLS):
         self.device = torch.device(device)
+        # 10 classes keep the 104-word accumulator and slk_eval_accumulate; any other count runs slk_eval_accumulate_n
+        self.num_classes = NCLS if num_classes == NCLS else ops.check_num_classes(num_classes)
         if self.device.type != "cuda":
             raise RuntimeError(f"splitcnn: EvalMetrics on {self.device}; the metrics accumulate on the MI355X HIP "
                                "kernels only. There is no CPU fallback.")
-        self.acc = torch.zeros(ops.EVAL_ACC_WORDS, dtype=torch.int64, device=self.device)
+        self.acc = torch.zeros(4 + self.num_classes ** 2, dtype=torch.int64, device=self.device)
 
     def reset(self) -> "EvalMetrics":
         self.acc.zero_()
         return self
 
     def update(self, loss_i: torch.Tensor, pred: torch.Tensor, labels: torch.Tensor) -> None:
-        ops.eval_accumulate(loss_i, pred, labels, self.acc)
+        if self.num_classes == NCLS:
+            ops.eval_accumulate(loss_i, pred, labels, self.acc)
+        else:
+            ops.eval_accumulate_n(loss_i, pred, labels, self.num_classes, self.acc)
 
     def result(self) -> EvalResult:
-        return EvalResult.from_raw(self.acc.cpu().numpy())
+        return EvalResult.from_raw(self.acc.cpu().numpy(), self.num_classes)
 
 
 def evaluate_logits(logits: torch.Tensor, labels: torch.Tensor, metrics: Optional[EvalMetrics] = None):

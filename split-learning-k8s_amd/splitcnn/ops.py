@@ -1146,3 +1146,100 @@ def dp_noise(out, i0, sigma, max_norm, grad_scale, seed, step):
               _dev(max_norm, "max_norm", (1,)), float(grad_scale), int(seed), _dev(step, "step", (1,), torch.int32),
               _stream(out))
     return out
+
+
+# ------------------------------------------------------------------------------------ widened head, 2..128 classes
+HEADN_MAX_CLASSES = 128
+HEADN_WQ_ELEMS = 2 * 128 * 16384   # bf16 elements of the weight shadow: [128][16384] and its transpose
+
+
+def check_num_classes(nc, who="num_classes") -> int:
+    """nc as an int in [2, 128], the class counts the K5 head serves (ValueError otherwise)."""
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 2 <= nc <= HEADN_MAX_CLASSES:
+        raise ValueError(f"{who}={nc!r}: the widened head serves 2..{HEADN_MAX_CLASSES} classes")
+    return nc
+
+
+def wide_headn_nslab(B: int) -> int:
+    """fc weight-gradient slabs of slk_wide_headn_bwd for B samples (one per 256 samples)."""
+    return _lib.query("slk_wide_headn_nslab", int(B))
+
+
+def wide_headn_work(B: int) -> int:
+    """Floats of the `work` buffer slk_wide_headn_fwd / _bwd need for B samples."""
+    return _lib.query("slk_wide_headn_work", int(B))
+
+
+def wide_fcn_shadow(wf, nc, wq=None):
+    """The bf16 shadow of the fc weight f32 [nc * 16384] the n-class head reads (slk_wide_fcn_shadow): bf16
+    [HEADN_WQ_ELEMS], the C8-ordered rows and their transpose."""
+    nc = check_num_classes(nc)
+    wq = _out(wq, (HEADN_WQ_ELEMS,), wf, torch.bfloat16, "wq")
+    _lib.call("slk_wide_fcn_shadow", _dev(wf, "fc.weight", (nc * 16384,)), nc, _dev(wq, "wq", dtype=torch.bfloat16),
+              _stream(wf))
+    return wq
+
+
+def _headn_common(cut, wq, nc, step, work):
+    B = int(cut.shape[0])
+    if cut.numel() != B * 16384:
+        raise ValueError(f"cut: expected {B} rows of 16384 elements, got {tuple(cut.shape)}")
+    if work.numel() < wide_headn_work(B):
+        raise ValueError(f"work: expected at least {wide_headn_work(B)} floats, got {work.numel()}")
+    return B, (_dev(cut, "cut", dtype=torch.bfloat16), _dev(wq, "wq", (HEADN_WQ_ELEMS,), torch.bfloat16)), \
+        _dev(step, "step", (1,), torch.int32), _dev(work, "work")
+
+
+def wide_headn_fwd(cut, wq, bf, nc, labels, step, seed, keep_threshold, keep_scale, grad_scale, logits, work,
+                   loss_i=None, dlogits=None, err_flag=None, b0=0):
+    """The n-class head's forward (slk_wide_headn_fwd). With labels: logits, loss_i, dlogits (all f32, the caller's)
+    and err_flag (int32 [1]) are written; labels=None writes the logits only and takes none of the three. Returns
+    (logits, loss_i, dlogits)."""
+    nc = check_num_classes(nc)
+    B, (pc, pw), ps, pwork = _headn_common(cut, wq, nc, step, work)
+    if labels is None:
+        if loss_i is not None or dlogits is not None or err_flag is not None:
+            raise ValueError("wide_headn_fwd: labels=None (logits only) takes no loss_i, dlogits or err_flag")
+        tail = (None, None, None)
+    else:
+        tail = (_dev(loss_i, "loss_i", (B,)), _dev(dlogits, "dlogits", (B, nc)), _dev(err_flag, "err_flag", (1,), torch.int32))
+    _lib.call("slk_wide_headn_fwd", pc, pw, _dev(bf, "fc.bias", (nc,)), nc, _labels(labels, B) if labels is not None else None,
+              ps, int(seed) & 0xFFFFFFFF, int(keep_threshold) & 0xFFFFFFFF, float(keep_scale), float(grad_scale),
+              _dev(logits, "logits", (B, nc)), tail[0], tail[1], pwork, tail[2], int(b0), B, _stream(cut))
+    return logits, loss_i, dlogits
+
+
+def wide_headn_bwd(cut, wq, dlogits, nc, step, seed, keep_threshold, keep_scale, dcut, slabs, work, b0=0):
+    """The n-class head's backward from f32 dlogits [B, nc] (slk_wide_headn_bwd): the bf16 cut gradient and the fc
+    weight-gradient slabs [wide_headn_nslab(B), nc * 16384 + nc]. Returns (dcut, slabs)."""
+    nc = check_num_classes(nc)
+    B, (pc, pw), ps, pwork = _headn_common(cut, wq, nc, step, work)
+    _lib.call("slk_wide_headn_bwd", pc, pw, _dev(dlogits, "dlogits", (B, nc)), nc, ps, int(seed) & 0xFFFFFFFF,
+              int(keep_threshold) & 0xFFFFFFFF, float(keep_scale), _dev(dcut, "dcut", tuple(cut.shape), torch.bfloat16),
+              _dev(slabs, "slabs", (wide_headn_nslab(B), nc * 16384 + nc)), pwork, int(b0), B, _stream(cut))
+    return dcut, slabs
+
+
+def eval_logits_n(logits, labels=None, loss_i=None, pred=None, err_flag=None):
+    """eval_logits for f32 [B, nc] logits of any class count 2..128 (slk_eval_logits_n; at nc = 10 the same bits).
+    With labels an err_flag (int32 [1]) is required. Returns (loss_i, pred); labels=None predicts only."""
+    if logits.dim() != 2:
+        raise ValueError(f"logits: expected [B, nc], got {tuple(logits.shape)}")
+    B, nc = int(logits.shape[0]), check_num_classes(int(logits.shape[1]), "logits.shape[1]")
+    pred = _out(pred, (B,), logits, torch.int64, "pred")
+    lptr = liptr = eptr = None
+    if labels is not None:
+        lptr, loss_i = _labels(labels, B), _out(loss_i, (B,), logits, name="loss_i")
+        liptr, eptr = _dev(loss_i, "loss_i"), _dev(err_flag, "err_flag", (1,), torch.int32)
+    _lib.call("slk_eval_logits_n", _dev(logits, "logits"), nc, lptr, B, liptr, _dev(pred, "pred", dtype=torch.int64),
+              eptr, _stream(logits))
+    return (loss_i if labels is not None else None), pred
+
+
+def eval_accumulate_n(loss_i, pred, labels, nc, acc):
+    """eval_accumulate for nc classes: acc is int64 [4 + nc * nc] (slk_eval_accumulate_n)."""
+    nc = check_num_classes(nc)
+    B = batch_of(loss_i, (), "loss_i")
+    _lib.call("slk_eval_accumulate_n", _dev(loss_i, "loss_i", (B,)), _dev(pred, "pred", (B,), torch.int64),
+              _labels(labels, B), nc, B, _dev(acc, "acc", (4 + nc * nc,), torch.int64), _stream(loss_i))
+    return acc

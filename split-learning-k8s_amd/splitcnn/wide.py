@@ -82,15 +82,18 @@ class WideModelPartA(nn.Module):
 
 
 class WideModelPartB(nn.Module):
-    """Server top stack: Dropout(0.25) -> flatten -> Linear(16384, 10). In training mode each forward
-    draws a fresh dropout mask (the hash of seed, forward count, sample, feature — the stages' mask
-    at the same step); eval mode keeps every feature."""
+    """Server top stack: Dropout(0.25) -> flatten -> Linear(16384, num_classes), 2..128 classes. In training mode
+    each forward draws a fresh dropout mask (the hash of seed, forward count, sample, feature — the stages' mask
+    at the same step); eval mode keeps every feature. At num_classes != 10 the forward is the n-class head's
+    logits-only kernel (include/slk.h, "The n-class head") and has no backward (NotImplementedError): train such a
+    head with WideServerStage / WideTrainer."""
 
-    def __init__(self):
+    def __init__(self, num_classes: int = 10):
         super().__init__()
+        ops.check_num_classes(num_classes)
         self.dropout = nn.Dropout(P_DROP)
         self.flatten = nn.Flatten()
-        self.fc = nn.Linear(256 * 8 * 8, 10)
+        self.fc = nn.Linear(256 * 8 * 8, num_classes)
         self.dropout_seed = 0
         self._drop_step = None   # device forward counter (not state: keeps the state_dict contract)
 
@@ -100,7 +103,8 @@ class WideModelPartB(nn.Module):
             self._drop_step = torch.zeros(1, dtype=torch.int32, device=x.device)
         snap = self._drop_step.clone()
         thresh, scale = (KEEP_THRESHOLD, KEEP_SCALE) if self.training else (0, 1.0)
-        logits = _WideHeadFn.apply(x, self.fc.weight, self.fc.bias, snap, self.dropout_seed, thresh, scale)
+        fn = _WideHeadFn if self.fc.out_features == 10 else _WideHeadNFn
+        logits = fn.apply(x, self.fc.weight, self.fc.bias, snap, self.dropout_seed, thresh, scale)
         if self.training:
             ops.tick(self._drop_step)
         return logits
@@ -109,9 +113,9 @@ class WideModelPartB(nn.Module):
 class WideFullModel(nn.Module):
     """The unsplit widened network; parameter names = A ∪ B (like FullModel, src/model_def.py:31-46)."""
 
-    def __init__(self):
+    def __init__(self, num_classes: int = 10):
         super().__init__()
-        a, b = WideModelPartA(), WideModelPartB()
+        a, b = WideModelPartA(), WideModelPartB(num_classes)
         self.conv1, self.conv2, self.conv3 = a.conv1, a.conv2, a.conv3
         self.dropout, self.fc = b.dropout, b.fc
         self._head = [b]   # shares fc / dropout; kept out of the module tree (state_dict keys)
@@ -135,10 +139,10 @@ def get_wide_model(role="client"):
     raise ValueError(f"Unknown LEARNING_MODE: {mode}. Use 'split' or 'federated'.")
 
 
-def init_wide_models(seed: int = 0):
-    """Seeded default init, client (conv1, conv2, conv3) then server (fc)."""
+def init_wide_models(seed: int = 0, num_classes: int = 10):
+    """Seeded default init, client (conv1, conv2, conv3) then server (fc, num_classes rows)."""
     torch.manual_seed(seed)
-    return WideModelPartA(), WideModelPartB()
+    return WideModelPartA(), WideModelPartB(num_classes)
 
 
 class SyntheticCIFAR:
@@ -325,6 +329,30 @@ class _WideHeadFn(torch.autograd.Function):
            thresh, scale, dcut.data_ptr(), slabs.data_ptr(), 0, B, _stream(dlogits))
         g = _reduce(slabs)
         return (c8_to_nchw(dcut).to(ctx.in_dtype), g[:163840].view(10, 16384), g[163840:], None, None, None, None)
+
+
+class _WideHeadNFn(torch.autograd.Function):
+    """_WideHeadFn's forward for a class count other than 10: slk_wide_headn_fwd in its logits-only form."""
+
+    @staticmethod
+    def forward(ctx, cut_nchw, Wf, bf, step, seed, thresh, scale):
+        B, nc = cut_nchw.shape[0], Wf.shape[0]
+        if tuple(cut_nchw.shape[1:]) != (256, 8, 8):
+            raise ValueError(f"cut: expected [B,256,8,8], got {tuple(cut_nchw.shape)}")
+        cut = nchw_to_c8(cut_nchw.detach().to(_BF))
+        with TIMER("wide_fcn_shadow"):
+            wq = ops.wide_fcn_shadow(Wf.detach().contiguous().view(-1), nc)
+        logits = torch.empty((B, nc), dtype=_F32, device=cut.device)
+        work = torch.empty(ops.wide_headn_work(B), dtype=_F32, device=cut.device)
+        with TIMER("wide_headn_fwd"):
+            ops.wide_headn_fwd(cut, wq, bf.detach().contiguous(), nc, None, step, seed, thresh, scale, 0.0, logits, work)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        raise NotImplementedError("splitcnn: WideModelPartB with num_classes != 10 has no module backward; train it "
+                                  "with WideServerStage / WideTrainer (the 10-class module is differentiable)")
+
 
 # ------------------------------------------------------------------------------------ stages
 class _AdamRecipe(StageRecipe):
@@ -562,11 +590,21 @@ class WideServerStage(_AdamRecipe):
         # eps is a constructor constant passed by value, so a captured graph keeps it (no setter)
         self.loss = check_loss(loss)
         self.model = (model if model is not None else WideModelPartB()).to(self.device)
+        # 10 classes run slk_wide_head and its buffers exactly as before; any other count in 2..128 runs the n-class
+        # head (slk_wide_headn_*: include/slk.h, "The n-class head") with hard labels
+        self.nc = nc = ops.check_num_classes(int(self.model.fc.out_features), "fc.out_features")
+        if nc != 10 and self.loss is not None:
+            raise ValueError(f"WideServerStage: loss= (the soft-target head) is limited to 10 classes, the model has {nc}")
+        self.nw, self.nparam = nc * 16384, nc * 16384 + nc
+        self.PAIRS = ((0, self.nparam, self.nw),)
         self.params, self.grads = _flatten_params([self.model.fc.weight, self.model.fc.bias], self.device)
-        assert self.params.numel() == SERVER_NPARAM
+        assert self.params.numel() == self.nparam
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, int(seed)
         self._init_optim(optim, schedule, clip, ema)
-        self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
+        if nc == 10:
+            self.wf8 = torch.empty(163840, dtype=_F32, device=self.device)
+        else:   # the bf16 shadow the n-class head reads, C8-ordered rows and their transpose
+            self.wf8 = torch.empty(ops.HEADN_WQ_ELEMS, dtype=_BF, device=self.device)
         # the averaged fc weight in the cut's order, rebuilt inside every evaluation pass that reads it
         self.wf8_ema = torch.empty_like(self.wf8) if self.ema is not None else None
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -580,8 +618,16 @@ class WideServerStage(_AdamRecipe):
     def _b(self, name, shape, dtype):
         return self._buf.get(name, shape, dtype, self.device)
 
+    def _shadow(self, flat, out):
+        """The head's copy of the fc weight of the flat block `flat`, into `out`."""
+        if self.nc == 10:
+            _k("wide_fc_shadow", flat.data_ptr(), out.data_ptr(), _stream(flat))
+        else:
+            with TIMER("wide_fcn_shadow"):
+                ops.wide_fcn_shadow(flat[:self.nw], self.nc, out)
+
     def refresh_shadows(self):
-        _k("wide_fc_shadow", self.params.data_ptr(), self.wf8.data_ptr(), _stream(self.params))
+        self._shadow(self.params, self.wf8)
 
     def evaluate(self, cut, labels=None, metrics=None, ema: bool = False):
         """Forward only, as WideModelPartB.eval() runs it: slk_wide_head_fwd with every feature kept
@@ -593,19 +639,27 @@ class WideServerStage(_AdamRecipe):
         and of its graph) and the bias is the block's own; the block is not written."""
         B = cut.shape[0]
         _dev(cut, "cut", (B,) + CUT_SHAPE, _BF)
-        logits = self._b("eval_logits", (B, 10), _F32)
+        logits = self._b("eval_logits", (B, self.nc), _F32)
         wf8, flat = self.wf8, self.params
         if ema:
             if self.ema is None:
                 raise RuntimeError("WideServerStage: weights='ema' needs a stage built with ema= (optim.EMA)")
             wf8, flat = self.wf8_ema, self.ema
-            _k("wide_fc_shadow", flat.data_ptr(), wf8.data_ptr(), _stream(cut))
-        _k("wide_head_fwd", cut.data_ptr(), wf8.data_ptr(), flat[163840:].data_ptr(),
-           self.step_ctr.data_ptr(), self.seed, 0, 1.0, logits.data_ptr(), 0, B, _stream(cut))
-        with TIMER("eval_logits"):
-            loss_i, pred = ops.eval_logits(logits, labels,
-                                           loss_i=self._b("eval_loss_i", (B,), _F32) if labels is not None else None,
-                                           pred=self._b("eval_pred", (B,), torch.int64), err_flag=self.eval_err_flag)
+            self._shadow(flat, wf8)
+        outs = dict(loss_i=self._b("eval_loss_i", (B,), _F32) if labels is not None else None,
+                    pred=self._b("eval_pred", (B,), torch.int64))
+        if self.nc == 10:
+            _k("wide_head_fwd", cut.data_ptr(), wf8.data_ptr(), flat[163840:].data_ptr(),
+               self.step_ctr.data_ptr(), self.seed, 0, 1.0, logits.data_ptr(), 0, B, _stream(cut))
+            with TIMER("eval_logits"):
+                loss_i, pred = ops.eval_logits(logits, labels, err_flag=self.eval_err_flag, **outs)
+        else:   # the n-class head's logits-only form at threshold 0, scale 1, then the n-class evaluation kernel
+            with TIMER("wide_headn_fwd"):
+                ops.wide_headn_fwd(cut, wf8, flat[self.nw:], self.nc, None, self.step_ctr, self.seed, 0, 1.0, 0.0,
+                                   logits, self._b("eval_work", (ops.wide_headn_work(B),), _F32))
+            with TIMER("eval_logits_n"):
+                loss_i, pred = ops.eval_logits_n(logits, labels, **outs,
+                                                 err_flag=self.eval_err_flag if labels is not None else None)
         self.eval_logits = logits
         if metrics is not None:
             if labels is None:
@@ -619,11 +673,22 @@ class WideServerStage(_AdamRecipe):
         _dev(cut, "cut", (B,) + CUT_SHAPE, _BF)
         _dev(labels, "labels", (B,), torch.int64)
         s = _stream(cut)
-        logits = self._b("logits", (B, 10), _F32)
+        logits = self._b("logits", (B, self.nc), _F32)
         loss_i = self._b("loss_i", (B,), _F32)
-        dlogits = self._b("dlogits", (B, 10), _F32)
+        dlogits = self._b("dlogits", (B, self.nc), _F32)
         dcut = dcut if dcut is not None else self._b("dcut", (B,) + CUT_SHAPE, _BF)
         _dev(dcut, "dcut", (B,) + CUT_SHAPE, _BF)
+        if self.nc != 10:   # shadow (refresh_shadows) -> fwd -> bwd; the slabs feed the same Adam-from-slabs
+            sf = self._b("sf", (ops.wide_headn_nslab(B), self.nparam), _F32)
+            work = self._b("work", (ops.wide_headn_work(B),), _F32)
+            drop = (self.step_ctr, self.seed, KEEP_THRESHOLD, KEEP_SCALE)
+            with TIMER("wide_headn_fwd"):
+                ops.wide_headn_fwd(cut, self.wf8, self.params[self.nw:], self.nc, labels, *drop, grad_scale, logits,
+                                   work, loss_i=loss_i, dlogits=dlogits, err_flag=self.err_flag, b0=b0)
+            with TIMER("wide_headn_bwd"):
+                ops.wide_headn_bwd(cut, self.wf8, dlogits, self.nc, *drop, dcut, sf, work, b0=b0)
+            self._logits, self._dlogits = logits, dlogits
+            return dcut, loss_i, sf
         sf = self._b("sf", (_q("slk_wide_head_nslab", B), SERVER_NPARAM), _F32)
         work = self._b("work", (_q("slk_wide_head_work", B),), _F32)
         if self.loss is None:
@@ -640,7 +705,7 @@ class WideServerStage(_AdamRecipe):
         return dcut, loss_i, sf
 
     def step_from_slabs(self, sf):
-        self._adamw([(0, SERVER_NPARAM, sf)])
+        self._adamw([(0, self.nparam, sf)])
         self.refresh_shadows()
         self._tick()
 
@@ -664,9 +729,9 @@ class WideServerStage(_AdamRecipe):
         return dcut, loss_i
 
     def check_labels(self):
-        """Raise if any label seen so far was outside [0, 10) or, with loss=, any target was malformed."""
+        """Raise if any label seen so far was outside [0, num_classes) or, with loss=, any target was malformed."""
         if int(self.err_flag.item()) != 0:
-            raise IndexError(LABEL_ERROR)
+            raise IndexError(LABEL_ERROR if self.nc == 10 else f"splitcnn: a label was out of range [0, {self.nc})")
 
     # --- micro-batched / multi-client steps (dist.WideHub): accumulate, then one Adam step
     def accumulate(self, cut, labels, grad_scale: float, b0: int, k: int, nparts: int, dcut=None):
@@ -691,6 +756,8 @@ class WideServerStage(_AdamRecipe):
         writing the cut gradient into `out`: records of format fmt_out, or dense bf16 [B, 128, 8, 8, 8]-shaped rows
         for fmt_out=None. Bitwise MxCut.decode -> forward_backward -> MxCut.encode, with the same stage buffers;
         a malformed record sets records_err_flag(). Returns (out, loss_i, sf)."""
+        if self.nc != 10:
+            raise ValueError(f"WideServerStage: the head on MX records is limited to 10 classes, the model has {self.nc}")
         if self.loss is not None:
             raise ValueError("WideServerStage: the head on MX records has no soft-target form (the stage was built "
                              "with loss=)")
@@ -953,7 +1020,7 @@ class WideTrainer(GraphedTrainer):
         return distance_correlation(x, cut)
 
     def predict(self, x, return_logits: bool = False, weights: str = "live"):
-        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, 10] logits.
+        """pred = argmax of the logits of x (int64 [B]); with return_logits also the f32 [B, num_classes] logits.
         weights="ema": on the averaged weights (optim.EMA)."""
         pred, _ = self._eval_eager(x, None, weights=weights)
         return (pred.clone(), self.server.eval_logits.clone()) if return_logits else pred.clone()
