@@ -1005,7 +1005,10 @@ int slk_wide_head_mx_work(int B);
  * Order inside a training step (wide.WideTrainer(cut_codec=codec.TopKCut(...))): the cut noise if any,
  * slk_cuttopk_roundtrip with the forward k, the head, slk_cuttopk_roundtrip with the backward k in place, the clip's
  * slk_cut_scale_rows if any, the client's backward: straight through, the backward is not masked by the forward's
- * selection.
+ * selection. With TopKCut(k, "masked") ("the masked backward" below) the forward launch is slk_cuttopk_roundtrip_map
+ * into a stage buffer u8 [B, 2048], and where the backward roundtrip stood there is one slk_cuttopk_mask in place on
+ * dcut under that map; everything else keeps its place. Evaluation and prediction are forward only and launch
+ * slk_cuttopk_roundtrip as before.
  * One workgroup of 256 threads per sample; a wave owns 4,096 contiguous elements and reads and writes them as
  * 16-byte pieces, 1 KiB contiguous per instruction. The selection is an exact two-level radix select on the key
  * (mag >> 7 in 256 bins, then mag & 127 in 128 bins over the crossing bin) with one histogram per wave in LDS —
@@ -1019,6 +1022,45 @@ int slk_cuttopk_encode(const void* x_bf16, int n, int k, void* rec, void* stream
 int slk_cuttopk_decode(const void* rec, int n, int k, void* out_bf16, int* err_flag, void* stream);
 int slk_cuttopk_roundtrip(const void* x_bf16, int n, int k, void* out_bf16, void* stream);
 int64_t slk_cuttopk_record_bytes(int k); /* 2064 + 2 k; -1 for a k the rule refuses */
+/* Top-k cut records: the masked backward. The cut gradient travels at the positions the forward kept, as the top-k
+ * split-learning papers have it: the client made the forward's selection itself and still knows it, so the return
+ * record needs no bit map and no selection. k is the forward's k, under the rule above.
+ * Map: u8 [n, 2048], the base 16-byte aligned — the forward record's bit map, bytes 16..2063 of a slk_cuttopk_encode
+ * record: element i is bit i & 7 of byte i >> 3.
+ * slk_cuttopk_roundtrip_map writes out exactly as slk_cuttopk_roundtrip does (out may equal x) and also writes the map
+ * of its selection. A poisoned sample, one with a non-finite element, gets an all-zero map.
+ * slk_cuttopk_mask: out_i = g_i bit for bit where bit i is set, else +0 (0x0000). out may equal g.
+ * Poison: a map whose population count is not k poisons its sample; that covers a poisoned forward, because 0 != k.
+ * For a poisoned sample slk_cuttopk_mask writes 16,384 x 0x7FC0 and slk_cuttopk_gather writes a poisoned record. The
+ * population count is checked before anything is written, and no other sample of the launch is touched.
+ * Kept values travel as raw bf16 bits, non-finite values and -0 included: the gradient is not scanned.
+ * Masked record: u8 [n, 16 + 2 k], records contiguous, the base 16-byte aligned (k = 1024: 2,064 bytes; k = 2048:
+ * 4,112; the top-k record of the same k is 2,048 bytes longer; the dense row is 32,768).
+ *   bytes 0..15   header: uint32 words, little endian: word 0 = k, word 1 = 0x21 (disjoint from 0x20, 0x10, 0x11, 0
+ *                 and 1, so every decoder reports the others' records as malformed), word 2 = 1 for a poisoned
+ *                 sample and 0 otherwise, word 3 = 0.
+ *   bytes 16..    the k values under the map's set bits as raw bf16 bits, in ascending element index; all zero in a
+ *                 poisoned record.
+ * slk_cuttopk_scatter is bitwise slk_cuttopk_mask's output for slk_cuttopk_gather's record under the same map. A
+ * poisoned record gives 16,384 x 0x7FC0 without touching err_flag, and neither its payload nor the map is looked at.
+ * A malformed record gives 16,384 x 0x7FC0 for its sample and stores err_flag[0] = 1 (a plain store; nobody clears
+ * it); the other samples decode as usual. Malformed is any of: word 0 != the k passed to the call; word 1 != 0x21;
+ * word 2 > 1; word 3 != 0; an unpoisoned record offered with a map whose population count is not k.
+ * Identities: mask == scatter(gather), and mask is idempotent.
+ * One workgroup of 256 threads per sample in the family's piece ownership: in round r lane l of a wave holds 16-byte
+ * piece 64 r + l of the wave's 4,096 elements, and its share of the map is that piece's byte. Ranks are population
+ * counts: a wave prefix sum of the lanes' byte counts, two rounds packed per scan, the rounds accumulated in order and
+ * the waves' bases passed through LDS; the block's total is the poison check. gather compacts through a 16 KiB LDS
+ * stage and stores 16-byte pieces, scatter stages the values and fetches by rank, mask moves no value out of its
+ * lane. Every output byte has one writer; no global atomics, no scratch; the bits repeat from run to run.
+ * Every pointer is required. n == 0 launches nothing and returns 0. Refused before any launch, in this order: n < 0
+ * or k < 0, then a NULL pointer or a pointer that is not 16-byte aligned (err_flag: 4-byte), with
+ * hipErrorInvalidValue; then a k that is not a multiple of 8 in [8, 8192] with hipErrorInvalidConfiguration (9). */
+int slk_cuttopk_roundtrip_map(const void* x_bf16, int n, int k, void* out_bf16, void* map, void* stream);
+int slk_cuttopk_mask(const void* g_bf16, const void* map, int n, int k, void* out_bf16, void* stream);
+int slk_cuttopk_gather(const void* g_bf16, const void* map, int n, int k, void* rec, void* stream);
+int slk_cuttopk_scatter(const void* rec, const void* map, int n, int k, void* out_bf16, int* err_flag, void* stream);
+int64_t slk_cuttopk_masked_record_bytes(int k); /* 16 + 2 k; -1 for a k the rule refuses */
 /* Cut noise (csrc/slk_cut_noise.hip): an opt-in defence of the K5 cut against model inversion — a per-sample norm
  * bound, then additive noise from a 1,024-entry table. An experiment's tool, not a certified mechanism: no epsilon
  * is claimed. A sample is the 16,384 contiguous bf16 elements of one cut row, as in the FP8 records. All float

@@ -379,9 +379,170 @@ __global__ __launch_bounds__(THREADS) void cuttopk_decode_kernel(const uint8_t* 
     }
     store_sample(o, s);
 }
+
+// ---- The masked backward ("Top-k cut records: the masked backward"): the cut gradient travels at the positions the
+// forward kept. The selection is given — the forward's bit map, u8 [n, 2048] — so there is no select: a thread's
+// share of the map is one byte per round (piece p is map byte p), the ranks are piece_ranks over those bytes, and
+// the block-wide popcount that falls out of them is the poison check (a map that does not hold k bits).
+constexpr uint32_t MASKED_FMT_WORD = 0x21u;
+inline size_t masked_record_bytes(int k) { return (size_t)HEADER + 2u * (size_t)k; }
+
+// The thread's eight map bytes, byte j = round j: a wave's load covers 64 contiguous bytes.
+__device__ __forceinline__ uint64_t load_map(const uint8_t* map) {
+    uint64_t m = 0;
+#pragma unroll
+    for (int j = 0; j < ROUNDS; ++j) m |= (uint64_t)map[piece_of(j)] << (8 * j);
+    return m;
+}
+
+// How many bits the block's masks hold. One barrier; red holds WAVES words of its own.
+__device__ __forceinline__ uint32_t block_popcount(uint64_t m, uint32_t* red) {
+    uint32_t c = (uint32_t)__popcll(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+    if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// slk_cuttopk_roundtrip that also leaves its selection: the kept bytes go through a 2 KiB LDS byte map and leave as
+// 128 16-byte stores. A kernel of its own, so that cuttopk_roundtrip_kernel's code stays what it is.
+__global__ __launch_bounds__(THREADS) void cuttopk_roundtrip_map_kernel(const uint16_t* x, uint32_t k, uint16_t* out,
+                                                                        uint8_t* __restrict__ map) {
+    __shared__ SelectLds L;
+    __shared__ RankLds W;
+    __shared__ __attribute__((aligned(16))) uint8_t bitmap[PIECES];
+    Sample s;
+    load_sample(x + (size_t)blockIdx.x * SAMPLE, s);
+    uint16_t* o = out + (size_t)blockIdx.x * SAMPLE;
+    u32x4* bm_out = reinterpret_cast<u32x4*>(map + (size_t)blockIdx.x * PIECES);
+    const Threshold t = select(s, k, L);
+    if (t.poison) {   // uniform
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        if (threadIdx.x < PIECES / 16) bm_out[threadIdx.x] = zero;
+        nan_sample(s);
+        store_sample(o, s);
+        return;
+    }
+    uint64_t gt, eq;
+    masks(s, t.T, gt, eq);
+    uint32_t eq_rank[ROUNDS], neq;
+    piece_ranks(eq, W.eq, eq_rank, neq);
+    const uint64_t kept = kept_mask(gt, eq, eq_rank, t.r);
+#pragma unroll
+    for (int j = 0; j < ROUNDS; ++j) bitmap[piece_of(j)] = (uint8_t)byte_of(kept, j);
+    sparsify(s, kept);
+    store_sample(o, s);
+    __syncthreads();
+    if (threadIdx.x < PIECES / 16) bm_out[threadIdx.x] = reinterpret_cast<const u32x4*>(bitmap)[threadIdx.x];
+}
+
+// out = bit set ? g : +0; g and out are not __restrict__: they may be the same buffer (as in the roundtrip). No value
+// leaves its lane: the map byte of a piece is the byte mask of that piece's eight elements.
+__global__ __launch_bounds__(THREADS) void cuttopk_mask_kernel(const uint16_t* g, const uint8_t* __restrict__ map,
+                                                               uint32_t k, uint16_t* out) {
+    __shared__ uint32_t red[WAVES];
+    Sample s;
+    load_sample(g + (size_t)blockIdx.x * SAMPLE, s);
+    const uint64_t m = load_map(map + (size_t)blockIdx.x * PIECES);
+    if (block_popcount(m, red) != k)   // uniform, and before anything is written
+        nan_sample(s);
+    else
+        sparsify(s, m);
+    store_sample(out + (size_t)blockIdx.x * SAMPLE, s);
+}
+
+// The k values under the map's bits, compacted in index order through the LDS stage into a masked record.
+__global__ __launch_bounds__(THREADS) void cuttopk_gather_kernel(const uint16_t* __restrict__ g,
+                                                                 const uint8_t* __restrict__ map, uint32_t k,
+                                                                 uint8_t* __restrict__ rec) {
+    __shared__ RankLds W;
+    __shared__ __attribute__((aligned(16))) uint16_t stage[K_MAX];
+    uint8_t* r = rec + (size_t)blockIdx.x * (HEADER + 2u * (size_t)k);
+    Sample s;
+    load_sample(g + (size_t)blockIdx.x * SAMPLE, s);
+    const uint64_t m = load_map(map + (size_t)blockIdx.x * PIECES);
+    uint32_t rank[ROUNDS], total;
+    piece_ranks(m, W.gt, rank, total);
+    const bool poison = total != k;   // uniform, and before anything is written
+    if (threadIdx.x == 0) {
+        const u32x4 head = {k, MASKED_FMT_WORD, poison ? 1u : 0u, 0u};
+        *reinterpret_cast<u32x4*>(r) = head;
+    }
+    u32x4* val_out = reinterpret_cast<u32x4*>(r + HEADER);
+    const uint32_t nval = k / 8u;
+    if (poison) {
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        for (uint32_t i = threadIdx.x; i < nval; i += THREADS) val_out[i] = zero;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < ROUNDS; ++j) {
+        const uint32_t b = byte_of(m, j);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if ((b >> e) & 1u) {
+                const uint32_t slot = rank[j] + (uint32_t)__popc(b & ((1u << e) - 1u));   // < total == k
+                stage[slot & (K_MAX - 1)] = (uint16_t)elem(s.v[j], e);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nval; i += THREADS) val_out[i] = reinterpret_cast<const u32x4*>(stage)[i];
+}
+
+// A masked record back to a dense row: the values staged in LDS, then every set bit fetches its own by rank.
+__global__ __launch_bounds__(THREADS) void cuttopk_scatter_kernel(const uint8_t* __restrict__ rec,
+                                                                  const uint8_t* __restrict__ map, uint32_t k,
+                                                                  uint16_t* __restrict__ out, int* __restrict__ err_flag) {
+    __shared__ RankLds W;
+    __shared__ __attribute__((aligned(16))) uint16_t stage[K_MAX];
+    const uint8_t* r = rec + (size_t)blockIdx.x * (HEADER + 2u * (size_t)k);
+    uint16_t* o = out + (size_t)blockIdx.x * SAMPLE;
+    const u32x4 head = *reinterpret_cast<const u32x4*>(r);
+    const bool bad_head = head[0] != k || head[1] != MASKED_FMT_WORD || head[2] > 1u || head[3] != 0u;
+    Sample s;
+    if (bad_head || head[2] == 1u) {   // uniform: malformed, or poisoned (neither payload nor map is looked at)
+        if (bad_head && threadIdx.x == 0) err_flag[0] = 1;
+        nan_sample(s);
+        store_sample(o, s);
+        return;
+    }
+    const uint32_t nval = k / 8u;
+    for (uint32_t i = threadIdx.x; i < nval; i += THREADS)
+        reinterpret_cast<u32x4*>(stage)[i] = reinterpret_cast<const u32x4*>(r + HEADER)[i];
+    const uint64_t m = load_map(map + (size_t)blockIdx.x * PIECES);
+    uint32_t rank[ROUNDS], total;
+    piece_ranks(m, W.gt, rank, total);   // its barrier also publishes the stage
+    if (total != k) {                    // uniform, and before anything is written or gathered
+        if (threadIdx.x == 0) err_flag[0] = 1;
+        nan_sample(s);
+        store_sample(o, s);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < ROUNDS; ++j) {
+        const uint32_t b = byte_of(m, j);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int e = 2 * i + h;
+                if ((b >> e) & 1u) {
+                    const uint32_t slot = rank[j] + (uint32_t)__popc(b & ((1u << e) - 1u));   // < total == k
+                    w |= (uint32_t)stage[slot & (K_MAX - 1)] << (16 * h);
+                }
+            }
+            s.v[j][i] = w;
+        }
+    }
+    store_sample(o, s);
+}
 }  // namespace
 
 extern "C" int64_t slk_cuttopk_record_bytes(int k) { return k_ok(k) ? (int64_t)record_bytes(k) : -1; }
+extern "C" int64_t slk_cuttopk_masked_record_bytes(int k) { return k_ok(k) ? (int64_t)masked_record_bytes(k) : -1; }
 
 // Refusals in this order: negative counts, then n == 0 (nothing looked at), then the pointers, then k against the rule.
 extern "C" int slk_cuttopk_encode(const void* x_bf16, int n, int k, void* rec, void* stream) {
@@ -412,5 +573,49 @@ extern "C" int slk_cuttopk_roundtrip(const void* x_bf16, int n, int k, void* out
     if (!k_ok(k)) return (int)hipErrorInvalidConfiguration;
     cuttopk_roundtrip_kernel<<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(static_cast<const uint16_t*>(x_bf16),
                                                                            (uint32_t)k, static_cast<uint16_t*>(out_bf16));
+    return slk_launch_status();
+}
+
+// The masked backward's entries: the family's refusals in the family's order; every pointer is required.
+extern "C" int slk_cuttopk_roundtrip_map(const void* x_bf16, int n, int k, void* out_bf16, void* map, void* stream) {
+    SLK_CHECK_ARG(n >= 0 && k >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(x_bf16 && out_bf16 && map && aligned16(x_bf16) && aligned16(out_bf16) && aligned16(map));
+    if (!k_ok(k)) return (int)hipErrorInvalidConfiguration;
+    cuttopk_roundtrip_map_kernel<<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(
+        static_cast<const uint16_t*>(x_bf16), (uint32_t)k, static_cast<uint16_t*>(out_bf16), static_cast<uint8_t*>(map));
+    return slk_launch_status();
+}
+
+extern "C" int slk_cuttopk_mask(const void* g_bf16, const void* map, int n, int k, void* out_bf16, void* stream) {
+    SLK_CHECK_ARG(n >= 0 && k >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(g_bf16 && map && out_bf16 && aligned16(g_bf16) && aligned16(map) && aligned16(out_bf16));
+    if (!k_ok(k)) return (int)hipErrorInvalidConfiguration;
+    cuttopk_mask_kernel<<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(
+        static_cast<const uint16_t*>(g_bf16), static_cast<const uint8_t*>(map), (uint32_t)k, static_cast<uint16_t*>(out_bf16));
+    return slk_launch_status();
+}
+
+extern "C" int slk_cuttopk_gather(const void* g_bf16, const void* map, int n, int k, void* rec, void* stream) {
+    SLK_CHECK_ARG(n >= 0 && k >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(g_bf16 && map && rec && aligned16(g_bf16) && aligned16(map) && aligned16(rec));
+    if (!k_ok(k)) return (int)hipErrorInvalidConfiguration;
+    cuttopk_gather_kernel<<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(
+        static_cast<const uint16_t*>(g_bf16), static_cast<const uint8_t*>(map), (uint32_t)k, static_cast<uint8_t*>(rec));
+    return slk_launch_status();
+}
+
+extern "C" int slk_cuttopk_scatter(const void* rec, const void* map, int n, int k, void* out_bf16, int* err_flag,
+                                   void* stream) {
+    SLK_CHECK_ARG(n >= 0 && k >= 0);
+    if (n == 0) return 0;
+    SLK_CHECK_ARG(rec && map && out_bf16 && err_flag && aligned16(rec) && aligned16(map) && aligned16(out_bf16));
+    SLK_CHECK_ARG((reinterpret_cast<uintptr_t>(err_flag) & 3u) == 0);
+    if (!k_ok(k)) return (int)hipErrorInvalidConfiguration;
+    cuttopk_scatter_kernel<<<(unsigned)n, THREADS, 0, slk_stream(stream)>>>(
+        static_cast<const uint8_t*>(rec), static_cast<const uint8_t*>(map), (uint32_t)k, static_cast<uint16_t*>(out_bf16),
+        err_flag);
     return slk_launch_status();
 }

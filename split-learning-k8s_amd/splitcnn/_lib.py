@@ -134,6 +134,12 @@ _SIGS = {
     "slk_cuttopk_decode": [_P, _I, _I, _P, _P, _P],
     "slk_cuttopk_roundtrip": [_P, _I, _I, _P, _P],
     "slk_cuttopk_record_bytes": [_I],
+    # the masked backward: the cut gradient at the forward's positions (codec.TopKCut(k, "masked"))
+    "slk_cuttopk_roundtrip_map": [_P, _I, _I, _P, _P, _P],
+    "slk_cuttopk_mask": [_P, _P, _I, _I, _P, _P],
+    "slk_cuttopk_gather": [_P, _P, _I, _I, _P, _P],
+    "slk_cuttopk_scatter": [_P, _P, _I, _I, _P, _P, _P],
+    "slk_cuttopk_masked_record_bytes": [_I],
     # per-sample clip + table noise on the K5 cut (privacy.CutNoise)
     "slk_cut_noise": [_P, _I, _P, _F, _P, _P, _U, _P, _I, _P, _P, _P],
     "slk_cut_scale_rows": [_P, _I, _P, _P, _P],
@@ -189,6 +195,7 @@ _SIGS = {
 _RESTYPES = {"slk_error_string": ctypes.c_char_p, "slk_build_id": ctypes.c_char_p, "slk_conv2_act16_bytes": ctypes.c_int64,
              "slk_relu_bits_bytes": ctypes.c_int64, "slk_cut8_record_bytes": ctypes.c_int64,
              "slk_cutmx_record_bytes": ctypes.c_int64, "slk_cuttopk_record_bytes": ctypes.c_int64,
+             "slk_cuttopk_masked_record_bytes": ctypes.c_int64,
              "slk_dcor_workspace_bytes": ctypes.c_int64,
              "slk_dcor_grad_workspace_bytes": ctypes.c_int64}
 

@@ -29,6 +29,8 @@ CUTMX_FORMATS = {"e2m1": 0, "e4m3": 1}
 CUTMX_RECORD = {"e2m1": 8720, "e4m3": 16912}   # a 16-byte header, 512 scale bytes, 4- or 8-bit codes
 CUTTOPK_K = (8, 8192)    # the k of a top-k record: a multiple of 8 in this range
 CUTTOPK_HEAD = 2064      # a 16-byte header and a 2,048-byte bit map; then k bf16 values
+CUTTOPK_MAP = 2048       # bytes of one sample's bit map: element i is bit i & 7 of byte i >> 3
+CUTTOPK_MASKED_HEAD = 16  # a masked-backward record: the header, then the forward's k bf16 values
 
 
 class CutCodec:
@@ -359,19 +361,30 @@ class TopKCut:
     may be None, which leaves that direction dense bf16. k is a constructor constant passed to the kernels by value: a
     captured graph keeps it, and there is no setter. Nothing is rounded (rounding_of is always "nearest").
 
+    bwd="masked" is the papers' backward (include/slk.h, "Top-k cut records: the masked backward"): the cut gradient
+    travels at the positions the forward kept and is +0 elsewhere. The forward's selection is a bit map, uint8
+    [n, 2048], 16-byte aligned, that roundtrip(x, out, "fwd", map=m) writes beside `out`; every "bwd" method then
+    takes the same map=: roundtrip masks (out may be g), encode gathers the fwd values under the map into a record of
+    16 + 2 fwd bytes (no bit map travels back: the client made the selection and still knows it), decode scatters it.
+    A map that does not hold fwd bits — a poisoned forward's is all zero — poisons its sample: NaNs, or a poisoned
+    record. The gradient itself is not scanned: a kept non-finite value travels as it is.
+
     A sample is 16,384 contiguous bf16 elements: x / out are [n, ...] with 16,384 elements per row, records are uint8
     [n, record_bytes(direction)]. The surface is MxCut's: every method works on caller-visible buffers and launches on
     the tensor's current stream; encode / roundtrip accept and ignore step= / row0=."""
 
     def __init__(self, fwd=2048, bwd=None):
         for name, v in (("fwd", fwd), ("bwd", bwd)):
-            if v is None:
+            if v is None or (name == "bwd" and isinstance(v, str) and v == "masked"):
                 continue
             lo, hi = CUTTOPK_K
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi or v % 8:
-                raise ValueError(f"TopKCut: {name}={v!r}; expected k, a multiple of 8 with {lo} <= k <= {hi}, or None")
+                raise ValueError(f"TopKCut: {name}={v!r}; expected k, a multiple of 8 with {lo} <= k <= {hi}, or None"
+                                 + (", or 'masked'" if name == "bwd" else ""))
         if fwd is None and bwd is None:
             raise ValueError("TopKCut: fwd and bwd are both None — that is the dense exchange (pass no codec)")
+        if bwd == "masked" and fwd is None:
+            raise ValueError("TopKCut: bwd='masked' needs fwd=k: with fwd=None there is no selection to mask by")
         self.fwd, self.bwd = fwd, bwd
         self._bufs = {}
 
@@ -388,24 +401,41 @@ class TopKCut:
         return self
 
     def format(self, direction: str):
-        """The k of "fwd" / "bwd", or None where that direction stays dense."""
+        """The k of "fwd" / "bwd", None where that direction stays dense, or "masked" (bwd only)."""
         if direction not in ("fwd", "bwd"):
             raise ValueError(f"TopKCut: direction {direction!r}; expected 'fwd' or 'bwd'")
         return self.fwd if direction == "fwd" else self.bwd
+
+    def _masked(self, direction: str) -> bool:
+        return self.format(direction) == "masked"
 
     def _k(self, direction: str) -> int:
         k = self.format(direction)
         if k is None:
             raise ValueError(f"TopKCut: the {direction} direction is dense (built with {direction}=None)")
-        return k
+        return self.fwd if k == "masked" else k
 
     def record_bytes(self, direction: str) -> int:
-        """Bytes of one sample's record in "fwd" / "bwd": 2,064 + 2 k."""
-        return CUTTOPK_HEAD + 2 * self._k(direction)
+        """Bytes of one sample's record in "fwd" / "bwd": 2,064 + 2 k; 16 + 2 fwd for the masked backward."""
+        return (CUTTOPK_MASKED_HEAD if self._masked(direction) else CUTTOPK_HEAD) + 2 * self._k(direction)
 
     def _records(self, rec, n, direction, name="rec"):
         _dev(rec, name, (n, self.record_bytes(direction)), torch.uint8)
         Fp8Cut._aligned(rec, name)
+
+    def _map(self, map, n, direction, like):
+        """The checked data pointer of map= (uint8 [n, 2048], 16-byte aligned, on `like`'s device); None without one
+        in a direction that does not need it."""
+        if map is None:
+            if self._masked(direction):
+                raise ValueError("TopKCut: the masked backward needs map=, the uint8 [n, 2048] bit map that "
+                                 "roundtrip(x, out, 'fwd', map=...) wrote")
+            return None
+        _dev(map, "map", (n, CUTTOPK_MAP), torch.uint8)
+        if map.device != like.device:
+            raise ValueError(f"map: on {map.device}, the tensor is on {like.device}")
+        Fp8Cut._aligned(map, "map")
+        return map.data_ptr()
 
     def records(self, key, n: int, device, direction=None):
         """The uint8 [n, record_bytes(direction)] record buffer of `key`; `direction` is required: the two directions
@@ -421,29 +451,51 @@ class TopKCut:
             self._bufs[k] = t
         return t
 
-    def encode(self, x, rec, direction: str = "fwd", step=None, row0: int = 0):
-        """x (bf16 [n, ...]) -> rec (uint8 [n, record_bytes(direction)]) with `direction`'s k."""
+    def encode(self, x, rec, direction: str = "fwd", step=None, row0: int = 0, map=None):
+        """x (bf16 [n, ...]) -> rec (uint8 [n, record_bytes(direction)]) with `direction`'s k. The masked backward
+        gathers x's values under map= instead of selecting; elsewhere map= is not accepted."""
         k, n = self._k(direction), Fp8Cut._rows(x, "x")
         self._records(rec, n, direction)
+        if self._masked(direction):
+            _lib.call("slk_cuttopk_gather", x.data_ptr(), self._map(map, n, direction, x), n, k, rec.data_ptr(),
+                      _stream(x))
+            return rec
+        if map is not None:
+            raise ValueError("TopKCut.encode: map= belongs to the masked backward; a record carries its own bit map")
         _lib.call("slk_cuttopk_encode", x.data_ptr(), n, k, rec.data_ptr(), _stream(x))
         return rec
 
-    def decode(self, rec, out, err_flag, direction: str = "fwd"):
+    def decode(self, rec, out, err_flag, direction: str = "fwd", map=None):
         """rec -> out (bf16 [n, ...]); a malformed record (a wrong header word, another k, a bit map that does not
         hold k bits) decodes its sample to NaNs and sets err_flag (int32 [1]); a poisoned record (its sample had a
-        non-finite element) decodes to NaNs without the flag."""
+        non-finite element) decodes to NaNs without the flag. The masked backward scatters the record's values to
+        the set bits of map=; elsewhere map= is not accepted."""
         k, n = self._k(direction), Fp8Cut._rows(out, "out")
         self._records(rec, n, direction)
         _dev(err_flag, "err_flag", (1,), torch.int32)
+        if self._masked(direction):
+            _lib.call("slk_cuttopk_scatter", rec.data_ptr(), self._map(map, n, direction, out), n, k, out.data_ptr(),
+                      err_flag.data_ptr(), _stream(out))
+            return out
+        if map is not None:
+            raise ValueError("TopKCut.decode: map= belongs to the masked backward; a record carries its own bit map")
         _lib.call("slk_cuttopk_decode", rec.data_ptr(), n, k, out.data_ptr(), err_flag.data_ptr(), _stream(out))
         return out
 
-    def roundtrip(self, x, out, direction: str, step=None, row0: int = 0):
-        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x."""
+    def roundtrip(self, x, out, direction: str, step=None, row0: int = 0, map=None):
+        """out = decode(encode(x)) bit for bit in one launch, no record in memory; out may be x. With map= (uint8
+        [n, 2048]) the selection's bit map is written there too; map=None is the plain launch. In the masked
+        backward map= is read: out = x under its set bits, +0 elsewhere."""
         k, n = self._k(direction), Fp8Cut._rows(x, "x")
         if Fp8Cut._rows(out, "out") != n:
             raise ValueError(f"out: expected {n} samples like x, got {out.shape[0]}")
-        _lib.call("slk_cuttopk_roundtrip", x.data_ptr(), n, k, out.data_ptr(), _stream(x))
+        m = self._map(map, n, direction, x)
+        if self._masked(direction):
+            _lib.call("slk_cuttopk_mask", x.data_ptr(), m, n, k, out.data_ptr(), _stream(x))
+        elif m is not None:
+            _lib.call("slk_cuttopk_roundtrip_map", x.data_ptr(), n, k, out.data_ptr(), m, _stream(x))
+        else:
+            _lib.call("slk_cuttopk_roundtrip", x.data_ptr(), n, k, out.data_ptr(), _stream(x))
         return out
 
 

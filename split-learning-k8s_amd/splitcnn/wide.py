@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
-from .codec import Fp8Cut, MxCut, TopKCut, check_cut_codec
+from .codec import CUTTOPK_MAP, Fp8Cut, MxCut, TopKCut, check_cut_codec
 from .engine import TIMER, LossLog, _Buffers
 from .graphs import GraphedTrainer
 from .loss import LABEL_ERROR, SoftCrossEntropy, check_loss
@@ -832,7 +832,11 @@ class WideTrainer(GraphedTrainer):
     slk_cutmx_roundtrip launches at the same two places, always to nearest, evaluation and prediction included.
     A codec.TopKCut runs the top-k sparsification (include/slk.h, "Top-k cut records") there: slk_cuttopk_roundtrip
     with the direction's k. The backward is straight through: the client back-propagates the server's whole dcut,
-    sparsified by its own k if bwd is set, not masked by the forward's selection.
+    sparsified by its own k if bwd is set, not masked by the forward's selection. TopKCut(k, "masked") is the papers'
+    backward instead: the forward launch is slk_cuttopk_roundtrip_map, which also leaves the selection's bit map in
+    the server-stage buffer `cut_map` (uint8 [B, 2048]), and in the backward roundtrip's place one slk_cuttopk_mask
+    zeroes dcut in place wherever the forward dropped the activation — no second selection. evaluate / eval_batch /
+    predict are forward only and keep slk_cuttopk_roundtrip.
 
     `cut_noise` (privacy.CutNoise) puts a noise defence on the cut, inside the captured step: the cut is clipped per
     sample and noised (slk_cut_noise) into the server-stage buffer `cut_n` under the client's step_ctr with row0 = 0,
@@ -902,6 +906,12 @@ class WideTrainer(GraphedTrainer):
         if step is None:
             q = q.nearest()
         out = self.server._b(name, tuple(t.shape), _BF) if name is not None else t
+        if step is not None and isinstance(q, TopKCut) and q.format("bwd") == "masked":
+            # a training step of the masked backward: the forward leaves its selection in the stage buffer cut_map,
+            # the backward masks dcut by it in place (evaluation is forward only: the plain launch below)
+            with TIMER("cuttopk_roundtrip_map" if direction == "fwd" else "cuttopk_mask"):
+                return q.roundtrip(t, out, direction, map=self.server._b("cut_map", (t.shape[0], CUTTOPK_MAP),
+                                                                         torch.uint8))
         with TIMER("cuttopk_roundtrip" if isinstance(q, TopKCut) else
                    "cutmx_roundtrip" if isinstance(q, MxCut) else "cut8_roundtrip"):
             if q.rounding_of(direction) == "stochastic":
